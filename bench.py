@@ -15,9 +15,11 @@ One UNROLL = what the reference does between `reset` and the last `fx` (SURVEY.m
 (one of a ring of --instances pre-sampled instances already resident in HBM) -> rewind x / LSTM state -> T x {f(x), grad f,
 LSTM optimizer step, x += delta} -> f(x_T) -> per-step loss reduction (-> all-reduce of the T+1 partial losses
 over ranks when N > 1).  One bench "step" = --unrolls-per-step consecutive unrolls (default per config, so that
---steps 20 times >= --min-timed-seconds = 1 s of GPU work: config 2 -> 278 unrolls per step; `sustained` compares the
-first and the last tenth of the timed steps); value counts every one of them.  Inputs are resident in HBM when the
-timed region starts; nothing is copied to the host inside it.
+20 steps time >= --min-timed-seconds = 1 s of GPU work: config 2 -> 278 unrolls per step, whatever --steps says;
+`sustained` compares the first and the last tenth of the timed steps); value counts every one of them.  --steps K times
+exactly K steps and ms_per_step is one of them.  Inputs are resident in HBM when the timed region starts; nothing is
+copied to the host inside it.  --dump-outputs DIR writes what the last timed unroll computed (seeded inputs: the same
+arrays on every run with the same arguments).
 
     python bench.py --gpus N --steps K --warmup W     (N > 1 without WORLD_SIZE: re-launches itself under
                                                        torch.distributed.run, one rank per GPU, 127.0.0.1)
@@ -54,6 +56,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK = 8.0e12          # MI355X_MICROARCH.md: 8 TB/s spec
 FP32_PEAK = 157.3e12
 N_SIMD = 256 * 4           # 256 CUs x 4 SIMDs
+STEPS_PER_MIN_TIMED = 20   # the default --unrolls-per-step makes this many steps (the default --steps) >= --min-timed-seconds
+DUMP_BYTES = 64 * 10 ** 6 - 64 * 1024   # --dump-outputs: array data in all (the rest of 64 MB is left to the .npy headers)
 PARITY_PIN = ("reference KATs (tests/golden/reference_kats.json: meta_test / problems_test / preprocess_test / "
               "networks_test values) + torch.nn.LSTMCell for the LSTM cell; dm-sonnet 1.11 / TF 1.14 are absent, so "
               "the cell's gate order and forget bias are pinned to Sonnet's published source, not to a reference run")
@@ -350,6 +354,7 @@ class ReplicaGraph(object):
         self.reps = reps
         self.x, self.constants = [], []
         self.last_path = None
+        self.last_fx = None                                  # every replica's fx[0..T] of the last launch
         self._x0 = None
 
     def reset(self):
@@ -371,10 +376,43 @@ class ReplicaGraph(object):
         if events is not None:
             events[1].record()
         self.last_path = "mlp_unroll"
+        self.last_fx = fx
         return fx[0], None
 
     def wait_fx(self):
         pass
+
+
+def timed_outputs(graph, eng, fx_host):
+    """What the last timed unroll handed its caller, copied to the host: the losses fx[0..T] (all-reduced when sharded)
+    and every optimizee variable at x_T (this rank's shard when sharded); one set per replica for a ReplicaGraph."""
+    def var(v):
+        return "x_T_" + "".join(c if c.isalnum() else "_" for c in v.name.split(":")[0])
+    if isinstance(graph, ReplicaGraph):
+        out = {}
+        for r, (g, fx) in enumerate(zip(graph.reps.graphs, graph.last_fx)):
+            out["replica%d_fx" % r] = eng.to_numpy(fx)
+            out.update(("replica%d_%s" % (r, var(v)), eng.to_numpy(v.value)) for v in g.x)
+        return out
+    out = {"fx": fx_host}
+    out.update((var(v), eng.to_numpy(v.value)) for v in graph.x)
+    return out
+
+
+def write_outputs(path, outputs):
+    """--dump-outputs: DIR/<name>.npy in float32.  Beyond DUMP_BYTES in all, every array keeps the same share of its
+    elements: a fixed seeded sample of its flattened elements, in index order (the same elements on every run)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(a, np.float32) for k, a in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    share = min(1.0, DUMP_BYTES / float(total)) if total else 1.0
+    for name, a in sorted(arrays.items()):
+        if share < 1.0:
+            pick = np.random.default_rng(0).choice(a.size, int(a.size * share), replace=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        np.save(os.path.join(path, name + ".npy"), a)
+    print("bench.py: %d output arrays -> %s%s" % (len(arrays), path, "" if share == 1.0 else
+                                                 " (a seeded sample of %.3g of each)" % share), file=sys.stderr)
 
 
 def parse_args(argv=None):
@@ -392,7 +430,7 @@ def parse_args(argv=None):
                                                              "optimizer is committed (the round-1/2 bench)")
     ap.add_argument("--unrolls-per-step", dest="reps", type=int, default=None,
                     help="complete unrolls (each on a fresh problem instance) per bench step; default per config so "
-                         "that 20 steps are >= 50 ms of GPU work")
+                         "that 20 steps are >= --min-timed-seconds of GPU work, whatever --steps says")
     ap.add_argument("--instances", type=int, default=4, help="ring of pre-sampled problem instances resident in HBM")
     ap.add_argument("--no-also", action="store_true", help="skip the extra runs of the `also` block (N > 1: strong scaling / "
                                                            "config 4; N = 1: configs 3, 4, 4's shard of 8, 5)")
@@ -400,8 +438,12 @@ def parse_args(argv=None):
     ap.add_argument("--also-cpu-seconds", dest="also_cpu_seconds", type=float, default=4.0,
                     help="bound of each also-run's cpu_baseline sample")
     ap.add_argument("--min-timed-seconds", dest="min_timed_seconds", type=float, default=1.0,
-                    help="the default --unrolls-per-step is chosen so that the timed region (--steps steps) is at least this "
+                    help="the default --unrolls-per-step is chosen so that a timed region of 20 steps is at least this "
                          "long: a sustained measurement, not a burst (VERDICT r05 item 4)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed unroll returned (fx[0..T], every optimizee "
+                         "variable at x_T; rank 0) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed seeded "
+                         "sample of each array beyond that)")
     ap.add_argument("--real-collective", dest="real_collective", action="store_true",
                     help="with --emulate-world: issue the shard's collectives through a REAL world-size-1 RCCL process "
                          "group of this process (communicator, stream hand-over, enqueue path) instead of skipping them")
@@ -433,10 +475,12 @@ def parse_args(argv=None):
 
 
 def default_reps(args, B_local):
-    """--unrolls-per-step when none was given: enough complete unrolls per bench step that --steps steps are at least
-    --min-timed-seconds of GPU work (round 5 timed 57 ms: a burst says nothing about sustained clocks).  From the
-    measured unroll times of round 5 (config 2 0.18 ms; config 4 0.19 ms per 128-problem shard, 1.23 ms for 1024 problems;
-    config 3 4.6 ms; config 5 1.8 ms), scaled by problems per GPU and T."""
+    """--unrolls-per-step when none was given: enough complete unrolls per bench step that STEPS_PER_MIN_TIMED steps are
+    at least --min-timed-seconds of GPU work (round 5 timed 57 ms: a burst says nothing about sustained clocks).  The
+    size of a step does not depend on --steps: --steps K times K of the same steps, so ms_per_step of one run tells how
+    many steps a later run needs for a given timed length.  From the measured unroll times of round 5 (config 2 0.18 ms;
+    config 4 0.19 ms per 128-problem shard, 1.23 ms for 1024 problems; config 3 4.6 ms; config 5 1.8 ms), scaled by
+    problems per GPU and T."""
     if args.problem == "quadratic":
         ms = 0.18 * max(1.0, B_local / 128.0) * (0.6 if B_local > 128 else 1.0) * args.unroll / 100.0
     elif args.problem == "rastrigin":
@@ -445,7 +489,7 @@ def default_reps(args, B_local):
         ms = 4.6 * max(1.0, B_local / 256.0) * args.unroll / 200.0
     else:
         ms = (4.6 if (args.replicas > 1 or args.xcd_form) else 1.8) * args.unroll / 200.0
-    return max(1, int(np.ceil(args.min_timed_seconds * 1e3 / max(1, args.steps) / ms)))
+    return max(1, int(np.ceil(args.min_timed_seconds * 1e3 / STEPS_PER_MIN_TIMED / ms)))
 
 
 def self_launch(args, argv):
@@ -701,6 +745,8 @@ def run_case(args, eng, world, rank, Bg, B, label):
     dt, t_enqueue, ev_all_ms, step_ms = min(regions)
     tenth = max(1, args.steps // 10)
     fx_host = eng.to_numpy(fx)
+    # (before the replays below overwrite x and fx)
+    outputs = timed_outputs(graph, eng, fx_host) if getattr(args, "dump_outputs", None) else None
     fx_ranks = None
     if world > 1:                                   # every rank's copy of the all-reduced final loss (must be identical)
         mine = torch.tensor([float(fx_host[-1])], device=eng.device, dtype=torch.float64)
@@ -766,7 +812,7 @@ def run_case(args, eng, world, rank, Bg, B, label):
             "fused": fused, "kernel": kernel, "dispatches": dispatches, "loop_ticks": loop_ticks,
             "n_cus": int(getattr(eng, "coresident_cus", 256)), "hbm_bound": bool(streaming or (not fused and args.problem != "mnist")), "streaming": bool(streaming),
             "hbm_model_bytes": hbm_model, "t_reset": t_reset, "D": D, "B": B, "Bg": Bg, "T": T, "Mrows": Mrows,
-            "shared": shared}
+            "shared": shared, "outputs": outputs}
 
 
 def workload_names(args, D, B, Bg, T, Mrows, shared):
@@ -868,6 +914,8 @@ def main(argv=None):
         Bg, B = args.batch, args.batch // args.emulate_world
     case = run_case(args, eng, world, rank, Bg, B, "primary")
     _graph_core.emulate_world()
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, case["outputs"])
 
     also = {}
     if world > 1 and not args.no_also and args.problem == "quadratic" and args.config in (None, 2):
@@ -1063,25 +1111,25 @@ def main(argv=None):
         torch.cuda.empty_cache()
         t_also = time.perf_counter()
         short = ["--min-timed-seconds", "0.2"]               # (each also-run: two timed regions of >= 0.2 s)
-        for name, extra_argv in (("config3", ["--config", "3", "--steps", "3"] + short),
-                                 ("config4_one_gpu", ["--config", "4", "--steps", "5"] + short),
-                                 ("config4_shard_of_8", ["--config", "4", "--emulate-world", "8", "--steps", "10"] + short),
+        for name, extra_argv in (("config3", ["--config", "3"] + short),
+                                 ("config4_one_gpu", ["--config", "4"] + short),
+                                 ("config4_shard_of_8", ["--config", "4", "--emulate-world", "8"] + short),
                                  # (the same shard with its collectives ISSUED through a real world-size-1 RCCL group: what a
                                  #  rank pays for the loss all-reduce -- collective_us_per_unroll below)
                                  ("config4_shard_of_8_rccl", ["--config", "4", "--emulate-world", "8", "--real-collective",
-                                                              "--steps", "10", "--no-cpu-baseline"] + short),
-                                 ("config5", ["--config", "5", "--steps", "5"] + short),
+                                                              "--no-cpu-baseline"] + short),
+                                 ("config5", ["--config", "5"] + short),
                                  # (config 5's two kernel forms, VERDICT r05 item 1: EIGHT replicas per launch, one per XCD --
                                  #  the throughput form -- and ONE instance on one XCD -- that form's latency)
-                                 ("config5_replicas8", ["--config", "5", "--replicas", "8", "--steps", "5", "--no-cpu-baseline"] + short),
-                                 ("config5_one_xcd", ["--config", "5", "--xcd-form", "--steps", "5", "--no-cpu-baseline"] + short),
+                                 ("config5_replicas8", ["--config", "5", "--replicas", "8", "--no-cpu-baseline"] + short),
+                                 ("config5_one_xcd", ["--config", "5", "--xcd-form", "--no-cpu-baseline"] + short),
                                  # (the 2- and 4-GPU shards of config 4, GPU side only: DESIGN.md 6 projects the scaling curve
                                  #  from these driver-timed per-shard rates)
-                                 ("config4_shard_of_2", ["--config", "4", "--emulate-world", "2", "--steps", "5", "--no-cpu-baseline"] + short),
-                                 ("config4_shard_of_4", ["--config", "4", "--emulate-world", "4", "--steps", "5", "--no-cpu-baseline"] + short),
+                                 ("config4_shard_of_2", ["--config", "4", "--emulate-world", "2", "--no-cpu-baseline"] + short),
+                                 ("config4_shard_of_4", ["--config", "4", "--emulate-world", "4", "--no-cpu-baseline"] + short),
                                  # (config 2's shape with a second tile per SIMD: 256 problems, global batch 256 -- what the
                                  #  chip does when a shard is large enough for k_unroll_lds; NOT the contract workload)
-                                 ("config2_shape_256_problems", ["--batch", "256", "--steps", "5", "--no-cpu-baseline"] + short)):
+                                 ("config2_shape_256_problems", ["--batch", "256", "--no-cpu-baseline"] + short)):
             if time.perf_counter() - t_also > args.also_budget:
                 also[name] = {"skipped": "the also-block's time budget (%g s) was spent" % args.also_budget}
                 continue

@@ -1,5 +1,6 @@
 """bench.py's roofline arithmetic on CPU (no GPU): the work / peak figure (stated minimal instruction counts x measured
-PIPE rates / measured cycles per step) and the counters lookup by build id, on synthetic counters files."""
+PIPE rates / measured cycles per step) and the counters lookup by build id, on synthetic counters files; the size of a
+bench step and the --dump-outputs writer."""
 import importlib.util
 import json
 import os
@@ -127,3 +128,47 @@ def test_roofline_frac_is_work_over_the_guide_peak(tmp_path):
     cyc4 = 1.2263e-3 * 2.4e9 / (4 * 100.3)
     assert abs(roof4["cycles_per_step"] - cyc4) < 1e-6 * cyc4 and roof4["tiles_per_simd"] == 2
     assert abs(roof4["frac"] - floor4 / cyc4) < 1e-9 and 0.25 < roof4["frac"] < 0.4 and "issue_cost_frac" not in roof4
+
+
+def test_step_size_does_not_depend_on_steps():
+    """--steps K times K steps of ONE size: the default --unrolls-per-step comes from the workload alone, so ms_per_step
+    of one run sizes the next (config 2: 278 unrolls per step, 20 steps >= 1 s)."""
+    b = _bench()
+    for preset in ([], ["--config", "3"], ["--config", "4"], ["--config", "5"]):
+        reps = {b.default_reps(a, a.batch) for a in (b.parse_args(preset + ["--steps", str(k)]) for k in (1, 5, 20, 500))}
+        assert len(reps) == 1, (preset, reps)
+    assert b.default_reps(b.parse_args(["--steps", "7"]), 128) == 278
+
+
+def test_dump_outputs_are_float32_and_capped(tmp_path, monkeypatch):
+    """--dump-outputs: what the last timed unroll returned (fx and every variable at x_T, by name) as float32 .npy;
+    beyond the cap, the same seeded sample of every array on every run."""
+    import numpy as np
+    b = _bench()
+
+    class V:
+        def __init__(self, name, value):
+            self.name, self.value = name, value
+
+    class G:
+        x = [V("x:0", np.arange(12, dtype=np.float32).reshape(3, 4)), V("mlp/w_0:0", np.ones((2, 5), np.float64))]
+
+    class E:
+        to_numpy = staticmethod(np.asarray)
+
+    fx = np.linspace(1.0, 0.1, 11).astype(np.float32)
+    outs = b.timed_outputs(G, E, fx)
+    assert sorted(outs) == ["fx", "x_T_mlp_w_0", "x_T_x"]
+    b.write_outputs(str(tmp_path / "full"), outs)
+    for name, a in outs.items():
+        got = np.load(str(tmp_path / "full" / (name + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, np.asarray(a, np.float32))
+    big = {"a": np.arange(10000, dtype=np.float32), "b": -np.arange(3000, dtype=np.float64)}
+    monkeypatch.setattr(b, "DUMP_BYTES", 4 * 1300)
+    for run in ("r1", "r2"):
+        b.write_outputs(str(tmp_path / run), big)
+    a1, b1 = (np.load(str(tmp_path / "r1" / n)) for n in ("a.npy", "b.npy"))
+    assert a1.nbytes + b1.nbytes <= 4 * 1300 and a1.size == 1000 and b1.size == 300
+    assert np.all(np.diff(a1) > 0) and np.all(np.isin(a1, big["a"])) and np.all(np.isin(b1, big["b"]))
+    assert np.array_equal(a1, np.load(str(tmp_path / "r2" / "a.npy")))
+    assert np.array_equal(b1, np.load(str(tmp_path / "r2" / "b.npy")))

@@ -34,13 +34,13 @@ def test_committed_curves_are_inside_the_readme_bands():
 
 @pytest.mark.gpu
 @pytest.mark.slow
-@pytest.mark.skipif(not os.environ.get("L2O_RUN_SLOW"), reason="~1 min of meta-training: set L2O_RUN_SLOW=1")
 def test_rastrigin_n2_plateau_matches_the_readme_figure(tmp_path):
-    """Stated band: mean f after 1000 steps of a freshly meta-trained L2O-DM on Rastrigin n = 2 in [5.0, 7.0]."""
+    """Stated band: mean f after 1000 steps of a freshly meta-trained L2O-DM on Rastrigin n = 2 in [5.0, 7.0].  Trained on
+    the reference's schedule (readme_curves.py's defaults: 10 000 epochs, evaluated on 10 batches), the schedule the
+    figure's curves come from; 4 000 epochs stop short of the plateau (f = 7.2 after 1000 steps)."""
     out = tmp_path / "curves.json"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "readme_curves.py"), "--out", str(out), "--dims", "2",
-                        "--kinds", "dm", "--num_epochs", "4000", "--eval_epochs", "4"], capture_output=True, text=True,
-                       timeout=900, cwd=ROOT)
+                        "--kinds", "dm"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     rec = json.load(open(out))
     f = rec["cases"]["dm_rastrigin_n2"]["f_after_k_steps"]
