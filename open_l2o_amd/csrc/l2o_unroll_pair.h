@@ -290,7 +290,10 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
   // register copies of the loop-carried B operands sat between the update and its LDS write: ~200 cycles of the step's
   // critical path) -- and the split runs at the top of the next step UNDER the xs reads; the loss reduction runs under the
   // residual reads of the g pass; the two row partials share one swap butterfly.
-  if (q == 0) xs[wv * kTile + c] = live ? xv * sc : 0.0f;
+  // (every q lane writes its coordinate's xs entry: the four q lanes of a coordinate hold the same bits of xv -- the
+  //  network output is a quad_q_sum, whose adds meet a + b on one lane and b + a on its partner -- so the four writes
+  //  agree, and the step loop carries no exec-masked region for them)
+  xs[wv * kTile + c] = live ? xv * sc : 0.0f;
   const size_t hist_n = (size_t)pp.B_local * D;
   const long long loop_t0 = __builtin_readcyclecounter();
   for (int t = 0;; ++t) {
@@ -363,15 +366,22 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
     float contrib = 0.0f;
     if (gq < 2) {
       int spins = 0;
-      if (!dead && (unsigned)(g >> 32) != tag) {
+      // The spin is the exception (the first poll load usually finds the granule): a wave whose lanes all have their
+      // granule skips it with ONE uniform branch, and the expectation moves the spin's exec-masked blocks out of the
+      // straight-line step (the asm statement keeps the compiler from merging the two conditions back into one mask)
+      const bool wait = !dead && (unsigned)(g >> 32) != tag;
+      if (__builtin_expect(__builtin_amdgcn_ballot_w64(wait) != 0, 0)) {
+        asm volatile("");
+        if (wait) {
 #pragma nounroll
-        for (;;) {
-          g = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((unsigned)(g >> 32) == tag) break;
-          if (++spins > (1 << 20)) { dead = true; atomicExch(&pa.ws->status, 1u); break; }
+          for (;;) {
+            g = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((unsigned)(g >> 32) == tag) break;
+            if (++spins > (1 << 20)) { dead = true; atomicExch(&pa.ws->status, 1u); break; }
 #ifndef L2O_POLL_NOSLEEP
-          __builtin_amdgcn_s_sleep(1);
+            __builtin_amdgcn_s_sleep(1);
 #endif
+          }
         }
       }
       const float r = (part + __uint_as_float((unsigned)g)) - myy;   // rows >= M: W row and y are zero -> r == 0
@@ -404,7 +414,9 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
       const float fw = wave_sum64(contrib);
       __builtin_amdgcn_sched_group_barrier(0x100, CH, 0);      // the DS reads, then the reduction's DPP chain
       __builtin_amdgcn_sched_group_barrier(0x002, 24, 0);
-      if (lane == 0) pa.fx_half[((size_t)t * pa.nb + bl) * (2 * NWH) + half * NWH + wv] = fw;
+      // (every lane stores: wave_sum64 leaves the same bits on all 64 lanes, so the one address gets one value and the
+      //  store needs no exec-masked region -- 3 857 -> 3 813 cycles per step on config 2)
+      pa.fx_half[((size_t)t * pa.nb + bl) * (2 * NWH) + half * NWH + wv] = fw;
     }
     if (t == a.T && !HIST) break;
 
@@ -454,7 +466,7 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
     // the next step's scaled iterate -> LDS NOW (its readers sit behind barrier B1; this step's readers of xs all
     // passed barrier B2 before any wave gets here)
     __builtin_amdgcn_sched_barrier(0);
-    if (q == 0) xs[wv * kTile + c] = live ? xv * sc : 0.0f;
+    xs[wv * kTile + c] = live ? xv * sc : 0.0f;           // (all four q lanes, the same value: see above)
     __builtin_amdgcn_sched_barrier(0);
     // the next step's accumulator inits (the gate biases: 10 ds_read_b128) go out HERE: their latency overlaps the wait
     // for barrier B1, which drains this wave's LDS queue anyway

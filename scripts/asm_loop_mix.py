@@ -11,7 +11,8 @@ for i, l in enumerate(body):
     m = re.search(r's_c?branch\S*\s+(\.LBB\d+_\d+)', l)
     if m and m.group(1) in labels and labels[m.group(1)] < i:
         lo = labels[m.group(1)]
-        n = sum('v_mfma' in x for x in body[lo:i])
+        # the most MFMAs, then a region holding both barriers of a step (see isa_stall_model.py), then the shortest
+        n = (sum('v_mfma' in x for x in body[lo:i]), min(2, sum('s_barrier' in x for x in body[lo:i])))
         if best is None or n > best[0] or (n == best[0] and i - lo < best[2] - best[1]):
             best = (n, lo, i)
 _, start, end = best
