@@ -1,4 +1,6 @@
 """Shared helpers for the parity tests (oracle <-> HIP path)."""
+import copy
+
 import numpy as np
 
 import oracle as O
@@ -69,6 +71,77 @@ def device_problem(eng, arrays, B, D, B_global=None, x_scale=None):
                        C=eng.tensor(arrays["C"]) if "C" in arrays else None,
                        x_scale=None if x_scale is None else eng.tensor(x_scale),
                        w_shared=bool(arrays.get("w_shared", False)))
+
+
+def as_float64(prob):
+    """A copy of an oracle problem (Quadratic, Lasso, Rastrigin, SquareCos) with float64 arrays."""
+    p = copy.copy(prob)
+    for k, v in vars(prob).items():
+        if isinstance(v, np.ndarray):
+            setattr(p, k, v.astype(np.float64))
+    return p
+
+
+def oracle_meta_grad(cfg, params, prob, x0, state0, T, m0=None, v0=None, step0=1, beta1=0.95, beta2=0.95):
+    """The meta-gradient of ONE unroll from any starting point, by the oracle's forward and its hand-derived BPTT
+    (oracle.net_bwd_step); float64 when params / x0 / the problem are.  x0 is shaped as ``prob`` expects it, state0 the
+    net state before step 0, m0 / v0 RNNProp's carried moments (zeros: None), step0 the fed `step`.
+    Returns (grads {module: {variable: array}} of L = sum_{t=0..T} f(x_t), end) with end = dict(x, state, m, v, loss):
+    what the harness' `update` carries into the next unroll."""
+    dt = x0.dtype.type
+    rn = cfg.kind == "rnnprop"
+    x, state = x0.copy(), state0
+    m = None if not rn else (np.zeros_like(x0) if m0 is None else np.asarray(m0, x0.dtype).reshape(x0.shape).copy())
+    v = None if not rn else (np.zeros_like(x0) if v0 is None else np.asarray(v0, x0.dtype).reshape(x0.shape).copy())
+    hist = []
+    loss = dt(0)
+    for t in range(T):
+        loss = loss + prob.f(x)
+        g = prob.grad(x)
+        if rn:
+            (mt, gt), m, v = O.rnnprop_inputs(g, m, v, step0 + t, beta1, beta2)
+            inputs = (mt.reshape(-1), gt.reshape(-1))
+        else:
+            inputs = g.reshape(-1)
+        hist.append((inputs, state, g))
+        delta, state = O.net_apply(cfg, params, inputs, state)
+        x = x + delta.reshape(x.shape)
+    loss = loss + prob.f(x)
+    G = prob.grad(x).reshape(-1)
+    N = x0.size
+    carry = tuple(np.zeros((N, 20), x0.dtype) for _ in range(4))
+    grads = {}
+
+    def add(mod, var, val):
+        grads.setdefault(mod, {})
+        grads[mod][var] = val if var not in grads[mod] else grads[mod][var] + val
+
+    for t in reversed(range(T)):
+        inputs, st_prev, g = hist[t]
+        carry, rows = O.net_bwd_step(cfg, params, inputs, st_prev, G, carry)
+        add("lstm_1", "w_gates", rows["act1"].T @ rows["dz1"])
+        add("lstm_1", "b_gates", rows["dz1"].sum(0))
+        add("lstm_2", "w_gates", rows["act2"].T @ rows["dz2"])
+        add("lstm_2", "b_gates", rows["dz2"].sum(0))
+        add("linear", "w", rows["h2"].T @ rows["dd"][:, None])
+        add("linear", "b", rows["dd"].sum(keepdims=True))
+        if rn:
+            add("input_projection", "w", rows["feats"].T @ rows["du"])
+            add("input_projection", "b", rows["du"].sum(0))
+        G = G + g.reshape(-1)
+    return grads, dict(x=x, state=state, m=m, v=v, loss=loss)
+
+
+def block_errors(got, want):
+    """{(module, variable): max |got - want| / max |want|} over the weight-gradient blocks of ``want``
+    ({module: {variable: array}}); ``got`` is keyed either the same way or by (module, variable)."""
+    out = {}
+    for mod in want:
+        for var, w in want[mod].items():
+            g = got[(mod, var)] if (mod, var) in got else got[mod][var]
+            g = np.asarray(g, np.float64).reshape(w.shape)
+            out[(mod, var)] = float(np.abs(g - w).max()) / max(float(np.abs(w).max()), 1e-30)
+    return out
 
 
 def rel_err(a, b):

@@ -11,7 +11,8 @@ import pytest
 import torch
 
 import oracle as O
-from helpers import ORACLE_CFGS, lib_option, make_params, make_problem, max_abs, random_state, rel_err, spec_of
+from helpers import (ORACLE_CFGS, block_errors, lib_option, make_params, make_problem, max_abs, oracle_meta_grad,
+                     random_state, rel_err, spec_of)
 from open_l2o_amd import _abi, _engine, meta, meta_rnnprop_eval, problems
 from open_l2o_amd.session import Session
 from test_meta_api import _net_config, engine  # noqa: F401  (fixture)
@@ -46,16 +47,17 @@ def test_results_reference_golden_through_meta_minimize(engine):
 
 
 # ------------------------------------------------------------------ autograd reference
-def _torch_meta_grad(cfg, params, prob_kind, prob, x0, state0, T, step0=1):
-    """dL/dtheta of loss = sum_t f(x_t) by torch autograd (float64) with g detached."""
+def _torch_meta_grad(cfg, params, prob_kind, prob, x0, state0, T, step0=1, m0=None, v0=None):
+    """dL/dtheta of loss = sum_t f(x_t) by torch autograd (float64) with g detached, from the LSTM state state0 and
+    (RNNProp) the carried moments m0 / v0 (zeros: None) with exponent step0 + t."""
     tp = {k: {v: torch.tensor(np.asarray(a, np.float64), requires_grad=True) for v, a in d.items()}
           for k, d in params.items()}
     W, y = torch.tensor(prob.w.astype(np.float64)), torch.tensor(prob.y.astype(np.float64))
     B, D = x0.shape
     x = torch.tensor(x0.astype(np.float64))
     st = [[torch.tensor(a.astype(np.float64)) for a in hc] for hc in state0]
-    m = torch.zeros_like(x)
-    v = torch.zeros_like(x)
+    m = torch.zeros_like(x) if m0 is None else torch.tensor(np.asarray(m0, np.float64).reshape(x.shape))
+    v = torch.zeros_like(x) if v0 is None else torch.tensor(np.asarray(v0, np.float64).reshape(x.shape))
     H = 20
 
     def f(xx):
@@ -100,51 +102,6 @@ def _torch_meta_grad(cfg, params, prob_kind, prob, x0, state0, T, step0=1):
     return {k: {v: t.grad.numpy() for v, t in d.items()} for k, d in tp.items()}, float(loss.detach())
 
 
-def _oracle_meta_grad(cfg, params, prob, x0, state0, T, step0=1):
-    """Forward with the oracle, backward with oracle.net_bwd_step (float64 when params are)."""
-    dt = x0.dtype.type
-    x, state = x0.copy(), state0
-    m = np.zeros_like(x0)
-    v = np.zeros_like(x0)
-    hist = []
-    for t in range(T):
-        g = prob.grad(x)
-        if cfg.kind == "rnnprop":
-            k = dt(step0 + t)
-            m = dt(0.95) * m + dt(1 - 0.95) * g
-            v = dt(0.95) * v + dt(1 - 0.95) * g * g
-            mh, vh = m / (dt(1) - np.power(dt(0.95), k)), v / (dt(1) - np.power(dt(0.95), k))
-            inputs = ((mh / (np.sqrt(vh) + dt(1e-8))).reshape(-1), (g / (np.sqrt(vh) + dt(1e-8))).reshape(-1))
-        else:
-            inputs = g.reshape(-1)
-        hist.append((inputs, state, g))
-        delta, state = O.net_apply(cfg, params, inputs if cfg.kind == "rnnprop" else g, state)
-        x = x + delta.reshape(x.shape)
-    G = prob.grad(x).reshape(-1)
-    N = x0.size
-    carry = tuple(np.zeros((N, 20), x0.dtype) for _ in range(4))
-    grads = {}
-
-    def add(mod, var, val):
-        grads.setdefault(mod, {})
-        grads[mod][var] = val if var not in grads[mod] else grads[mod][var] + val
-
-    for t in reversed(range(T)):
-        inputs, st_prev, g = hist[t]
-        carry, rows = O.net_bwd_step(cfg, params, inputs, st_prev, G, carry)
-        add("lstm_1", "w_gates", rows["act1"].T @ rows["dz1"])
-        add("lstm_1", "b_gates", rows["dz1"].sum(0))
-        add("lstm_2", "w_gates", rows["act2"].T @ rows["dz2"])
-        add("lstm_2", "b_gates", rows["dz2"].sum(0))
-        add("linear", "w", rows["h2"].T @ rows["dd"][:, None])
-        add("linear", "b", rows["dd"].sum(keepdims=True))
-        if cfg.kind == "rnnprop":
-            add("input_projection", "w", rows["feats"].T @ rows["du"])
-            add("input_projection", "b", rows["du"].sum(0))
-        G = G + g.reshape(-1)
-    return grads
-
-
 @pytest.mark.parametrize("name", ["dm", "dm_logsign", "rnnprop"])
 def test_oracle_bptt_matches_torch_autograd(name):
     cfg = ORACLE_CFGS[name]
@@ -154,8 +111,19 @@ def test_oracle_bptt_matches_torch_autograd(name):
     prob, x0 = O.Quadratic.sample(rng, B, D, stddev=0.5, dtype=np.float64)
     state0 = random_state(cfg, B * D, 102)
     state0 = tuple((h.astype(np.float64), c.astype(np.float64)) for h, c in state0)
-    want, _ = _torch_meta_grad(cfg, params, "quadratic", prob, x0, state0, T)
-    got = _oracle_meta_grad(cfg, params, prob, x0, state0, T)
+    # a carried start (the 2nd..5th unroll of a training epoch): non-zero state, moments and step0 > 1
+    m0 = rng.standard_normal((B, D)) * 0.3
+    v0 = rng.random((B, D)) * 0.5 + 0.05
+    step0 = 41
+    want, loss = _torch_meta_grad(cfg, params, "quadratic", prob, x0, state0, T, step0=step0, m0=m0, v0=v0)
+    got, end = oracle_meta_grad(cfg, params, prob, x0, state0, T, m0=m0, v0=v0, step0=step0)
+    assert abs(end["loss"] - loss) <= 1e-12 * abs(loss)
+    res = O.unroll(prob, cfg, params, x0, state0, T, m0=m0 if cfg.kind == "rnnprop" else None,
+                   v0=v0 if cfg.kind == "rnnprop" else None, step0=step0)
+    np.testing.assert_array_equal(end["x"], res.x)
+    if cfg.kind == "rnnprop":
+        np.testing.assert_array_equal(end["m"], res.m)
+        np.testing.assert_array_equal(end["v"], res.v)
     for mod in want:
         for var in want[mod]:
             np.testing.assert_allclose(got[mod][var].reshape(want[mod][var].shape), want[mod][var],
@@ -164,8 +132,9 @@ def test_oracle_bptt_matches_torch_autograd(name):
 
 @pytest.mark.parametrize("name", ["dm", "dm_logsign", "rnnprop"])
 def test_train_step_gradient_and_adam(engine, name):
-    """One sess.run([fx, update, step]) == forward + BPTT + Adam: the weights move exactly as
-    tf.train.AdamOptimizer would move them given the autograd gradient."""
+    """One sess.run([fx, update, step]) == forward + BPTT + Adam: the gradient handed to Adam is the autograd gradient
+    (every block at 5e-4 of its largest entry), and the weights move exactly as tf.train.AdamOptimizer would move them
+    given it."""
     cfg = ORACLE_CFGS[name]
     params = make_params(cfg, seed=103, trained_like=True)
     B, D, T = 4, 6, 7
@@ -180,11 +149,18 @@ def test_train_step_gradient_and_adam(engine, name):
     else:
         optimizer = meta.MetaOptimizer(**_net_config(cfg, params, key=key))
         ms = optimizer.meta_minimize(problem, T, learning_rate=0.01)
+    cap = {}
+    graph = optimizer.graph
+    orig = graph._adam_apply
+    graph._adam_apply = lambda grads, lr, **kw: (cap.update(grads={k: np.array(v) for k, v in grads[key].items()}),
+                                                 orig(grads, lr, **kw))[1]
     with Session() as sess:
         sess.run(ms.reset)
         cost = sess.run([ms.fx, ms.update, ms.step], feed_dict=feed)[0]
     st0 = O.net_initial_state(cfg, B * D)
     want, loss = _torch_meta_grad(cfg, params, "quadratic", prob, x0, st0, T)
+    for k, err in block_errors(cap["grads"], want).items():
+        assert err < 5e-4, (k, err)
     res = O.unroll(prob, cfg, params, x0, st0, T)
     assert rel_err(cost, res.fx[-1]) < 1e-5 and rel_err(res.loss, loss) < 1e-5
     new = optimizer._nets[key].variables
