@@ -84,10 +84,14 @@ def as_float64(prob):
 
 def oracle_meta_grad(cfg, params, prob, x0, state0, T, m0=None, v0=None, step0=1, beta1=0.95, beta2=0.95):
     """The meta-gradient of ONE unroll from any starting point, by the oracle's forward and its hand-derived BPTT
-    (oracle.net_bwd_step); float64 when params / x0 / the problem are.  x0 is shaped as ``prob`` expects it, state0 the
-    net state before step 0, m0 / v0 RNNProp's carried moments (zeros: None), step0 the fed `step`.
+    (oracle.net_bwd_step); float64 when params / x0 / the problem are.  ``prob``: an oracle problem (prob.f / prob.grad,
+    the same at every step), or ``fg(x, t) -> (f, g)``, an optimizee that changes per step (a minibatch per evaluation,
+    t = 0..T; mnist_fg).  x0 is shaped as ``prob`` expects it -- for several variables stepped by one coordinate-wise net
+    the flat concatenation of all of them (the BPTT is the same over the concatenation) --, state0 the net state before
+    step 0, m0 / v0 RNNProp's carried moments (zeros: None), step0 the fed `step`.
     Returns (grads {module: {variable: array}} of L = sum_{t=0..T} f(x_t), end) with end = dict(x, state, m, v, loss):
     what the harness' `update` carries into the next unroll."""
+    fg = (lambda x, t: (prob.f(x), prob.grad(x))) if hasattr(prob, "grad") else prob
     dt = x0.dtype.type
     rn = cfg.kind == "rnnprop"
     x, state = x0.copy(), state0
@@ -96,8 +100,8 @@ def oracle_meta_grad(cfg, params, prob, x0, state0, T, m0=None, v0=None, step0=1
     hist = []
     loss = dt(0)
     for t in range(T):
-        loss = loss + prob.f(x)
-        g = prob.grad(x)
+        f, g = fg(x, t)
+        loss = loss + f
         if rn:
             (mt, gt), m, v = O.rnnprop_inputs(g, m, v, step0 + t, beta1, beta2)
             inputs = (mt.reshape(-1), gt.reshape(-1))
@@ -106,8 +110,9 @@ def oracle_meta_grad(cfg, params, prob, x0, state0, T, m0=None, v0=None, step0=1
         hist.append((inputs, state, g))
         delta, state = O.net_apply(cfg, params, inputs, state)
         x = x + delta.reshape(x.shape)
-    loss = loss + prob.f(x)
-    G = prob.grad(x).reshape(-1)
+    f, G = fg(x, T)
+    loss = loss + f
+    G = G.reshape(-1)
     N = x0.size
     carry = tuple(np.zeros((N, 20), x0.dtype) for _ in range(4))
     grads = {}
@@ -130,6 +135,25 @@ def oracle_meta_grad(cfg, params, prob, x0, state0, T, m0=None, v0=None, step0=1
             add("input_projection", "b", rows["du"].sum(0))
         G = G + g.reshape(-1)
     return grads, dict(x=x, state=state, m=m, v=v, loss=loss)
+
+
+def mnist_fg(mlp, shapes, idx, scales=None):
+    """``fg(x, t)`` of oracle_meta_grad over an O.MnistMLP (fg / fg_deep; float64 when x is): x is the flat
+    concatenation of the optimizee's variables, split by ``shapes`` in the graph's order; evaluation t (step t, and t = T
+    for the gradient at x_T) uses minibatch row idx[t]; with per-coordinate scales (one array per variable, the train
+    forks' x-scale feed) it returns f(x * s) and s * grad f(x * s)."""
+    sizes = [int(np.prod(sh)) for sh in shapes]
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+    s = None if scales is None else np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in scales])
+
+    def fg(x, t):
+        sc = None if s is None else s.astype(x.dtype)
+        xs = x if sc is None else x * sc
+        vs = [xs[offs[i]:offs[i + 1]].reshape(sh) for i, sh in enumerate(shapes)]
+        f, grads = mlp.fg(vs, np.asarray(idx[t]))
+        g = np.concatenate([a.reshape(-1) for a in grads])
+        return f, (g if sc is None else g * sc)
+    return fg
 
 
 def block_errors(got, want):

@@ -11,8 +11,8 @@ import pytest
 import torch
 
 import oracle as O
-from helpers import (ORACLE_CFGS, block_errors, lib_option, make_params, make_problem, max_abs, oracle_meta_grad,
-                     random_state, rel_err, spec_of)
+from helpers import (ORACLE_CFGS, block_errors, lib_option, make_params, make_problem, max_abs, mnist_fg,
+                     oracle_meta_grad, random_state, rel_err, spec_of)
 from open_l2o_amd import _abi, _engine, meta, meta_rnnprop_eval, problems
 from open_l2o_amd.session import Session
 from test_meta_api import _net_config, engine  # noqa: F401  (fixture)
@@ -50,19 +50,23 @@ def test_results_reference_golden_through_meta_minimize(engine):
 def _torch_meta_grad(cfg, params, prob_kind, prob, x0, state0, T, step0=1, m0=None, v0=None):
     """dL/dtheta of loss = sum_t f(x_t) by torch autograd (float64) with g detached, from the LSTM state state0 and
     (RNNProp) the carried moments m0 / v0 (zeros: None) with exponent step0 + t."""
+    W, y = torch.tensor(prob.w.astype(np.float64)), torch.tensor(prob.y.astype(np.float64))
+
+    def f(xx, t):
+        r = torch.matmul(W, xx.unsqueeze(-1)).squeeze(-1) - y
+        return torch.mean(torch.sum(r * r, 1))
+    return _torch_meta_grad_of(cfg, params, f, x0, state0, T, step0, m0, v0)
+
+
+def _torch_meta_grad_of(cfg, params, f, x0, state0, T, step0=1, m0=None, v0=None):
+    """The same for any optimizee ``f(x, t)`` (a torch function of x that may change with the evaluation t = 0..T)."""
     tp = {k: {v: torch.tensor(np.asarray(a, np.float64), requires_grad=True) for v, a in d.items()}
           for k, d in params.items()}
-    W, y = torch.tensor(prob.w.astype(np.float64)), torch.tensor(prob.y.astype(np.float64))
-    B, D = x0.shape
     x = torch.tensor(x0.astype(np.float64))
     st = [[torch.tensor(a.astype(np.float64)) for a in hc] for hc in state0]
     m = torch.zeros_like(x) if m0 is None else torch.tensor(np.asarray(m0, np.float64).reshape(x.shape))
     v = torch.zeros_like(x) if v0 is None else torch.tensor(np.asarray(v0, np.float64).reshape(x.shape))
     H = 20
-
-    def f(xx):
-        r = torch.matmul(W, xx.unsqueeze(-1)).squeeze(-1) - y
-        return torch.mean(torch.sum(r * r, 1))
 
     def cell(inp, h, c, p):
         z = torch.cat([inp, h], 1) @ p["w_gates"] + p["b_gates"]
@@ -74,9 +78,9 @@ def _torch_meta_grad(cfg, params, prob_kind, prob, x0, state0, T, step0=1, m0=No
     loss = 0
     for t in range(T):
         xr = x.detach().clone().requires_grad_(True)
-        fx = f(xr)
+        fx = f(xr, t)
         g = torch.autograd.grad(fx, xr)[0].detach()
-        loss = loss + f(x)
+        loss = loss + f(x, t)
         if cfg.kind == "rnnprop":
             k = float(step0 + t)
             m = 0.95 * m + (1 - 0.95) * g
@@ -97,7 +101,7 @@ def _torch_meta_grad(cfg, params, prob_kind, prob, x0, state0, T, step0=1, m0=No
         d = h2 @ tp["linear"]["w"] + tp["linear"]["b"]
         d = (torch.tanh(d) if cfg.tanh_output else d) * cfg.scale
         x = x + d.reshape(x.shape)
-    loss = loss + f(x)
+    loss = loss + f(x, T)
     loss.backward()
     return {k: {v: t.grad.numpy() for v, t in d.items()} for k, d in tp.items()}, float(loss.detach())
 
@@ -128,6 +132,129 @@ def test_oracle_bptt_matches_torch_autograd(name):
         for var in want[mod]:
             np.testing.assert_allclose(got[mod][var].reshape(want[mod][var].shape), want[mod][var],
                                        rtol=1e-8, atol=1e-11, err_msg="%s/%s" % (mod, var))
+
+
+# ------------------------------------------------------------------ the MLP optimizee (problems.mnist)
+def _torch_mlp_loss(images, labels, shapes, idx, activation, scales=None):
+    """f(x, t) of _torch_meta_grad_of for the MLP optimizee, written in torch: the flat x split by ``shapes`` into
+    [w0, b0, w1, b1, ...], the mean softmax cross-entropy of minibatch row idx[t]; with x-scale s evaluated at x * s
+    (autograd then gives s * grad f(x * s) by itself)."""
+    X, Y = torch.tensor(images.astype(np.float64)), torch.tensor(labels.astype(np.int64))
+    sizes = [int(np.prod(sh)) for sh in shapes]
+    s = None if scales is None else torch.tensor(np.concatenate([a.reshape(-1) for a in scales]).astype(np.float64))
+    nl = len(shapes) // 2
+
+    def f(x, t):
+        parts = torch.split(x if s is None else x * s, sizes)
+        ix = torch.tensor(np.asarray(idx[t], np.int64))
+        a = X[ix]
+        for l in range(nl):
+            a = a @ parts[2 * l].reshape(shapes[2 * l]) + parts[2 * l + 1]
+            if l < nl - 1:
+                a = torch.sigmoid(a) if activation == "sigmoid" else torch.relu(a)
+        return torch.nn.functional.cross_entropy(a, Y[ix])
+    return f
+
+
+MLP_CASES = [pytest.param((20,), "sigmoid", False, id="20-sigmoid"),
+             pytest.param((20,), "relu", True, id="20-relu-xscale"),
+             pytest.param((20, 20), "sigmoid", False, id="20x20-sigmoid"),
+             pytest.param((20, 20), "relu", False, id="20x20-relu")]
+
+
+@pytest.mark.parametrize("layers,activation,scaled", MLP_CASES)
+@pytest.mark.parametrize("name", ["dm", "dm_logsign", "rnnprop"])
+def test_oracle_mlp_meta_grad_matches_torch_autograd(name, layers, activation, scaled):
+    """The float64 reference of the MNIST meta-gradient (helpers.oracle_meta_grad over helpers.mnist_fg: all the MLP's
+    variables as one flat vector through the shared coordinate-wise net, minibatch row t at evaluation t) == torch
+    autograd of the restated unroll, on a small MLP (36-pixel images), a different minibatch every evaluation, g
+    detached, from a carried start (non-zero state, m0 / v0, step0 = 41) and once with the train forks' x-scale."""
+    cfg = ORACLE_CFGS[name]
+    rng = np.random.default_rng(110)
+    params = {k: {v: a.astype(np.float64) for v, a in d.items()} for k, d in make_params(cfg, 111).items()}
+    n_in, n_data, batch, T = 36, 40, 8, 5
+    images = rng.random((n_data, n_in)).astype(np.float32)
+    labels = rng.integers(0, 10, n_data).astype(np.int32)
+    mlp = O.MnistMLP(images, labels, activation)
+    widths = [n_in] + list(layers) + [10]
+    shapes = [sh for l in range(len(widths) - 1) for sh in ((widths[l], widths[l + 1]), (widths[l + 1],))]
+    v0 = [rng.standard_normal(sh) * 0.3 for sh in shapes]       # (large enough that every activation bends)
+    x0 = np.concatenate([a.reshape(-1) for a in v0])
+    N = x0.size
+    idx = rng.integers(0, n_data, size=(T + 1, batch))
+    assert len({tuple(r) for r in idx}) == T + 1                 # a different minibatch at every evaluation
+    state0 = tuple((h.astype(np.float64), c.astype(np.float64)) for h, c in random_state(cfg, N, 112))
+    m0 = rng.standard_normal(N) * 0.3
+    v0m = rng.random(N) * 0.5 + 0.05
+    step0 = 41
+    scales = [np.exp(rng.uniform(-1, 1, sh)) for sh in shapes] if scaled else None
+    want, loss = _torch_meta_grad_of(cfg, params, _torch_mlp_loss(images, labels, shapes, idx, activation, scales),
+                                     x0, state0, T, step0=step0, m0=m0, v0=v0m)
+    got, end = oracle_meta_grad(cfg, params, mnist_fg(mlp, shapes, idx, scales), x0, state0, T, m0=m0, v0=v0m,
+                                step0=step0)
+    assert abs(end["loss"] - loss) <= 1e-12 * abs(loss)
+    for mod in want:
+        for var in want[mod]:
+            np.testing.assert_allclose(got[mod][var].reshape(want[mod][var].shape), want[mod][var],
+                                       rtol=1e-8, atol=1e-11, err_msg="%s/%s" % (mod, var))
+    # the concatenation steps exactly as one net state / pair of moments per variable does (O.unroll_multi)
+    sizes = np.cumsum([0] + [a.size for a in v0])
+    rows = lambda a, i: a[sizes[i]:sizes[i + 1]]
+    sts = [tuple((rows(h, i), rows(c, i)) for h, c in state0) for i in range(len(v0))]
+    rn = cfg.kind == "rnnprop"
+
+    def fg_multi(vs, t, wg):
+        f, g = mnist_fg(mlp, shapes, idx, scales)(np.concatenate([a.reshape(-1) for a in vs]), t)
+        return f, [rows(g, i).reshape(shapes[i]) for i in range(len(vs))]
+    res = O.unroll_multi(fg_multi, cfg, params, v0, sts, T, step0=step0, return_moments=True,
+                         ms=[rows(m0, i).reshape(shapes[i]) for i in range(len(v0))] if rn else None,
+                         vs=[rows(v0m, i).reshape(shapes[i]) for i in range(len(v0))] if rn else None)
+    np.testing.assert_allclose(end["x"], np.concatenate([a.reshape(-1) for a in res[1]]), rtol=1e-12, atol=1e-15)
+    assert abs(end["loss"] - res[0].sum()) <= 1e-12 * abs(loss)
+
+
+@pytest.mark.parametrize("layers", [(20,), (20, 20, 20)])
+@pytest.mark.parametrize("name", ["dm", "dm_logsign", "rnnprop"])
+def test_mnist_train_steps_on_the_oracle_engine(name, layers, monkeypatch):
+    """Two MNIST meta_minimize steps (reset, then one from carried state) on the OracleEngine: the gradient handed to the
+    meta-Adam == the float64 reference from the step's own start, on the minibatch rows the graph drew (read back from
+    its index buffer), every block at 5e-4 of its largest entry; the carry per variable.  That holds the host's part of
+    the MNIST meta-gradient -- which row feeds g_t and g_final, the moment history, step0, the four (784-20-10) or eight
+    ((20, 20, 20): the limit of one multi-panel launch) panels in ONE BPTT launch, the gather into the meta-Adam --
+    without a GPU."""
+    from oracle_engine import OracleEngine
+    from test_training_gradient import Trainer, check_carry, check_grad, split_carry, spy_bwd_unroll
+    eng = OracleEngine()
+    old = _engine._default_engine
+    _engine.set_default_engine(eng)
+    try:
+        cfg = ORACLE_CFGS[name]
+        T, batch = 4, 16
+        data = problems.synthetic_mnist(100, seed=12)
+        mlp = O.MnistMLP(data["images"], data["labels"].astype(np.int32), "sigmoid")
+        meta.set_random_seed(13)
+        tr = Trainer(eng, name, make_params(cfg, seed=14, trained_like=True),
+                     problems.mnist(layers=layers, batch_size=batch, data=data), T)
+        shapes = [tuple(v.shape) for v in tr.graph.x]
+        widths = [784] + list(layers) + [10]
+        assert shapes == [sh for l in range(len(widths) - 1) for sh in ((widths[l], widths[l + 1]), (widths[l + 1],))]
+        launches = spy_bwd_unroll(eng, monkeypatch)
+        tr.reset()
+        prev = None
+        for k in range(2):
+            snap = tr.snapshot()
+            if prev is not None:
+                for j, (sv, ev, e32) in enumerate(zip(snap["vars"], split_carry(prev, shapes), split_carry(prev32, shapes))):
+                    check_carry(sv, ev, e32, "carry into step %d, variable %d" % (k, j))
+            got = tr.train_step()
+            assert tr.graph.last_path == "steps" and launches == [[(1, int(np.prod(sh))) for sh in shapes]] * (k + 1)
+            idx = eng.to_numpy(tr.graph._mlp_idx[0])
+            assert idx.shape == (T + 1, batch)
+            want, prev = tr.reference(mnist_fg(mlp, shapes, idx), snap)
+            prev32 = tr.reference(mnist_fg(mlp, shapes, idx), snap, np.float32)[1]
+            check_grad(got, want, "step %d" % k)
+    finally:
+        _engine.set_default_engine(old)
 
 
 @pytest.mark.parametrize("name", ["dm", "dm_logsign", "rnnprop"])

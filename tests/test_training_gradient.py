@@ -25,7 +25,7 @@ import torch
 import oracle as O
 from helpers import (ORACLE_CFGS, as_float64, block_errors, lib_option, make_params, make_problem, oracle_meta_grad,
                      random_state, spec_of)
-from open_l2o_amd import _abi, _engine, meta, meta_rnnprop_eval, problems
+from open_l2o_amd import _abi, _engine, meta, meta_dm_train, meta_rnnprop_eval, meta_rnnprop_train, problems
 from open_l2o_amd.session import Session
 from test_meta_api import _net_config
 
@@ -63,13 +63,24 @@ def _case(kind, B, D, seed, M=None):
 
 class Trainer(object):
     """meta_minimize driven the way the training harness drives it (reset, then train steps that carry x / state /
-    moments), with a snapshot of every step's starting point and the gradient each step hands to the meta-Adam."""
+    moments), with a snapshot of every step's starting point and the gradient each step hands to the meta-Adam.
+    fork: the random-scaling training forks (meta_dm_train / meta_rnnprop_train, DM/util.py:40-54) instead of meta /
+    meta_rnnprop_eval; ``scale_feed`` (a list of arrays, one per variable) is then fed to every train step."""
 
-    def __init__(self, eng, name, params, api, T, lr=1e-3):
+    def __init__(self, eng, name, params, api, T, lr=1e-3, fork=False):
         self.eng, self.cfg, self.T = eng, ORACLE_CFGS[name], T
         self.rn = self.cfg.kind == "rnnprop"
         self.key = "rp" if self.rn else "cw"
-        if self.rn:
+        self.scale_ph, self.scale_feed = None, None
+        if fork and self.rn:
+            self.opt = meta_rnnprop_train.MetaOptimizer(0, 0.95, 0.95, **_net_config(self.cfg, params, key="rp"))
+            out = self.opt.meta_minimize(api, T, learning_rate=lr)
+            self.ms, self.scale_ph, self.step_ph = out[0], out[1], out[5]
+        elif fork:
+            self.opt = meta_dm_train.MetaOptimizer(0, **_net_config(self.cfg, params))
+            out = self.opt.meta_minimize(api, T, learning_rate=lr)
+            self.ms, self.scale_ph, self.step_ph = out[0], out[1], None
+        elif self.rn:
             self.opt = meta_rnnprop_eval.MetaOptimizer(0.95, 0.95, **_net_config(self.cfg, params, key="rp"))
             out = self.opt.meta_minimize(api, T, learning_rate=lr)
             self.ms, self.step_ph = out[0], out[3]
@@ -89,19 +100,37 @@ class Trainer(object):
         self.step0 = 1
 
     def snapshot(self):
-        """What the next unroll starts from: float64 weights, x, ((h1, c1), (h2, c2)), m, v, step0."""
+        """What the next unroll starts from: float64 weights, step0 and, per variable in the graph's order, x,
+        ((h1, c1), (h2, c2)), m, v ("vars").  x / state / m / v: those of the one variable, or for several the
+        concatenation in the same order (flat x, m, v; stacked state rows) -- every variable goes through the same
+        coordinate-wise net, so that is what the reference unrolls."""
         g, eng = self.graph, self.eng
-        s = g.slots[0]
-        B, D = s.state.B, s.state.D
         w = {m: {v: np.asarray(a, np.float64).copy() for v, a in d.items()} for m, d in self.opt._nets[self.key].variables.items()}
-        h1, c1, h2, c2 = (eng.to_numpy(a).astype(np.float64) for a in eng.state_unpack(s.state.packed, B, D))
-        m = eng.to_numpy(s.m).astype(np.float64).reshape(B, D) if self.rn else None
-        v = eng.to_numpy(s.v).astype(np.float64).reshape(B, D) if self.rn else None
-        return dict(w=w, x=g.x[0].eval().astype(np.float64), state=((h1, c1), (h2, c2)), m=m, v=v, step0=self.step0)
+        slot_of = {s.var_index: s for s in g.slots}
+        per = []
+        for j, var in enumerate(g.x):
+            s = slot_of[j]
+            B, D = s.state.B, s.state.D
+            h1, c1, h2, c2 = (eng.to_numpy(a).astype(np.float64) for a in eng.state_unpack(s.state.packed, B, D))
+            m = eng.to_numpy(s.m).astype(np.float64).reshape(B, D) if self.rn else None
+            v = eng.to_numpy(s.v).astype(np.float64).reshape(B, D) if self.rn else None
+            per.append(dict(x=var.eval().astype(np.float64), state=((h1, c1), (h2, c2)), m=m, v=v))
+        snap = dict(w=w, step0=self.step0, vars=per)
+        if len(per) == 1:
+            snap.update(per[0])
+        else:
+            cat = lambda arrs: np.concatenate([a.reshape(-1) for a in arrs])
+            snap.update(x=cat([p["x"] for p in per]),
+                        state=tuple((np.concatenate([p["state"][l][0] for p in per]),
+                                     np.concatenate([p["state"][l][1] for p in per])) for l in range(2)),
+                        m=cat([p["m"] for p in per]) if self.rn else None, v=cat([p["v"] for p in per]) if self.rn else None)
+        return snap
 
     def train_step(self):
         """One sess.run([fx, update, step]); returns the gradient handed to Adam."""
         feed = {self.step_ph: self.step0} if self.rn else {}
+        if self.scale_feed is not None:
+            feed.update(zip(self.scale_ph, self.scale_feed))
         n = len(self.caps)
         self.sess.run([self.ms.fx, self.ms.update, self.ms.step], feed_dict=feed)
         assert len(self.caps) == n + 1
@@ -109,8 +138,11 @@ class Trainer(object):
         return self.caps[-1]
 
     def reference(self, prob, snap, dtype=np.float64):
-        """oracle_meta_grad from the snapshot, in float64 (prob: a float64 problem) or float32 (the float32 problem)."""
-        x0 = snap["x"].reshape(prob_x_shape(prob, snap["x"])).astype(dtype)
+        """oracle_meta_grad from the snapshot, in float64 (prob: a float64 problem) or float32 (the float32 problem);
+        prob may also be an ``fg(x, t)`` (helpers.mnist_fg), which takes x as the snapshot holds it."""
+        x0 = snap["x"].astype(dtype)
+        if hasattr(prob, "grad"):
+            x0 = x0.reshape(prob_x_shape(prob, snap["x"]))
         w = {m: {v: a.astype(dtype) for v, a in d.items()} for m, d in snap["w"].items()}
         st = tuple((h.astype(dtype), c.astype(dtype)) for h, c in snap["state"])
         m0, v0 = ((None, None) if snap["m"] is None else (snap["m"].astype(dtype), snap["v"].astype(dtype)))
@@ -136,6 +168,36 @@ def _carried(d):
     if d["m"] is not None:
         out.update(m=d["m"], v=d["v"])
     return {k: np.asarray(a, np.float64).reshape(-1) for k, a in out.items()}
+
+
+def split_carry(d, shapes):
+    """An end state of oracle_meta_grad over the flat concatenation of several variables -> one dict (x, state, m, v)
+    per variable, as Trainer.snapshot's "vars" holds them."""
+    offs = np.concatenate([[0], np.cumsum([int(np.prod(sh)) for sh in shapes])]).astype(int)
+    out = []
+    for a, b in zip(offs[:-1], offs[1:]):
+        out.append(dict(x=d["x"].reshape(-1)[a:b], state=tuple((h[a:b], c[a:b]) for h, c in d["state"]),
+                        m=None if d["m"] is None else d["m"].reshape(-1)[a:b],
+                        v=None if d["v"] is None else d["v"].reshape(-1)[a:b]))
+    return out
+
+
+def spy_bwd_unroll(eng, monkeypatch):
+    """Record the (B, D) of the panels of every BPTT launch the graph makes through eng.bwd_unroll (not an engine's
+    own inner calls); returns the list it appends to."""
+    launches, depth = [], [0]
+    real = eng.bwd_unroll
+
+    def spy(spec, w, panels, *a, **kw):
+        if not depth[0]:
+            launches.append([(pn["B"], pn["D"]) for pn in panels])
+        depth[0] += 1
+        try:
+            return real(spec, w, panels, *a, **kw)
+        finally:
+            depth[0] -= 1
+    monkeypatch.setattr(eng, "bwd_unroll", spy)
+    return launches
 
 
 def check_carry(snap, end, end32, what):
