@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define L2O_ABI_VERSION 13
+#define L2O_ABI_VERSION 14
 
 #define L2O_OK 0
 #define L2O_ERR_ARG (-1)
@@ -334,6 +334,14 @@ size_t l2o_mlp_unroll_multi_workspace_bytes(const l2o_mlp* mlp, int32_t n_inst);
 int l2o_mlp_unroll_multi(const l2o_net_cfg* cfg, const float* wpack /* device */, const l2o_mlp* mlp,
                          const l2o_mlp_instance* inst /* host [n_inst] */, int32_t n_inst, int32_t T, int32_t step0,
                          void* workspace, void* stream);
+/* The same launch, also recording what the meta-gradient needs (ABI v14; the multi-instance counterpart of
+ * l2o_mlp_unroll_record): hist[j] receives instance j's history in l2o_mlp_hist's layout, exactly what
+ * l2o_mlp_unroll_record writes for that instance alone.  Every instance's indices must hold T + 1 rows (the gradient at
+ * x_T is evaluated).  Same support predicate, workspace size, sticky status word and fault-injection word as
+ * l2o_mlp_unroll_multi; a team that does not assemble leaves garbage history and raises L2O_ERR_TIMEOUT. */
+int l2o_mlp_unroll_multi_record(const l2o_net_cfg* cfg, const float* wpack /* device */, const l2o_mlp* mlp,
+                                const l2o_mlp_instance* inst /* host [n_inst] */, int32_t n_inst, int32_t T, int32_t step0,
+                                const l2o_mlp_hist* hist /* host [n_inst] */, void* workspace, void* stream);
 
 /* ---- one optimizer step on a gradient panel: the closure `update`
  * (DM/meta.py:319-336; RNNProp DM/meta_rnnprop_train.py:371-395) for ONE variable:

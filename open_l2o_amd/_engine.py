@@ -377,17 +377,20 @@ class HipEngine(object):
         cc, cm = spec.to_c(), self._cmlp(d)
         return bool(self.lib.l2o_mlp_unroll_multi_supported(C.byref(cc), C.byref(cm), int(n_inst), self._stream()))
 
-    def mlp_unroll_multi(self, spec: NetSpec, wpack, d: MlpDesc, instances, T, step0):
+    def mlp_unroll_multi(self, spec: NetSpec, wpack, d: MlpDesc, instances, T, step0, hists=None):
         """T optimizer steps on up to EIGHT independent instances of the MLP optimizee in ONE launch, one instance per XCD
         (l2o_mlp_unroll_multi).  instances: list of dicts(indices=, xs=, sts=, ms=, vs=, scales=, fx=) as the arguments of
-        mlp_unroll (all instances share the network, the data set and T / step0).  The argument block of a repeated
-        launch (same buffers) is built once."""
+        mlp_unroll (all instances share the network, the data set and T / step0).  hists: None, or one history dict per
+        instance as mlp_unroll's `hist` (l2o_mlp_unroll_multi_record).  The argument block of a repeated launch (same
+        buffers) is built once."""
         def ptr(t):
             return 0 if t is None else t.data_ptr()
+        hkey = None if hists is None else tuple(
+            tuple(ptr(t) for k in ("st", "g", "m", "v") for t in (h.get(k) or (None,) * 4)) for h in hists)
         key = ("multi", _abi.options_word(), id(d), spec.kind, spec.preprocess, float(spec.scale), bool(spec.tanh_output),
                float(spec.logsign_k), float(spec.beta1), float(spec.beta2), wpack.data_ptr(), int(T),
                tuple((ptr(i["indices"]), ptr(i["fx"])) + tuple(ptr(t) for k in ("xs", "sts", "ms", "vs", "scales") for t in i[k])
-                     for i in instances))
+                     for i in instances), hkey)
         memo = self.__dict__.setdefault("_mlp_unroll_memo", {})
         ent = memo.get(key)
         if ent is None:
@@ -406,15 +409,31 @@ class HipEngine(object):
                     arr[j].m[k] = None if i["ms"][k] is None else i["ms"][k].data_ptr()
                     arr[j].v[k] = None if i["vs"][k] is None else i["vs"][k].data_ptr()
                     arr[j].x_scale[k] = None if i["scales"][k] is None else i["scales"][k].data_ptr()
-            ent = dict(cc=cc, cm=cm, ws=ws, arr=arr, keep=(d, wpack, [dict(i) for i in instances]))
+            harr = None
+            if hists is not None:
+                if len(hists) != len(instances):
+                    raise ValueError("mlp_unroll_multi: one history per instance")
+                harr = (_abi.MlpHist * len(hists))()
+                for j, h in enumerate(hists):
+                    for k in range(4):
+                        harr[j].st[k], harr[j].g[k] = h["st"][k].data_ptr(), h["g"][k].data_ptr()
+                        harr[j].m[k] = None if h.get("m") is None or h["m"][k] is None else h["m"][k].data_ptr()
+                        harr[j].v[k] = None if h.get("v") is None or h["v"][k] is None else h["v"][k].data_ptr()
+            ent = dict(cc=cc, cm=cm, ws=ws, arr=arr, harr=harr,
+                       keep=(d, wpack, [dict(i) for i in instances], None if hists is None else [dict(h) for h in hists]))
             if len(memo) >= 8:
                 memo.pop(next(iter(memo)))
             memo[key] = ent
         ws = ent["ws"]
         if self.__dict__.get("_mlp_ws") is not ws:           # (a larger workspace replaced it since)
             memo.pop(key, None)
-            return self.mlp_unroll_multi(spec, wpack, d, instances, T, step0)
+            return self.mlp_unroll_multi(spec, wpack, d, instances, T, step0, hists=hists)
         self._last_ws = ws
+        if ent["harr"] is not None:
+            _abi.check(self.lib.l2o_mlp_unroll_multi_record(C.byref(ent["cc"]), _ptr(wpack), C.byref(ent["cm"]), ent["arr"],
+                                                            len(instances), int(T), int(step0), ent["harr"],
+                                                            C.c_void_p(ws.data_ptr()), self._stream()))
+            return
         _abi.check(self.lib.l2o_mlp_unroll_multi(C.byref(ent["cc"]), _ptr(wpack), C.byref(ent["cm"]), ent["arr"], len(instances),
                                                  int(T), int(step0), C.c_void_p(ws.data_ptr()), self._stream()))
 

@@ -235,10 +235,8 @@ class BpttMixin(object):
             else:
                 srcs.pop(id(acc), None)
 
-    def _backward(self, T, rec):
-        eng = self.engine
-        step0 = rec["step0"]
-        out = {}                                           # net key -> {(module, variable): device grad}
+    def _bptt_panel_sets(self, rec):
+        """The BPTT panels of one recorded unroll, by network: {net key: (net, [panel dicts as _bptt_panels takes])}."""
         by_net = {}                                        # variables that share a network go through ONE launch per step
         for si, s in enumerate(self.slots):
             net = s.net
@@ -258,6 +256,13 @@ class BpttMixin(object):
                 pn.update(second=True, desc=rec["descs"][j], xs=[x[j] for x in rec["x"]],
                           weight=self.term_of[self.x[j].decl.name].weight)
             by_net.setdefault(s.key, (net, []))[1].append(pn)
+        return by_net
+
+    def _backward(self, T, rec):
+        eng = self.engine
+        step0 = rec["step0"]
+        out = {}                                           # net key -> {(module, variable): device grad}
+        by_net = self._bptt_panel_sets(rec)
         for key, (net, panels) in by_net.items():      # rec["plan"]: buffers of a planned unroll are reused, so is the table
             self._bptt_panels(net, out.setdefault(key, {}), T, step0, panels, cache=rec.get("plan"))
         if self.sharded:

@@ -86,6 +86,23 @@ class StepPlanMixin(object):
         plan of _run_steps_planned, and handed to _backward in the same format) + one l2o_mlp_unroll_record launch."""
         eng = self.engine
         term = self.terms[0]
+        plan = self._mlp_hist_plan(T, panels, slots, states, ms, vs)
+        index_of = {v.decl.name: j for j, v in enumerate(self.x)}
+        js = [index_of[tv.name] for tv in _term_vars(term)]               # w1, b1, w2, b2 -> variable index
+        slot_of = {s.var_index: si for si, s in enumerate(slots)}
+        sis = [slot_of[j] for j in js]
+        net = slots[sis[0]].net
+        eng.mlp_unroll(net.spec, net.wpack(eng), self._mlp_desc(term), self._mlp_idx[0],
+                       [panels[j] for j in js], [states[si].packed for si in sis], [ms[si] for si in sis],
+                       [vs[si] for si in sis], [scales[j] for j in js], T, step0, fx, hist=plan["hist"])
+        record.update(g=plan["g"], st=plan["st"], m=plan["m"], v=plan["v"], g_final=plan["g_final"], plan=plan)
+
+    def _mlp_hist_plan(self, T, panels, slots, states, ms, vs):
+        """The history buffers of a recording MLP unroll for this set of variable buffers (built once, kept while the
+        buffers stay): plan["hist"] in the argument order of l2o_mlp_unroll_record (w1, b1, w2, b2), and its per-step
+        views in the record format _backward reads.  Replicas.train_step hands the same to l2o_mlp_unroll_multi_record."""
+        eng = self.engine
+        term = self.terms[0]
         nvar = len(self.x)
         index_of = {v.decl.name: j for j, v in enumerate(self.x)}
         js = [index_of[tv.name] for tv in _term_vars(term)]               # w1, b1, w2, b2 -> variable index
@@ -108,11 +125,7 @@ class StepPlanMixin(object):
                 m=[[None if hm[si] is None else hm[si][t + 1] for si in range(len(slots))] for t in range(T)],
                 v=[[None if hv[si] is None else hv[si][t + 1] for si in range(len(slots))] for t in range(T)],
                 g_final=[hist_g[j][T] for j in range(nvar)])
-        net = slots[sis[0]].net
-        eng.mlp_unroll(net.spec, net.wpack(eng), self._mlp_desc(term), self._mlp_idx[0],
-                       [panels[j] for j in js], [states[si].packed for si in sis], [ms[si] for si in sis],
-                       [vs[si] for si in sis], [scales[j] for j in js], T, step0, fx, hist=plan["hist"])
-        record.update(g=plan["g"], st=plan["st"], m=plan["m"], v=plan["v"], g_final=plan["g_final"], plan=plan)
+        return plan
 
     def _mlp_unroll_ok(self, slots, states, scales):
         """l2o_mlp_unroll applies: ONE problems.mnist term of weight 1 whose four variables are all stepped by the

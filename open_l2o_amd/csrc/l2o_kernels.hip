@@ -2080,8 +2080,8 @@ size_t l2o_mlp_unroll_multi_workspace_bytes(const l2o_mlp* mlp, int32_t n_inst) 
   return mlp_xcd_layout(mlp, n_inst, &L) ? L.total : 0;
 }
 
-int l2o_mlp_unroll_multi(const l2o_net_cfg* cfg, const float* wpack, const l2o_mlp* mlp, const l2o_mlp_instance* inst,
-                         int32_t n_inst, int32_t T, int32_t step0, void* workspace, void* stream) {
+static int mlp_unroll_multi_launch(const l2o_net_cfg* cfg, const float* wpack, const l2o_mlp* mlp, const l2o_mlp_instance* inst,
+                                   int32_t n_inst, int32_t T, int32_t step0, const l2o_mlp_hist* hist, void* workspace, void* stream) {
   OptScope opt_scope(cfg_optw(cfg));
   if (!cfg || !wpack || !mlp || !inst || !workspace || T < 0 || !mlp->images || !mlp->labels)
     return fail(L2O_ERR_ARG, "l2o_mlp_unroll_multi: bad argument");
@@ -2091,7 +2091,7 @@ int l2o_mlp_unroll_multi(const l2o_net_cfg* cfg, const float* wpack, const l2o_m
     return fail(L2O_ERR_UNSUPPORTED, "l2o_mlp_unroll_multi: no one-XCD kernel for n_in=%d hidden=%d out=%d batch=%d x %d instances "
                 "(needs the reference's shape and all 8 x 32 CUs)", mlp->n_in, mlp->n_hidden, mlp->n_out, mlp->batch, (int)n_inst);
   const bool rn = cfg->preprocess == L2O_PRE_FC_ELU;
-  MlpXcdArgs a;
+  MlpXcdHistArgs a;                                   // (the plain form is launched with its MlpXcdArgs part)
   std::memset(&a, 0, sizeof(a));
   a.np = make_net_params(cfg, wpack);
   a.n_in = mlp->n_in; a.act = mlp->activation; a.T = T; a.ninst = n_inst;
@@ -2119,25 +2119,63 @@ int l2o_mlp_unroll_multi(const l2o_net_cfg* cfg, const float* wpack, const l2o_m
     o.P = reinterpret_cast<unsigned long long*>(ib);
     o.S = reinterpret_cast<unsigned long long*>(ib + L.p_bytes);
     o.Sm = reinterpret_cast<unsigned long long*>(ib + L.p_bytes + L.s_bytes);
+    if (hist) {
+      const l2o_mlp_hist& h = hist[j];
+      MxHist& oh = a.hist[j];
+      for (int k = 0; k < 4; ++k) {
+        if (!h.st[k] || !h.g[k] || (rn && (!h.m[k] || !h.v[k])))
+          return fail(L2O_ERR_ARG, "l2o_mlp_unroll_multi_record: NULL history buffer of variable %d of instance %d", k, j);
+        oh.st[k] = h.st[k]; oh.g[k] = h.g[k];
+        oh.m[k] = rn ? h.m[k] : nullptr; oh.v[k] = rn ? h.v[k] : nullptr;
+      }
+    }
   }
   HIP_TRY(hipMemsetAsync(wsb + L.team_off, 0, L.total - L.team_off, s));   // team counters + granules: the header survives
   // which form: four waves per member stepping tile PAIRS (a lone wave per SIMD with two independent chains; RNNProp: no
   // spills at 438 registers) or eight waves stepping single tiles (two waves per SIMD; the DM nets' pair form spills)
   const int wopt = (int)opt(L2O_OPT_MLP_XCD_WAVES);
   const bool four = wopt == 2 || (wopt == 0 && rn && L2O_MLP_XCD_DEFAULT_FOUR);
-  void (*fn)(MlpXcdArgs) = nullptr;
   size_t lds = 0;
   switch (cfg->preprocess) {
-    case L2O_PRE_IDENTITY: fn = four ? k_mlp_xcd<L2O_PRE_IDENTITY, 4> : k_mlp_xcd<L2O_PRE_IDENTITY, 8>; lds = mlp_xcd_lds_bytes<L2O_PRE_IDENTITY>(); break;
-    case L2O_PRE_LOGSIGN: fn = four ? k_mlp_xcd<L2O_PRE_LOGSIGN, 4> : k_mlp_xcd<L2O_PRE_LOGSIGN, 8>; lds = mlp_xcd_lds_bytes<L2O_PRE_LOGSIGN>(); break;
-    default: fn = four ? k_mlp_xcd<L2O_PRE_FC_ELU, 4> : k_mlp_xcd<L2O_PRE_FC_ELU, 8>; lds = mlp_xcd_lds_bytes<L2O_PRE_FC_ELU>();
+    case L2O_PRE_IDENTITY: lds = mlp_xcd_lds_bytes<L2O_PRE_IDENTITY>(); break;
+    case L2O_PRE_LOGSIGN: lds = mlp_xcd_lds_bytes<L2O_PRE_LOGSIGN>(); break;
+    default: lds = mlp_xcd_lds_bytes<L2O_PRE_FC_ELU>();
   }
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // one workgroup per CU of the whole chip: the 32 that land on XCD j < n_inst form instance j's team, the others exit
-  hipLaunchKernelGGL(fn, dim3(kMxMaxInst * kMxMembers), dim3(four ? kMxThreads4 : kMxThreads), lds, s, a);
+  const dim3 grid(kMxMaxInst * kMxMembers), block(four ? kMxThreads4 : kMxThreads);
+  if (hist) {
+    void (*fn)(MlpXcdHistArgs) = nullptr;
+    switch (cfg->preprocess) {
+      case L2O_PRE_IDENTITY: fn = four ? k_mlp_xcd<L2O_PRE_IDENTITY, 4, true> : k_mlp_xcd<L2O_PRE_IDENTITY, 8, true>; break;
+      case L2O_PRE_LOGSIGN: fn = four ? k_mlp_xcd<L2O_PRE_LOGSIGN, 4, true> : k_mlp_xcd<L2O_PRE_LOGSIGN, 8, true>; break;
+      default: fn = four ? k_mlp_xcd<L2O_PRE_FC_ELU, 4, true> : k_mlp_xcd<L2O_PRE_FC_ELU, 8, true>;
+    }
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(fn, grid, block, lds, s, a);
+  } else {
+    void (*fn)(MlpXcdArgs) = nullptr;
+    switch (cfg->preprocess) {
+      case L2O_PRE_IDENTITY: fn = four ? k_mlp_xcd<L2O_PRE_IDENTITY, 4> : k_mlp_xcd<L2O_PRE_IDENTITY, 8>; break;
+      case L2O_PRE_LOGSIGN: fn = four ? k_mlp_xcd<L2O_PRE_LOGSIGN, 4> : k_mlp_xcd<L2O_PRE_LOGSIGN, 8>; break;
+      default: fn = four ? k_mlp_xcd<L2O_PRE_FC_ELU, 4> : k_mlp_xcd<L2O_PRE_FC_ELU, 8>;
+    }
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(fn, grid, block, lds, s, static_cast<const MlpXcdArgs&>(a));
+  }
   HIP_TRY(hipGetLastError());
   note_form(L2O_FORM_MLP_XCD);
   return L2O_OK;
+}
+
+int l2o_mlp_unroll_multi(const l2o_net_cfg* cfg, const float* wpack, const l2o_mlp* mlp, const l2o_mlp_instance* inst,
+                         int32_t n_inst, int32_t T, int32_t step0, void* workspace, void* stream) {
+  return mlp_unroll_multi_launch(cfg, wpack, mlp, inst, n_inst, T, step0, nullptr, workspace, stream);
+}
+int l2o_mlp_unroll_multi_record(const l2o_net_cfg* cfg, const float* wpack, const l2o_mlp* mlp, const l2o_mlp_instance* inst,
+                                int32_t n_inst, int32_t T, int32_t step0, const l2o_mlp_hist* hist, void* workspace,
+                                void* stream) {
+  if (!hist) return fail(L2O_ERR_ARG, "l2o_mlp_unroll_multi_record: NULL hist");
+  return mlp_unroll_multi_launch(cfg, wpack, mlp, inst, n_inst, T, step0, hist, workspace, stream);
 }
 
 int l2o_cwlstm_step_multi(const l2o_net_cfg* cfg, const float* wpack, const l2o_step_seg* segs, int32_t nseg,

@@ -38,7 +38,8 @@ constexpr int kMxThreads4 = 256;                  // form 4: four waves, one per
 constexpr int kMxSlots = 32;                      // tiles per member (four per wave)
 constexpr int kMxCoords = kMxSlots * kTile;       // 512 coordinate positions per member
 constexpr int kMxMaxInst = 8;                     // instances per launch = XCDs
-constexpr int kMxB = 64, kMxH = 20, kMxO = 10;    // the reference's shape (DM/util.py:146-155: mnist, batch 64... the FAST form)
+constexpr int kMxB = 64, kMxH = 20, kMxO = 10;    // k_mlp_unroll's FAST shape: minibatch 64 only (the reference's `mnist`
+                                                  // config, DM/util.py:146-155, draws 128: that goes to k_mlp_unroll)
 constexpr int kMxNO = kMxB * kMxH;                // all-reduced outputs per evaluation
 constexpr int kMxR = kMxNO / kMxMembers;          // outputs per reducer: 40 = two samples x 20 hidden units
 constexpr int kMxKR = 28;                         // image columns a member's 512 w1 coordinates touch (<= 27), 7 MFMA k-steps
@@ -59,6 +60,13 @@ struct MxInst {                // one optimizee instance (replica)
   unsigned long long* Sm;      // [2][kMxNSMp]                   b1, w2, b2 (scaled), by step parity
 };
 
+struct MxHist {
+  float* st[4];                // [T][packed state]   the LSTM state BEFORE step t
+  float* g[4];                 // [T + 1][n]          the (scaled) gradient at x_t; slot T = the gradient at x_T
+  float* m[4];                 // [T + 1][n]          RNNProp moments AFTER step t in slot t + 1 (slot 0 untouched)
+  float* v[4];
+};
+
 struct MlpXcdArgs {
   NetParams np;
   int n_in, act, T, ninst;
@@ -72,6 +80,14 @@ struct MlpXcdArgs {
   unsigned* team;              // [8] arrival counters per XCD (zeroed by the launch)
   MxInst inst[kMxMaxInst];
 };
+// the HIST instantiation's arguments (l2o_mlp_unroll_multi_record): per instance and variable, the history of
+// l2o_mlp_unroll_record in its layout (MlpUnrollArgs::hist_*).  A struct of its own, so that the plain form's argument
+// block stays what it was (1 744 bytes, not 2 768)
+struct MlpXcdHistArgs : MlpXcdArgs {
+  MxHist hist[kMxMaxInst];
+};
+template <bool HIST>
+using MlpXcdArgsT = typename std::conditional<HIST, MlpXcdHistArgs, MlpXcdArgs>::type;
 
 struct MlpXcdLds {             // offsets (floats) into the dynamic LDS image behind the fragments and the input-weight rows
   int imgs, labs, xw, xL, scL, mL, vL, gL, Hs, dHs, dZs, small, w2p, red, redr, total;
@@ -153,8 +169,10 @@ static size_t mlp_xcd_lds_bytes() {
 // WV = waves per member: 8 (two per SIMD, four tiles each, one tile step at a time) or 4 (one per SIMD, eight tiles each,
 // stepped two at a time: every fragment read from LDS feeds two MFMAs and the wave has two independent dependent chains to
 // issue from -- what a lone wave per SIMD otherwise lacks)
-template <int PRE, int WV>
-__global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4 ? 1 : 2, WV == 4 ? 1 : 8))) void k_mlp_xcd(MlpXcdArgs a) {
+// HIST: also record the per-step history for the meta-gradient (l2o_mlp_unroll_multi_record): T + 1 gradient
+// evaluations (the one at x_T included), T optimizer steps -- k_mlp_unroll<PRE, FAST, true>'s record, per instance
+template <int PRE, int WV, bool HIST = false>
+__global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4 ? 1 : 2, WV == 4 ? 1 : 8))) void k_mlp_xcd(MlpXcdArgsT<HIST> a) {
   constexpr int kThreads = 64 * WV, kMxWaves = WV, kTPW = kMxSlots / WV;
   const long long kernel_t0 = __builtin_readcyclecounter();
   extern __shared__ __attribute__((aligned(16))) float mx_smem[];
@@ -512,7 +530,7 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
       *reinterpret_cast<f32x4*>(&dZs[s_l][4 * q]) = dzv;                      // (classes 10..15: zeros)
       const float lw = row_sum16(lse - zl);
       if (lane == 0) red[wv] = lw;
-      if (t < a.T) {
+      if (HIST || t < a.T) {                                                // (HIST: dH at x_T too)
         f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
@@ -539,7 +557,7 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
     __syncthreads();
     if (mem == 0 && tid == 0) I.fx[t] = ((red[0] + red[1]) + (red[2] + red[3])) * invB;
     pc.mark(4);
-    if (t == a.T) break;
+    if (!HIST && t == a.T) break;
     // ---- the w1 gradients of the member's coordinates on the matrix cores: wave = (row tile mt, hidden tile nt), K = the
     // 64 samples; D lands as lane (hidden 16 nt + c, q) <- image columns 16 mt + 4 q + r
     if (wv < 4 && owns_w1) {
@@ -598,6 +616,26 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
       gv = quad_q_sum(gv);
       if (q == 0) gL[slot * kTile + cc] = gv;
     }
+    if constexpr (HIST) {
+      // the scaled gradient at x_t as the LSTM phase below reads it (w1: behind the barrier above; b1 / w2 / b2: this
+      // wave's own LDS writes), and the state BEFORE this step's update
+      const MxHist& Hh = a.hist[inst];
+#pragma unroll
+      for (int k = 0; k < kTPW; ++k) {
+        const int slot = wv + kMxWaves * k;
+        const int ti = tile_of(slot);
+        if (ti < ntiles) {
+          const int var = var_of(ti);
+          const int jl = (ti - a.tile_begin[var]) * kTile + cc;
+          const int pos = slot * kTile + cc;
+          if (jl < a.n[var] && q == 0) Hh.g[var][(size_t)t * a.n[var] + jl] = gL[pos] * scL[pos];
+          if (t < a.T)
+            store_tile_state(sr[k], Hh.st[var] + ((size_t)t * (a.tile_begin[var + 1] - a.tile_begin[var]) + ti - a.tile_begin[var]) *
+                                                     kStateFloatsPerTile, lane);
+        }
+      }
+      if (t == a.T) break;                                   // (the gradient at x_T was still needed)
+    }
     if constexpr (WV == 8) {                                 // one tile step at a time, two waves per SIMD fill each other's stalls
       // (measured and removed, profiles/r06_c5_xcd_forms_ab.txt: starting waves 4-7 of a member 0.9 / 1.8 / 2.7 k cycles late --
       //  the two waves of a SIMD leave the barrier together and run the same sequence -- costs exactly the delay: 4.68 / 4.71 /
@@ -618,6 +656,13 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
           rnnprop_inputs(gv, m, v, a.np.beta1, a.np.beta2, a.np.omb1, a.np.omb2, om1, om2, in0, in1);
           if (!live) { in0 = 0.0f; in1 = 0.0f; }
           if (q == 0) { mL[pos] = m; vL[pos] = v; }
+          if constexpr (HIST) {
+            if (live && q == 0) {                            // the moments AFTER the step
+              const int jl = (ti - a.tile_begin[var]) * kTile + cc;
+              a.hist[inst].m[var][(size_t)(t + 1) * a.n[var] + jl] = m;
+              a.hist[inst].v[var][(size_t)(t + 1) * a.n[var] + jl] = v;
+            }
+          }
         } else {
           preprocess_grad<PRE>(gv, a.np.k_inv_ln2, a.np.exp_k, in0, in1);
         }
@@ -654,6 +699,13 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
         rnnprop_inputs(gv, m, v, a.np.beta1, a.np.beta2, a.np.omb1, a.np.omb2, om1, om2, io.in0, io.in1);
         if (!io.live) { io.in0 = 0.0f; io.in1 = 0.0f; }
         if (q == 0 && io.real) { mL[io.pos] = m; vL[io.pos] = v; }
+        if constexpr (HIST) {
+          if (io.live && q == 0) {                           // the moments AFTER the step
+            const int jl = (ti - a.tile_begin[var]) * kTile + cc;
+            a.hist[inst].m[var][(size_t)(t + 1) * a.n[var] + jl] = m;
+            a.hist[inst].v[var][(size_t)(t + 1) * a.n[var] + jl] = v;
+          }
+        }
       } else {
         preprocess_grad<PRE>(gv, a.np.k_inv_ln2, a.np.exp_k, io.in0, io.in1);
       }

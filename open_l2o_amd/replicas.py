@@ -13,6 +13,7 @@ eight instances (l2o_mlp_unroll_multi), or one after the other on the whole chip
     reps = Replicas(optimizer, [problems.mnist(...) for _ in range(8)], len_unroll=200)
     reps.reset()
     fx = reps.run({step: 1})            # -> [8] final losses; reps.fx_arrays: the T + 1 losses of every instance
+    out = reps.train_step({step: 1}, 1e-3)   # one meta-training step on all of them: the mean of their meta-gradients
 
 Every instance draws its own initial weights and its own minibatches, exactly as N separate ``meta_loss`` graphs would.
 """
@@ -23,8 +24,10 @@ import warnings
 
 import numpy as np
 
+import torch
+
 from . import _abi
-from ._graph_core import _term_vars
+from ._graph_core import _DevGrad, _all_reduce, _world
 
 
 class Replicas(object):
@@ -69,7 +72,7 @@ class Replicas(object):
             if ph is g0.step:
                 out[g.step] = val
             elif ph in g0.scale:
-                raise ValueError("x-scale placeholders are not supported by Replicas.run")
+                raise ValueError("x-scale placeholders are not supported by Replicas")
             else:
                 out[ph] = val
         return out
@@ -186,3 +189,156 @@ class Replicas(object):
             g.last_path = "mlp_xcd"
         self.fx_arrays = fx_host
         return np.array([f[T] for f in fx_host], np.float32)
+
+    # -- meta-training (DM/meta.py:398-414, DM/meta_rnnprop_train.py:559-593) on all replicas at once -----------------------
+    def _check_shared(self):
+        """The replicas of a train step: problems.mnist over ONE data set, all variables stepped by ONE network."""
+        g0 = self.graphs[0]
+        for g in self.graphs:
+            g._ensure_init()
+            nets = {id(s.net) for s in g.slots}
+            if (g.second_derivatives or len(g.terms) != 1 or g.terms[0].kind != _abi.PROB_MLP or len(nets) != 1
+                    or g.slots[0].net is not g0.slots[0].net or g._mlp_desc(g.terms[0]) is not g0._mlp_desc(g0.terms[0])):
+                raise ValueError("Replicas.train_step: the replicas must be problems.mnist instances over ONE data set, stepped "
+                                 "by one LSTM network, without second derivatives")
+
+    def _sync_weights(self):
+        """Every rank starts from rank 0's network weights (once per Replicas): the meta-gradient is averaged over the
+        ranks, so identical weights stay identical."""
+        import torch.distributed as dist
+        nets = self.graphs[0].nets
+        box = [{key: {m: {v: np.asarray(a, np.float32) for v, a in d.items()} for m, d in net.variables.items()}
+                for key, net in sorted(nets.items())}]
+        dist.broadcast_object_list(box, src=0)
+        for key, net in sorted(nets.items()):
+            for m, d in box[0][key].items():
+                for v, a in d.items():
+                    net.assign(m, v, a)
+
+    def _record_xcd(self, feed, step0):
+        """The forward of a train step on the one-instance-per-XCD recording kernel (l2o_mlp_unroll_multi_record):
+        launches of up to eight replicas; every replica's history goes to its own buffers (its graph's record plan,
+        built once per set of variable buffers).  Returns [(record, fx device [T + 1])] per replica."""
+        graphs = self.graphs
+        eng = graphs[0].engine
+        T = self.len_unroll
+        drew = self._draw_all()
+        insts, hists, out = [], [], []
+        for g in graphs:
+            inst = g.mlp_instance(self._feed(g, feed), draw=not drew)
+            if inst is None or (insts and (inst["desc"] is not insts[0]["desc"] or inst["net"] is not insts[0]["net"])):
+                raise ValueError("Replicas.train_step: the replicas must be problems.mnist instances over ONE data set, "
+                                 "stepped by one (20, 20) LSTM network")
+            slots = g.slots
+            panels = [v.value.view(*g._panel_shape(v)) for v in g.x]
+            plan = g._mlp_hist_plan(T, panels, slots, [s.state for s in slots], [s.m for s in slots], [s.v for s in slots])
+            rec = dict(step0=step0, shapes=[tuple(p.shape) for p in panels], g=plan["g"], st=plan["st"], m=plan["m"],
+                       v=plan["v"], g_final=plan["g_final"], plan=plan)
+            insts.append(inst)
+            hists.append(plan["hist"])
+            out.append((rec, inst["fx"]))
+            g.last_path = "mlp_xcd"
+        net, desc = insts[0]["net"], insts[0]["desc"]
+        wpack = net.wpack(eng)
+        for k in range(0, len(insts), 8):
+            eng.mlp_unroll_multi(net.spec, wpack, desc, insts[k:k + 8], T, step0, hists=hists[k:k + 8])
+        return out
+
+    def train_step(self, feed, learning_rate, form="auto"):
+        """One meta-training step on all N replicas, which share the optimizer's networks: loss L = (1/N) sum_r sum_t
+        fx_t^r, so the weight gradient is the MEAN of the N single-replica meta-gradients (each what UnrollGraph.train_step
+        computes for that replica alone), and ONE Adam step of the optimizer applies it.  Under torch.distributed the
+        gradient is also averaged over the ranks (the mean over N x world replicas).
+        Forward: launches of up to eight replicas on the recording one-instance-per-XCD kernel where it applies
+        (last_form "xcd"), else each replica's own recording unroll (last_form "chip").  Backward: the replicas' panels
+        pooled two replicas per fused BPTT launch (4 panels each; the launch takes 8).
+        A partner timeout of a recording kernel skips the (device-side, status-guarded) update, takes the Adam step back
+        and raises L2OPartnerTimeout, as UnrollGraph.train_step does.
+        Returns {"loss": mean over the replicas of sum_t fx_t, "fx": [N] final losses}; fx_arrays as run()."""
+        if form not in ("auto", "xcd", "chip"):
+            raise ValueError("form must be auto, xcd or chip")
+        graphs = self.graphs
+        g0 = graphs[0]
+        eng = g0.engine
+        T = self.len_unroll
+        feed = feed or {}
+        for ph in feed:
+            if ph in g0.scale:
+                raise ValueError("x-scale placeholders are not supported by Replicas")
+        self._check_shared()
+        rank, world = _world()
+        if world > 1 and not self.__dict__.get("_weights_synced"):
+            self._sync_weights()
+            self._weights_synced = True
+        step0 = int(feed[g0.step]) if g0.rnnprop else 1
+        use_xcd = form == "xcd" or (form == "auto" and self.xcd_supported())
+        if use_xcd and not self.xcd_supported():
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "Replicas.train_step(form='xcd'): l2o_mlp_unroll_multi_record "
+                                      "does not apply to this optimizee / network / device")
+        if use_xcd:
+            self.last_form = "xcd"
+            runs = self._record_xcd(feed, step0)
+            fused = hasattr(eng, "check_unroll_status")
+        else:
+            self.last_form = "chip"
+            runs = []
+            for g in graphs:
+                rec = {}
+                fx, _ = g.launch(self._feed(g, feed), True, record=rec)
+                runs.append((rec, fx))
+            fused = all(g.last_path in ("fused", "mlp_unroll") for g in graphs) and hasattr(eng, "check_unroll_status")
+        # backward: one accumulator per network over all replicas, two replicas per BPTT launch
+        out = {}
+        sets = [g._bptt_panel_sets(rec) for g, (rec, _) in zip(graphs, runs)]
+        caches = self.__dict__.setdefault("_bwd_tables", {})
+        for r0 in range(0, len(graphs), 2):
+            for key, (net, _) in sets[r0].items():
+                panels = [pn for ps in sets[r0:r0 + 2] for pn in ps[key][1]]
+                # (the BPTT pointer table of the group: keyed by what it points to -- step 0 of every history buffer)
+                ckey = (T,) + tuple(0 if a is None else a.data_ptr() for pn in panels if T
+                                    for a in (pn["gs"][0], pn["sts"][0], pn["ms"][0], pn["vs"][0]))
+                if ckey not in caches and len(caches) >= 16:
+                    caches.pop(next(iter(caches)))
+                g0._bptt_panels(net, out.setdefault(key, {}), T, step0, panels, cache=caches.setdefault(ckey, {}))
+        srcs = g0.__dict__.get("_gm_src", {})
+        n_rep = len(graphs)
+        for acc in out.values():                           # the mean: (1/N) sum, then over the ranks
+            srcs.pop(id(acc), None)
+            keys = sorted(acc)
+            flat = torch.cat([acc[k].reshape(-1) for k in keys])
+            if n_rep > 1:
+                eng.lincomb(flat, flat, 1.0 / n_rep)
+            if world > 1:
+                _all_reduce(flat)
+                eng.lincomb(flat, flat, 1.0 / world)
+            off = 0
+            for k in keys:
+                n = acc[k].numel()
+                acc[k] = flat[off:off + n].view(acc[k].shape)
+                off += n
+        early = all(g0._device_adam(g0.nets[k]) for k in out)
+        if early:
+            grads = {key: {k: _DevGrad(v) for k, v in acc.items()} for key, acc in out.items()}
+        else:
+            grads = {key: {k: eng.to_numpy(v) for k, v in acc.items()} for key, acc in out.items()}
+        if world > 1 and fused and hasattr(eng, "unroll_status_tensor"):
+            # every rank takes the same decision about the meta-step: the status word is MAX-reduced ahead of the guard
+            stw = eng.unroll_status_tensor()
+            red = torch.zeros(1, dtype=torch.int32, device=eng.device) if stw is None else stw.clone()
+            _all_reduce(red, op="MAX")
+            if stw is not None:
+                stw.copy_(red)
+        if early:
+            g0._adam_apply(grads, learning_rate, guarded=fused)
+        if fused and hasattr(eng, "prefetch_unroll_status"):
+            eng.prefetch_unroll_status()                    # (rides on the sync below)
+        fx_host = [eng.to_numpy(fx) for _, fx in runs]      # host sync
+        if fused:
+            g0._guarded_pending = g0.__dict__.get("_guarded_pending", 0) + (1 if early else 0)
+            g0._check_unroll_status()                       # raise: the guarded update did not run, its step is taken back
+        g0._guarded_pending = 0
+        if not early:
+            g0._adam_apply(grads, learning_rate)
+        self.fx_arrays = fx_host
+        return {"loss": np.float32(np.mean([f.sum(dtype=np.float32) for f in fx_host], dtype=np.float32)),
+                "fx": np.array([f[T] for f in fx_host], np.float32)}

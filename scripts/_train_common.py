@@ -11,7 +11,10 @@ open_l2o_amd -- same flags, same schedule:
   * --if_scale: random per-coordinate rescaling of the optimizee (DM/util.py:40-54);
   * --if_mt: with probability mt_ratio an epoch is an imitation epoch -- the trajectory of an
     analytic optimizer (--optimizers adam,rmsprop,nag; open_l2o_amd.data_generator) is recorded
-    on a fresh problem and the networks regress its updates (DM/train_dm.py:112-146).
+    on a fresh problem and the networks regress its updates (DM/train_dm.py:112-146);
+  * --replicas N (--problem mnist): every training segment is ONE meta-step on N optimizee instances
+    at once (open_l2o_amd.replicas.Replicas.train_step: the mean of their meta-gradients; up to eight
+    per launch of the one-instance-per-XCD kernel at minibatch 64).  Evaluation is unchanged.
 """
 import argparse
 import os
@@ -62,6 +65,8 @@ def parse_flags(rnnprop):
     p.add_argument("--synthetic_label_noise", type=float, default=0.0,
                    help="fraction of the synthetic labels re-drawn uniformly (problems.synthetic_mnist)")
     p.add_argument("--synthetic_seed", type=int, default=0)
+    p.add_argument("--replicas", type=int, default=1,
+                   help="--problem mnist: meta-train on N optimizee instances per step (the mean of their meta-gradients)")
     if rnnprop:
         p.add_argument("--beta1", type=float, default=0.95)
         p.add_argument("--beta2", type=float, default=0.95)
@@ -104,6 +109,24 @@ class Trainer(object):
             self.minimize, self.scale, self.var_x = out[0], out[1], out[2]
             mt = out[5:]
         self.loss_mt, self.steps_mt, self.update_mt, self.reset_mt, self.mt_labels, self.mt_inputs = mt
+        self.replicas = None
+        n_rep = getattr(flags, "replicas", 1)
+        if n_rep < 1:
+            raise ValueError("--replicas must be >= 1")
+        if n_rep > 1:
+            if flags.problem != "mnist":
+                raise ValueError("--replicas > 1 is implemented for --problem mnist only")
+            if flags.if_scale or flags.if_mt or flags.second_derivatives or flags.if_cl:
+                raise ValueError("--replicas > 1 does not combine with --if_scale, --if_mt, --if_cl or --second_derivatives")
+            from open_l2o_amd.replicas import Replicas
+            mg = self.optimizer.graph                      # (the evaluation graph: its networks are the ones trained)
+            self.replicas = Replicas(self.optimizer, [problem] * n_rep, flags.unroll_length, assignments)
+            for g in self.replicas.graphs:
+                g.nets = mg.nets
+                for s in g.slots:
+                    s.net = mg.nets[s.key]
+            self.optimizer._graph, self.optimizer._nets = mg, mg.nets
+            self.form_logged = False
         self.data_mt = None
         if flags.if_mt:                                        # DM/train_dm.py:91-96
             from open_l2o_amd.data_generator import data_loader
@@ -119,6 +142,21 @@ class Trainer(object):
             extra.update(scale=self.scale, rd_scale=self.f.if_scale, rd_scale_bound=self.f.rd_scale_bound,
                          assign_func=lambda vals: [v.load(a) for v, a in zip(self.var_x, vals)], var_x=self.var_x)
         return util.run_epoch(sess, cost_op, ops, reset, n_unrolls, **extra)
+
+    def _replica_epoch(self, n_unrolls):
+        """All replicas reset, then n_unrolls replica train steps; returns (seconds, the replicas' mean final loss of
+        the last one) as util.run_epoch does for one instance."""
+        reps, f = self.replicas, self.f
+        start = timer()
+        reps.reset()
+        cost = None
+        for i in range(n_unrolls):
+            feed = {reps.step: i * f.unroll_length + 1} if self.rnnprop else {}
+            cost = float(np.mean(reps.train_step(feed, f.learning_rate)["fx"]))
+            if not self.form_logged:
+                print("replicas={}, form={}".format(len(reps.graphs), reps.last_form), flush=True)
+                self.form_logged = True
+        return timer() - start, cost
 
     def _assign(self, vals):
         for v, a in zip(self.var_x, vals):
@@ -159,7 +197,9 @@ class Trainer(object):
                     if random.random() < mt_ratio:
                         mti = (mti + 1) % f.num_mt
                         task_i = mti
-                if task_i == -1:
+                if self.replicas is not None:
+                    _, cost = self._replica_epoch(n_train)
+                elif task_i == -1:
                     _, cost = self._epoch(sess, [update, step], n_train, train=True)
                 else:
                     _, cost = self._imitation_epoch(sess, task_i, n_train)
