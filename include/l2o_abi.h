@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define L2O_ABI_VERSION 14
+#define L2O_ABI_VERSION 15   /* v15: l2o_mlp_unroll_multi(_record) also serve minibatch 128 */
 
 #define L2O_OK 0
 #define L2O_ERR_ARG (-1)
@@ -149,7 +149,8 @@ int l2o_last_unroll_form(void);
 #define L2O_OPT_MLP_UNROLL 7         /* 1*: l2o_mlp_unroll available to the host layer (0: it reports "unsupported")       */
 #define L2O_OPT_MLP_XCD_WAVES 8       /* l2o_mlp_unroll_multi (ABI v13): 0*: the form measured faster for the net (RNNProp: four
                                         waves per member, one per SIMD, eight tiles each stepped two at a time; the DM nets: eight
-                                        waves, two per SIMD, four tiles each); 1: eight waves always; 2: four waves always.
+                                        waves, two per SIMD, four tiles each); 1: eight waves always; 2: four waves always --
+                                        the four-wave form has minibatch 64 only: with 2, batch 128 is unsupported.
                                         (Until ABI v11 option 8 was L2O_OPT_PAIR_NORMAL, removed in v12.)                         */
 #define L2O_OPT_EXACT_GATES 9        /* 0*: LSTM gate GEMM as a 3-way bf16 split on v_mfma_f32_16x16x32_bf16 (fp32-level error,
                                         but the matrix pipe TRUNCATES small products inside an 8-slot group: a deterministic
@@ -317,9 +318,10 @@ int l2o_mlp_unroll_record(const l2o_net_cfg* cfg, const float* wpack /* device *
  * ONE instance a longer latency than l2o_mlp_unroll: the caller chooses per call.
  *   inst[j]   indices / x / st / m / v / x_scale / fx of instance j, each as in l2o_mlp_unroll (all instances share the
  *             network, `mlp` (shape and data set) and T / step0; every instance draws its own minibatches)
- * Supported (l2o_mlp_unroll_multi_supported() != 0) for the reference's shape only (hidden 20, 10 classes, minibatch 64,
- * n_in * 20 + 230 coordinates <= 16 368), 1 <= n_inst <= 8, and a device whose 8 XCDs x 32 CUs are all available to the
- * stream.  A team that does not assemble (masked / shared device) raises the sticky status word -> L2O_ERR_TIMEOUT. */
+ * Supported (l2o_mlp_unroll_multi_supported() != 0) for the reference's shape only (hidden 20, 10 classes, minibatch 64
+ * or -- ABI v15 -- 128, n_in * 20 + 230 coordinates <= 16 368), 1 <= n_inst <= 8, and a device whose 8 XCDs x 32 CUs are
+ * all available to the stream; minibatch 128 not with L2O_OPT_MLP_XCD_WAVES = 2 (the four-wave form serves 64 only).
+ * Every other shape: the predicate and l2o_mlp_unroll_multi_workspace_bytes return 0.  A team that does not assemble (masked / shared device) raises the sticky status word -> L2O_ERR_TIMEOUT. */
 typedef struct l2o_mlp_instance {
   const int32_t* indices;      /* device [T + 1][batch] */
   float* x[4];

@@ -2050,7 +2050,8 @@ int l2o_mlp_deep_fg(const l2o_mlp_deep* m, const int32_t* indices, const float* 
 struct MlpXcdLayout { int n[4], tile_begin[5], nw1; size_t team_off, inst_off, p_bytes, s_bytes, sm_bytes, inst_bytes, total; };
 static bool mlp_xcd_layout(const l2o_mlp* mlp, int n_inst, MlpXcdLayout* L) {
   if (!mlp || n_inst < 1 || n_inst > kMxMaxInst) return false;
-  if (mlp->n_hidden != kMxH || mlp->n_out != kMxO || mlp->batch != kMxB || mlp->n_in < 1) return false;
+  if (mlp->n_hidden != kMxH || mlp->n_out != kMxO || (mlp->batch != 64 && mlp->batch != 128) || mlp->n_in < 1) return false;
+  const int NO = mlp->batch * kMxH;                   // MxShape<batch>::kNO
   L->n[0] = mlp->n_in * kMxH; L->n[1] = kMxH; L->n[2] = kMxH * kMxO; L->n[3] = kMxO;
   L->tile_begin[0] = 0;
   for (int v = 0; v < 4; ++v) L->tile_begin[v + 1] = L->tile_begin[v] + tiles_per_problem(L->n[v]);
@@ -2059,18 +2060,25 @@ static bool mlp_xcd_layout(const l2o_mlp* mlp, int n_inst, MlpXcdLayout* L) {
   L->nw1 = (L->n[0] + kMxCoords - 1) / kMxCoords;
   L->team_off = sizeof(MlpWs);
   L->inst_off = L->team_off + 64;
-  L->p_bytes = sizeof(unsigned long long) * kMxMembers * kMxMembers * kMxR;
-  L->s_bytes = sizeof(unsigned long long) * 2 * kMxNO;
+  L->p_bytes = sizeof(unsigned long long) * kMxMembers * kMxMembers * (NO / kMxMembers);
+  L->s_bytes = sizeof(unsigned long long) * 2 * NO;
   L->sm_bytes = sizeof(unsigned long long) * 2 * kMxNSMp;
   L->inst_bytes = (L->p_bytes + L->s_bytes + L->sm_bytes + 255) & ~(size_t)255;
   L->total = L->inst_off + (size_t)n_inst * L->inst_bytes;
   return true;
 }
 
+// the four-wave form (k_mlp_xcd<PRE, 4>): L2O_OPT_MLP_XCD_WAVES = 2, or the build's default for RNNProp
+static bool mlp_xcd_four(const l2o_net_cfg* cfg) {
+  const int wopt = (int)opt(L2O_OPT_MLP_XCD_WAVES);
+  return wopt == 2 || (wopt == 0 && cfg->preprocess == L2O_PRE_FC_ELU && L2O_MLP_XCD_DEFAULT_FOUR);
+}
+
 int l2o_mlp_unroll_multi_supported(const l2o_net_cfg* cfg, const l2o_mlp* mlp, int32_t n_inst, void* stream) {
   OptScope opt_scope(cfg_optw(cfg));
   MlpXcdLayout L;
   if (!cfg || !net_ok_for_mfma(cfg) || !opt(L2O_OPT_MLP_UNROLL) || !mlp_xcd_layout(mlp, n_inst, &L)) return 0;
+  if (mlp->batch != 64 && mlp_xcd_four(cfg)) return 0;      // (the four-wave form has no batch-128 instantiation)
   // every XCD's 32 CUs must be able to host one workgroup each at the same time
   return coresident_cus((hipStream_t)stream) >= kMxMaxInst * kMxMembers ? 1 : 0;
 }
@@ -2090,6 +2098,11 @@ static int mlp_unroll_multi_launch(const l2o_net_cfg* cfg, const float* wpack, c
   if (!net_ok_for_mfma(cfg) || !mlp_xcd_layout(mlp, n_inst, &L) || coresident_cus(s) < kMxMaxInst * kMxMembers)
     return fail(L2O_ERR_UNSUPPORTED, "l2o_mlp_unroll_multi: no one-XCD kernel for n_in=%d hidden=%d out=%d batch=%d x %d instances "
                 "(needs the reference's shape and all 8 x 32 CUs)", mlp->n_in, mlp->n_hidden, mlp->n_out, mlp->batch, (int)n_inst);
+  // which form: four waves per member stepping tile PAIRS (a lone wave per SIMD with two independent chains; RNNProp: no
+  // spills at 438 registers) or eight waves stepping single tiles (two waves per SIMD; the DM nets' pair form spills)
+  const bool four = mlp_xcd_four(cfg);
+  if (four && mlp->batch != 64)
+    return fail(L2O_ERR_UNSUPPORTED, "l2o_mlp_unroll_multi: the four-wave one-XCD form serves batch 64 only (batch %d)", mlp->batch);
   const bool rn = cfg->preprocess == L2O_PRE_FC_ELU;
   MlpXcdHistArgs a;                                   // (the plain form is launched with its MlpXcdArgs part)
   std::memset(&a, 0, sizeof(a));
@@ -2131,33 +2144,38 @@ static int mlp_unroll_multi_launch(const l2o_net_cfg* cfg, const float* wpack, c
     }
   }
   HIP_TRY(hipMemsetAsync(wsb + L.team_off, 0, L.total - L.team_off, s));   // team counters + granules: the header survives
-  // which form: four waves per member stepping tile PAIRS (a lone wave per SIMD with two independent chains; RNNProp: no
-  // spills at 438 registers) or eight waves stepping single tiles (two waves per SIMD; the DM nets' pair form spills)
-  const int wopt = (int)opt(L2O_OPT_MLP_XCD_WAVES);
-  const bool four = wopt == 2 || (wopt == 0 && rn && L2O_MLP_XCD_DEFAULT_FOUR);
+  const bool b128 = mlp->batch == 128;
   size_t lds = 0;
   switch (cfg->preprocess) {
-    case L2O_PRE_IDENTITY: lds = mlp_xcd_lds_bytes<L2O_PRE_IDENTITY>(); break;
-    case L2O_PRE_LOGSIGN: lds = mlp_xcd_lds_bytes<L2O_PRE_LOGSIGN>(); break;
-    default: lds = mlp_xcd_lds_bytes<L2O_PRE_FC_ELU>();
+    case L2O_PRE_IDENTITY: lds = b128 ? mlp_xcd_lds_bytes<L2O_PRE_IDENTITY, 128>() : mlp_xcd_lds_bytes<L2O_PRE_IDENTITY, 64>(); break;
+    case L2O_PRE_LOGSIGN: lds = b128 ? mlp_xcd_lds_bytes<L2O_PRE_LOGSIGN, 128>() : mlp_xcd_lds_bytes<L2O_PRE_LOGSIGN, 64>(); break;
+    default: lds = b128 ? mlp_xcd_lds_bytes<L2O_PRE_FC_ELU, 128>() : mlp_xcd_lds_bytes<L2O_PRE_FC_ELU, 64>();
   }
   // one workgroup per CU of the whole chip: the 32 that land on XCD j < n_inst form instance j's team, the others exit
   const dim3 grid(kMxMaxInst * kMxMembers), block(four ? kMxThreads4 : kMxThreads);
   if (hist) {
     void (*fn)(MlpXcdHistArgs) = nullptr;
     switch (cfg->preprocess) {
-      case L2O_PRE_IDENTITY: fn = four ? k_mlp_xcd<L2O_PRE_IDENTITY, 4, true> : k_mlp_xcd<L2O_PRE_IDENTITY, 8, true>; break;
-      case L2O_PRE_LOGSIGN: fn = four ? k_mlp_xcd<L2O_PRE_LOGSIGN, 4, true> : k_mlp_xcd<L2O_PRE_LOGSIGN, 8, true>; break;
-      default: fn = four ? k_mlp_xcd<L2O_PRE_FC_ELU, 4, true> : k_mlp_xcd<L2O_PRE_FC_ELU, 8, true>;
+      case L2O_PRE_IDENTITY:
+        fn = b128 ? k_mlp_xcd<L2O_PRE_IDENTITY, 8, true, 128> : four ? k_mlp_xcd<L2O_PRE_IDENTITY, 4, true> : k_mlp_xcd<L2O_PRE_IDENTITY, 8, true>;
+        break;
+      case L2O_PRE_LOGSIGN:
+        fn = b128 ? k_mlp_xcd<L2O_PRE_LOGSIGN, 8, true, 128> : four ? k_mlp_xcd<L2O_PRE_LOGSIGN, 4, true> : k_mlp_xcd<L2O_PRE_LOGSIGN, 8, true>;
+        break;
+      default: fn = b128 ? k_mlp_xcd<L2O_PRE_FC_ELU, 8, true, 128> : four ? k_mlp_xcd<L2O_PRE_FC_ELU, 4, true> : k_mlp_xcd<L2O_PRE_FC_ELU, 8, true>;
     }
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(fn, grid, block, lds, s, a);
   } else {
     void (*fn)(MlpXcdArgs) = nullptr;
     switch (cfg->preprocess) {
-      case L2O_PRE_IDENTITY: fn = four ? k_mlp_xcd<L2O_PRE_IDENTITY, 4> : k_mlp_xcd<L2O_PRE_IDENTITY, 8>; break;
-      case L2O_PRE_LOGSIGN: fn = four ? k_mlp_xcd<L2O_PRE_LOGSIGN, 4> : k_mlp_xcd<L2O_PRE_LOGSIGN, 8>; break;
-      default: fn = four ? k_mlp_xcd<L2O_PRE_FC_ELU, 4> : k_mlp_xcd<L2O_PRE_FC_ELU, 8>;
+      case L2O_PRE_IDENTITY:
+        fn = b128 ? k_mlp_xcd<L2O_PRE_IDENTITY, 8, false, 128> : four ? k_mlp_xcd<L2O_PRE_IDENTITY, 4> : k_mlp_xcd<L2O_PRE_IDENTITY, 8>;
+        break;
+      case L2O_PRE_LOGSIGN:
+        fn = b128 ? k_mlp_xcd<L2O_PRE_LOGSIGN, 8, false, 128> : four ? k_mlp_xcd<L2O_PRE_LOGSIGN, 4> : k_mlp_xcd<L2O_PRE_LOGSIGN, 8>;
+        break;
+      default: fn = b128 ? k_mlp_xcd<L2O_PRE_FC_ELU, 8, false, 128> : four ? k_mlp_xcd<L2O_PRE_FC_ELU, 4> : k_mlp_xcd<L2O_PRE_FC_ELU, 8>;
     }
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(fn, grid, block, lds, s, static_cast<const MlpXcdArgs&>(a));

@@ -17,13 +17,14 @@
 //                    arrangement -- packed bf16x3 fragments in LDS, the LSTM state of the wave's four tiles in registers,
 //                    x / scale / moments of the 512 coordinates in LDS)
 //   per step    partial  P_m[s][h] = sum over the member's own w1 rows of img[s][k] w1[k][h] on the fp32 matrix cores
-//                        (7 v_mfma_f32_16x16x4_f32 per wave, exact fp32 products) -> the inbox of the member that reduces
-//                        sample pair s / 2, PLAIN stores: the lines stay in the XCD's L2
-//               reduce   member r adds the <= 31 partials of its 40 outputs in ascending source order, publishes the sums
-//               gather   every member polls the 1 280 sums (L1-bypassing loads: they hit the same L2), bias + sigmoid fused
-//               tail     logits / softmax / dZ / dH on the matrix cores (waves 0-3, as k_mlp_unroll's tail); the NEXT minibatch's
-//                        indices / image columns are requested at the head of the step / behind the gather, landed before the LSTM phase
-//               gradient G[k][h] = sum_s img[s][k] dH[s][h] for the member's 512 coordinates: 16 MFMAs per wave (waves 0-3)
+//                        (7 v_mfma_f32_16x16x4_f32 per (sample tile, hidden tile), exact fp32 products) -> the inbox of the
+//                        member that reduces sample s / (B / 32), PLAIN stores: the lines stay in the XCD's L2
+//               reduce   member r adds the <= 31 partials of its B * 20 / 32 outputs in ascending source order, publishes the sums
+//               gather   every member polls the B * 20 sums (L1-bypassing loads: they hit the same L2), bias + sigmoid fused
+//               tail     logits / softmax / dZ / dH on the matrix cores (one wave per 16 samples, as k_mlp_unroll's tail); the
+//                        NEXT minibatch's indices / image columns are requested at the head of the step / behind the gather,
+//                        landed before the LSTM phase
+//               gradient G[k][h] = sum_s img[s][k] dH[s][h] for the member's 512 coordinates: B / 4 MFMAs per wave (waves 0-3)
 //               LSTM     every wave steps its four tiles (bx::tile_step_w on the LDS fragments), x += delta
 //   Two hops through ONE coherent L2 instead of three hops of which one crosses the fabric; no XCC_ID table, no flat
 //   fallback protocol, no cross-XCD traffic at all.  What it costs: eight tile-steps per SIMD and step instead of one, so
@@ -38,25 +39,39 @@ constexpr int kMxThreads4 = 256;                  // form 4: four waves, one per
 constexpr int kMxSlots = 32;                      // tiles per member (four per wave)
 constexpr int kMxCoords = kMxSlots * kTile;       // 512 coordinate positions per member
 constexpr int kMxMaxInst = 8;                     // instances per launch = XCDs
-constexpr int kMxB = 64, kMxH = 20, kMxO = 10;    // k_mlp_unroll's FAST shape: minibatch 64 only (the reference's `mnist`
-                                                  // config, DM/util.py:146-155, draws 128: that goes to k_mlp_unroll)
-constexpr int kMxNO = kMxB * kMxH;                // all-reduced outputs per evaluation
-constexpr int kMxR = kMxNO / kMxMembers;          // outputs per reducer: 40 = two samples x 20 hidden units
+constexpr int kMxH = 20, kMxO = 10;
+// The minibatch B is a template parameter of the kernel: 64 (k_mlp_unroll's FAST shape, BASELINE config 5) or 128 (what the
+// reference's `mnist` problems draw, DM/problems.py: batch_size=128).  Both in the eight-wave form; the four-wave form
+// (L2O_OPT_MLP_XCD_WAVES = 2) exists at B = 64 only, and l2o_mlp_unroll_multi_supported says 0 for batch 128 when that
+// option forces it (the caller falls back to k_mlp_unroll).
+template <int B>
+struct MxShape {
+  static_assert(B == 64 || B == 128, "k_mlp_xcd: minibatch 64 or 128");
+  static constexpr int kNO = B * kMxH;                // all-reduced outputs per evaluation
+  static constexpr int kR = kNO / kMxMembers;         // outputs per reducer: 40 | 80 = two | four samples x 20 hidden units
+  static constexpr int kSpr = B / kMxMembers;         // samples per reducer: 2 | 4
+  static constexpr int kSprLog = B == 64 ? 1 : 2;
+  static constexpr int kST = B / 16;                  // sample tiles of 16: 4 | 8
+  static constexpr int kSTLog = B == 64 ? 2 : 3;
+  // B = 128: the next minibatch's sample indices wait in LDS (rows), not as one row index per image column in registers
+  // (7 per thread, held across the reduce and the gather, spill the DM instantiations)
+  static constexpr bool kRowsL = B > 64;
+};
 constexpr int kMxKR = 28;                         // image columns a member's 512 w1 coordinates touch (<= 27), 7 MFMA k-steps
 constexpr int kMxNSM = kMxH + kMxH * kMxO + kMxO; // b1 | w2 | b2
 constexpr int kMxNSMp = (kMxNSM + 1) & ~1;
 constexpr int kMxXwFront = 32, kMxXwBack = 64;    // zero margins of the member's scaled w1 row (index -19 .. 559)
 
 struct MxInst {                // one optimizee instance (replica)
-  const int* idx;              // [T + 1][64] minibatch indices
+  const int* idx;              // [T + 1][B] minibatch indices
   float* x[4];                 // w1 [n_in, 20], b1 [20], w2 [20, 10], b2 [10]   in-out
   float* st[4];                // packed LSTM state per variable                 in-out
   float* m[4];                 // RNNProp moments per variable                   in-out
   float* v[4];
   const float* xscale[4];      // per-coordinate scale or NULL
   float* fx;                   // [T + 1]
-  unsigned long long* P;       // [32 reducers][32 sources][40]  partial pre-activations (granules)
-  unsigned long long* S;       // [2][1280]                      their sums, by step parity
+  unsigned long long* P;       // [32 reducers][32 sources][B * 20 / 32]  partial pre-activations (granules)
+  unsigned long long* S;       // [2][B * 20]                    their sums, by step parity
   unsigned long long* Sm;      // [2][kMxNSMp]                   b1, w2, b2 (scaled), by step parity
 };
 
@@ -90,26 +105,37 @@ template <bool HIST>
 using MlpXcdArgsT = typename std::conditional<HIST, MlpXcdHistArgs, MlpXcdArgs>::type;
 
 struct MlpXcdLds {             // offsets (floats) into the dynamic LDS image behind the fragments and the input-weight rows
-  int imgs, labs, xw, xL, scL, mL, vL, gL, Hs, dHs, dZs, small, w2p, red, redr, total;
+  int imgs, labs, xw, xL, scL, mL, vL, gL, Hs, dHs, dZs, small, w2p, red, redr, rows, total;
 };
+template <int B>
 __host__ __device__ constexpr MlpXcdLds mlp_xcd_lds(int frag_floats, int win_floats) {
   MlpXcdLds L{};
   int o = frag_floats + win_floats;
-  L.imgs = o; o += 2 * kMxB * kMxKR;
-  L.labs = o; o += 2 * kMxB;
+  L.imgs = o; o += 2 * B * kMxKR;
+  L.labs = o; o += 2 * B;
   L.xw = o; o += kMxXwFront + kMxCoords + kMxXwBack;
   L.xL = o; o += kMxCoords;
   L.scL = o; o += kMxCoords;
   L.mL = o; o += kMxCoords;
   L.vL = o; o += kMxCoords;
   L.gL = o; o += kMxCoords;
-  L.Hs = o; o += kMxB * kMxH;
-  L.dHs = o; o += kMxB * kMxH;
-  L.dZs = o; o += kMxB * 16;
+  L.Hs = o; o += B * kMxH;
+  L.dHs = o; o += B * kMxH;
+  L.dZs = o; o += B * 16;
   L.small = o; o += 256;
   L.w2p = o; o += kMxH * 12;
   L.red = o; o += 16;
-  L.redr = o; o += kMxMembers * kMxR;
+  if (B == 64) {
+    L.redr = o; o += kMxMembers * MxShape<B>::kR;
+    L.rows = 0;
+  } else {
+    // B = 128 with RNNProp's fragments would need 161.4 KiB + the bias table, over a CU's 160 KiB: the reduce's staging
+    // rows (32 x 80 = B x 20 floats) share dH's space (151.9 KiB; the DM nets 136.9 / 141.9).  dH is written by the tail
+    // and last read by the LSTM phase's b1 gradients; redr is written and read between the partial phase and the gather:
+    // a barrier lies between the two on either side
+    L.redr = L.dHs;
+    L.rows = o; o += B;
+  }
   L.total = o;
   return L;
 }
@@ -161,9 +187,9 @@ __device__ __forceinline__ void mx_store2(unsigned long long* p, float v0, float
 template <int PRE>
 using MxW = bx::NetWBLF<PRE, L2O_MX_FRAG_DEPTH>;
 
-template <int PRE>
+template <int PRE, int B>
 static size_t mlp_xcd_lds_bytes() {
-  return sizeof(float) * (size_t)mlp_xcd_lds(LstmCoreLds<PRE, MxW<PRE>>::kFragWords, MxW<PRE>::kWinFloats).total;
+  return sizeof(float) * (size_t)mlp_xcd_lds<B>(LstmCoreLds<PRE, MxW<PRE>>::kFragWords, MxW<PRE>::kWinFloats).total;
 }
 
 // WV = waves per member: 8 (two per SIMD, four tiles each, one tile step at a time) or 4 (one per SIMD, eight tiles each,
@@ -171,13 +197,19 @@ static size_t mlp_xcd_lds_bytes() {
 // issue from -- what a lone wave per SIMD otherwise lacks)
 // HIST: also record the per-step history for the meta-gradient (l2o_mlp_unroll_multi_record): T + 1 gradient
 // evaluations (the one at x_T included), T optimizer steps -- k_mlp_unroll<PRE, FAST, true>'s record, per instance
-template <int PRE, int WV, bool HIST = false>
+// B: the minibatch, 64 or 128 (MxShape; 128 in the eight-wave form only)
+template <int PRE, int WV, bool HIST = false, int B = 64>
 __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4 ? 1 : 2, WV == 4 ? 1 : 8))) void k_mlp_xcd(MlpXcdArgsT<HIST> a) {
   constexpr int kThreads = 64 * WV, kMxWaves = WV, kTPW = kMxSlots / WV;
+  using Sh = MxShape<B>;
+  constexpr int kMxB = B, kMxNO = Sh::kNO, kMxR = Sh::kR;
+  static_assert(B == 64 || WV == 8, "k_mlp_xcd: minibatch 128 in the eight-wave form only");
   const long long kernel_t0 = __builtin_readcyclecounter();
   extern __shared__ __attribute__((aligned(16))) float mx_smem[];
   using Core = LstmCoreLds<PRE, MxW<PRE>>;
-  constexpr MlpXcdLds LY = mlp_xcd_lds(Core::kFragWords, MxW<PRE>::kWinFloats);
+  constexpr MlpXcdLds LY = mlp_xcd_lds<B>(Core::kFragWords, MxW<PRE>::kWinFloats);
+  // dynamic + static (bias table, team slot) LDS within the 160 KiB of a gfx950 CU
+  static_assert(sizeof(float) * (LY.total + Core::kBiasFloats) + 2 * sizeof(int) <= 160 * 1024, "k_mlp_xcd: LDS over 160 KiB");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int q = lane >> 4;
@@ -225,6 +257,7 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
   float (*w2p)[12] = reinterpret_cast<float (*)[12]>(mx_smem + LY.w2p);
   float* red = mx_smem + LY.red;
   float (*redr)[kMxR] = reinterpret_cast<float (*)[kMxR]>(mx_smem + LY.redr);
+  int* rowsL = reinterpret_cast<int*>(mx_smem + LY.rows);  // (Sh::kRowsL) the next minibatch's sample indices
 
   const int n_in = a.n_in;
   const int ntiles = a.tile_begin[4];
@@ -359,28 +392,31 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
     // ---- the NEXT evaluation's minibatch, stage A: its indices -> registers (stage B, behind the gather: the image columns;
     // stage C, in front of the LSTM phase: -> the other parity buffer).  Two dependent global latencies, neither of them
     // waited for where it is issued.
+    // (Sh::kRowsL: only the index of sample tid, to LDS in front of the reduce's barrier; stage B reads the rows from there)
     constexpr int kPf = (kMxB * kMxKR + kThreads - 1) / kThreads;
-    int pf_row[kPf], pf_lab = 0;
+    int pf_row[Sh::kRowsL ? 1 : kPf], pf_lab = 0;
     float pf_val[kPf];
     const bool have_next = t < a.T;
     if (have_next) {
       const int* ix1 = I.idx + (size_t)(t + 1) * kMxB;
+      if constexpr (!Sh::kRowsL) {
 #pragma unroll
-      for (int u = 0; u < kPf; ++u) {
-        const int e = tid + kThreads * u;
-        pf_row[u] = e < kMxB * kMxKR ? ix1[e / kMxKR] : 0;
+        for (int u = 0; u < kPf; ++u) {
+          const int e = tid + kThreads * u;
+          pf_row[u] = e < kMxB * kMxKR ? ix1[e / kMxKR] : 0;
+        }
       }
       if (tid < kMxB) pf_lab = ix1[tid];
     }
     pc.mark(0);
     // ---- partial hidden pre-activations on the fp32 matrix cores: wave = (sample tile st, hidden tile ht);
     // D lands as lane (sample 16 st + c, q) <- hidden units 16 ht + 4 q + r: four consecutive outputs of one sample ->
-    // two granule pairs in the inbox of the member that reduces sample pair s / 2
+    // two granule pairs in the inbox of the member that reduces samples [s / kSpr * kSpr, + kSpr)
     if (owns_w1)
 #pragma unroll
-    for (int ci = 0; ci < 8 / kMxWaves; ++ci) {              // eight (sample tile, hidden tile) products over the member's waves
+    for (int ci = 0; ci < 2 * Sh::kST / kMxWaves; ++ci) {    // 8 | 16 (sample tile, hidden tile) products over the member's waves
       const int cb = wv + kMxWaves * ci;
-      const int st_ = cb & 3, ht = cb >> 2;
+      const int st_ = cb & (Sh::kST - 1), ht = cb >> Sh::kSTLog;
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       const bool arow = ht == 0 || cc < kMxH - 16;         // hidden rows 16 .. 19 only
 #pragma unroll
@@ -392,7 +428,8 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
       mx_settle(acc);
       if (ht == 0 || q == 0) {
         const int sidx = 16 * st_ + cc;
-        unsigned long long* dst = I.P + ((size_t)((sidx >> 1) * kMxMembers + mem)) * kMxR + (sidx & 1) * kMxH + 16 * ht + 4 * q;
+        unsigned long long* dst =
+            I.P + ((size_t)((sidx >> Sh::kSprLog) * kMxMembers + mem)) * kMxR + (sidx & (Sh::kSpr - 1)) * kMxH + 16 * ht + 4 * q;
         mx_store2(dst, acc[0], acc[1], tag);
         mx_store2(dst + 2, acc[2], acc[3], tag);
       }
@@ -405,9 +442,10 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
     }
     pc.mark(1);
     note_dead(dead, t, 2);
-    // ---- reduce: this member's 40 outputs over the w1 owners: thread = (pair p, source), all loads first, then the tags
+    // ---- reduce: this member's 40 | 80 outputs over the w1 owners: thread = (pair p, source), all loads first, then the tags
     {
-      constexpr int kSrcRound = kThreads / (kMxR / 2);                                  // sources per round: 25 (form 8) | 12 (form 4)
+      // sources per round: 25 (form 8, B = 64) | 12 (form 4; form 8, B = 128)
+      constexpr int kSrcRound = kThreads / (kMxR / 2);
       constexpr int kRounds = (kMxMembers - 1 + kSrcRound - 1) / kSrcRound;             // 2 | 3
       const int pq = tid % (kMxR / 2), s0 = tid / (kMxR / 2);
       const unsigned long long* inbox = I.P + ((size_t)mem * kMxMembers) * kMxR + 2 * pq;
@@ -437,6 +475,9 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
           redr[s0 + 2 * kSrcRound][2 * pq + 1] = __uint_as_float(d2[2]);
         }
       }
+      if constexpr (Sh::kRowsL) {
+        if (have_next && tid < kMxB) rowsL[tid] = pf_lab;
+      }
       lds_barrier();
       if (tid < kMxR / 2) {                                 // ascending source order: the same sum whoever computes it
         float t0 = 0.0f, t1 = 0.0f;
@@ -446,10 +487,11 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
     }
     pc.mark(2);
     note_dead(dead, t, 3);
-    // ---- gather the 1 280 sums (pairs), bias + activation fused into the LDS write
+    // ---- gather the 1 280 | 2 560 sums (pairs), bias + activation fused into the LDS write
     {
       const unsigned long long* Sp = I.S + (size_t)par * kMxNO;
-      constexpr int kG = (kMxNO / 2 + kThreads - 1) / kThreads;                         // pairs per thread: 2 | 3
+      // pairs per thread: 2 (form 8, B = 64) | 3 (form 4; form 8, B = 128)
+      constexpr int kG = (kMxNO / 2 + kThreads - 1) / kThreads;
       const bool w0 = tid < kMxNO / 2, w1 = tid + kThreads < kMxNO / 2, w2 = kG > 2 && tid + 2 * kThreads < kMxNO / 2;
       const unsigned long long* q0 = Sp + 2 * (w0 ? tid : 0);
       const unsigned long long* q1 = Sp + 2 * (w1 ? tid + kThreads : 0);
@@ -483,15 +525,18 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
 #pragma unroll
       for (int u = 0; u < kPf; ++u) {
         const int e = tid + kThreads * u, kk = e % kMxKR;
-        pf_val[u] = (e < kMxB * kMxKR && owns_w1 && k0 + kk < n_in) ? a.images[(size_t)pf_row[u] * n_in + k0 + kk] : 0.0f;
+        int row;
+        if constexpr (Sh::kRowsL) row = e < kMxB * kMxKR ? rowsL[e / kMxKR] : 0;
+        else row = pf_row[u];
+        pf_val[u] = (e < kMxB * kMxKR && owns_w1 && k0 + kk < n_in) ? a.images[(size_t)row * n_in + k0 + kk] : 0.0f;
       }
       if (tid < kMxB) pf_lab = a.labels[pf_lab];
     }
     __syncthreads();
     pc.mark(3);
     note_dead(dead, t, 4);
-    // ---- waves 0-3: forward tail + dH on the fp32 matrix cores (k_mlp_unroll's tail: wave w owns samples 16 w .. 16 w + 15)
-    if (wv < 4) {
+    // ---- waves 0-3 | 0-7: forward tail + dH on the fp32 matrix cores (k_mlp_unroll's tail: wave w owns samples 16 w .. 16 w + 15)
+    if (wv < Sh::kST) {
       const int s_l = 16 * wv + cc;
       f32x4 zacc;
 #pragma unroll
@@ -555,11 +600,14 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WV == 4
       }
     }
     __syncthreads();
-    if (mem == 0 && tid == 0) I.fx[t] = ((red[0] + red[1]) + (red[2] + red[3])) * invB;
+    if (mem == 0 && tid == 0) {
+      if constexpr (B == 64) I.fx[t] = ((red[0] + red[1]) + (red[2] + red[3])) * invB;
+      else I.fx[t] = (((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]))) * invB;
+    }
     pc.mark(4);
     if (!HIST && t == a.T) break;
     // ---- the w1 gradients of the member's coordinates on the matrix cores: wave = (row tile mt, hidden tile nt), K = the
-    // 64 samples; D lands as lane (hidden 16 nt + c, q) <- image columns 16 mt + 4 q + r
+    // B samples (16 | 32 MFMAs); D lands as lane (hidden 16 nt + c, q) <- image columns 16 mt + 4 q + r
     if (wv < 4 && owns_w1) {
       const int mt = wv & 1, nt = wv >> 1;
       const bool brow = nt == 0 || cc < kMxH - 16;

@@ -14,7 +14,8 @@ open_l2o_amd -- same flags, same schedule:
     on a fresh problem and the networks regress its updates (DM/train_dm.py:112-146);
   * --replicas N (--problem mnist): every training segment is ONE meta-step on N optimizee instances
     at once (open_l2o_amd.replicas.Replicas.train_step: the mean of their meta-gradients; up to eight
-    per launch of the one-instance-per-XCD kernel at minibatch 64).  Evaluation is unchanged.
+    per launch of the one-instance-per-XCD kernel at minibatch 64 or 128 -- the mnist default; other minibatches
+    run the replicas one after the other).  Evaluation is unchanged.
 """
 import argparse
 import os
@@ -66,7 +67,8 @@ def parse_flags(rnnprop):
                    help="fraction of the synthetic labels re-drawn uniformly (problems.synthetic_mnist)")
     p.add_argument("--synthetic_seed", type=int, default=0)
     p.add_argument("--replicas", type=int, default=1,
-                   help="--problem mnist: meta-train on N optimizee instances per step (the mean of their meta-gradients)")
+                   help="--problem mnist: meta-train on N optimizee instances per step (the mean of their meta-gradients); "
+                        "eight per launch, one per XCD, at --batch_size 64 or 128 (the default)")
     if rnnprop:
         p.add_argument("--beta1", type=float, default=0.95)
         p.add_argument("--beta2", type=float, default=0.95)

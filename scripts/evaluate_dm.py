@@ -38,7 +38,9 @@ def main():
                        help="problems.mnist on N synthetic MNIST-shaped examples (no dataset ships offline)")
     flags.add_argument("--replicas", type=int, default=1,
                        help="(ours) evaluate this many independent instances of the optimizee TOGETHER (own initial weights, "
-                            "own minibatches; problems.mnist on the MI355X: eight per launch, one per XCD -- "
+                            "own minibatches; problems.mnist with one hidden layer of 20 at --batch_size 64 or 128 (the "
+                            "default): eight per launch, one per XCD, other minibatches one instance at a time on the whole "
+                            "chip -- "
                             "open_l2o_amd.replicas.Replicas); the loss record holds one list per instance")
     FLAGS = flags.parse_args()
 
