@@ -93,6 +93,15 @@ class MlpDeepDesc:
     labels: torch.Tensor
 
 
+@dataclasses.dataclass
+class MnistConvDesc:
+    """Device-side view of problems.mnist_conv (struct l2o_mnist_conv)."""
+    batch: int
+    batch_norm: bool
+    images: torch.Tensor      # [n_data, 784] fp32 (NHWC 28x28x1)
+    labels: torch.Tensor      # [n_data] int32
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -314,6 +323,25 @@ class HipEngine(object):
         ga = None if grads is None else (C.c_void_p * nptr)(*[t.data_ptr() for t in grads])
         _abi.check(self.lib.l2o_mlp_deep_fg(C.byref(c), C.c_void_p(indices.data_ptr()), wa, _ptr(loss), ga, _ptr(scr),
                                             self._stream()))
+
+    def mnist_conv_fg(self, d: MnistConvDesc, indices, ws, loss, grads):
+        """Loss and gradients of the conv-net optimizee on ONE minibatch (l2o_mnist_conv_fg).  ws / grads: lists of device
+        tensors in the graph's variable order (10 with batch norm, 6 without; grads may be None: forward only)."""
+        c = _abi.MnistConv()
+        c.batch, c.n_data, c.batch_norm, c.flags = d.batch, int(d.images.shape[0]), 1 if d.batch_norm else 0, 0
+        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
+        n = int(self.lib.l2o_mnist_conv_scratch_floats(C.byref(c)))
+        if not n:
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_mnist_conv_fg: unsupported minibatch %d" % d.batch)
+        if len(ws) != (10 if d.batch_norm else 6) or (grads is not None and len(grads) != len(ws)):
+            raise ValueError("l2o_mnist_conv_fg: %d variables for batch_norm=%r" % (len(ws), d.batch_norm))
+        scr = self.__dict__.get("_mnist_conv_scratch")
+        if scr is None or scr.numel() < n:
+            scr = self._mnist_conv_scratch = self.empty(n)
+        wa = (C.c_void_p * len(ws))(*[_ptr(t).value for t in ws])
+        ga = None if grads is None else (C.c_void_p * len(grads))(*[_ptr(t).value for t in grads])
+        _abi.check(self.lib.l2o_mnist_conv_fg(C.byref(c), C.c_void_p(indices.data_ptr()), wa, _ptr(loss), ga, _ptr(scr),
+                                              self._stream()))
 
     def mlp_unroll_supported(self, spec: NetSpec, d: MlpDesc):
         """A fused persistent unroll exists for this (net, MLP optimizee) pair on this device (l2o_mlp_unroll)."""

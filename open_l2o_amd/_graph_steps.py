@@ -12,6 +12,9 @@ import torch
 from . import _abi, networks
 from ._graph_core import PackedState, _DevGrad, _LazyHost, _term_vars, _world, rng  # noqa: F401
 
+# the optimizees that draw a minibatch per evaluation (problems.mnist, problems.mnist_conv)
+_SAMPLED = (_abi.PROB_MLP, _abi.PROB_MNIST_CONV)
+
 
 class StepPlanMixin(object):
     def _execute_many_sampled(self, n):
@@ -193,7 +196,7 @@ class StepPlanMixin(object):
         if self.__dict__.get("_reuse_minibatches") and bufs:
             return                                          # (recovery re-run of an unroll: the minibatches it drew)
         for k, term in enumerate(self.terms):
-            if term.kind != _abi.PROB_MLP:
+            if term.kind not in _SAMPLED:
                 continue
             d = self._mlp_desc(term)
             sampler = term.hyper.get("sampler")
@@ -214,8 +217,16 @@ class StepPlanMixin(object):
                 bufs[k] = new
 
     def _mlp_desc(self, term):
-        """Device copy of the dataset of a problems.mnist term (uploaded once)."""
+        """Device copy of the dataset of a problems.mnist / mnist_conv term (uploaded once)."""
         cache = self.__dict__.setdefault("_mlp_cache", {})
+        if term.kind == _abi.PROB_MNIST_CONV:                  # problems.mnist_conv: l2o_mnist_conv_fg
+            key = (id(term.hyper["images"]), "conv", term.hyper["batch_size"], term.hyper["batch_norm"])
+            if key not in cache:
+                from ._engine import MnistConvDesc
+                cache[key] = MnistConvDesc(batch=int(term.hyper["batch_size"]), batch_norm=bool(term.hyper["batch_norm"]),
+                                           images=self.engine.tensor(np.ascontiguousarray(term.hyper["images"], np.float32)),
+                                           labels=self.engine.int_tensor(term.hyper["labels"]))
+            return cache[key]
         key = id(term.hyper["images"])
         layers = tuple(term.hyper.get("layers") or (term.var[0].shape[1],))
         key = (key, layers)
@@ -246,7 +257,7 @@ class StepPlanMixin(object):
         # one analytic term of weight 1: the per-problem losses of all T+1 steps are kept and
         # reduced over the batch by ONE launch at the end (like the fused path) instead of a
         # tiny reduction kernel per step
-        defer = single and self.terms[0].kind != _abi.PROB_MLP
+        defer = single and self.terms[0].kind not in _SAMPLED
         if defer:
             jd = index_of[self.terms[0].var.name]
             f_all = self._scratch("f_all", (T + 1) * descs[jd].B_local)
@@ -256,13 +267,16 @@ class StepPlanMixin(object):
                 fx[t:t + 1].zero_()
             for k, term in enumerate(self.terms):
                 out = fx[t:t + 1] if single else tmp
-                if term.kind == _abi.PROB_MLP:
+                if term.kind in _SAMPLED:
                     js = [index_of[tv.name] for tv in _term_vars(term)]
                     sc = getattr(self, "_mlp_scales", None) or [None] * nvar
                     xin = [panels[j] if sc[j] is None else
                            torch.mul(panels[j], sc[j], out=self._scratch("xs%d" % j, panels[j].numel()).view(panels[j].shape))
                            for j in js]
-                    if len(js) == 4:
+                    if term.kind == _abi.PROB_MNIST_CONV:
+                        eng.mnist_conv_fg(self._mlp_desc(term), mlp_idx[k][t], xin, out,
+                                          [grads[j] for j in js] if want_grad else None)
+                    elif len(js) == 4:
                         eng.mlp_fg(self._mlp_desc(term), mlp_idx[k][t], *xin, out,
                                    [grads[j] for j in js] if want_grad else None)
                     else:                                   # several hidden layers

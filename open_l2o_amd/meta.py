@@ -38,7 +38,7 @@ from ._graph_adam import AdamMixin
 from ._graph_bptt import BpttMixin
 from ._graph_core import (Fetch, Placeholder, Variable, PackedState, _make_nets, _DEFAULT_CONFIG, _DevGrad, _LazyHost,  # noqa: F401
                           _term_vars, _world, _all_reduce, synced_scale, local_slice, _Slot, set_random_seed, rng, _RngBox)
-from ._graph_steps import StepPlanMixin
+from ._graph_steps import StepPlanMixin, _SAMPLED
 
 MetaLoss = collections.namedtuple("MetaLoss", "loss, update, reset, fx, x")     # DM/meta.py:158
 MetaStep = collections.namedtuple("MetaStep", "step, update, reset, fx, x")     # DM/meta.py:159
@@ -120,7 +120,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
     def _panel_shape(self, var):
         """[B_local, D] view of a variable for the kernels."""
         term = self.term_of[var.decl.name]
-        if term.kind in (_abi.PROB_SIMPLE, _abi.PROB_MLP):
+        if term.kind in (_abi.PROB_SIMPLE, _abi.PROB_MLP, _abi.PROB_MNIST_CONV):
             return 1, int(np.prod(var.shape)) if len(var.shape) else 1
         B = var.shape[0]
         if self.sharded:
@@ -310,7 +310,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
     def deterministic(self):
         """True when an unroll draws nothing at random (no minibatch sampling): then n committed unrolls
         of L steps are exactly one unroll of n * L steps."""
-        return all(t.kind != _abi.PROB_MLP for t in self.terms)
+        return all(t.kind not in _SAMPLED for t in self.terms)
 
     def execute_many(self, n):
         """n consecutive committed unrolls (what util.run_eval_epoch asks for with n sess.run calls,
@@ -438,7 +438,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
 
         descs = []
         for v, sc in zip(self.x, scales):
-            if self.term_of[v.decl.name].kind == _abi.PROB_MLP:
+            if self.term_of[v.decl.name].kind in _SAMPLED:
                 descs.append(None)                          # (its x-scale is applied around l2o_mlp_fg, see _run_steps)
             else:
                 descs.append(self._desc(v, sc))
@@ -446,8 +446,8 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
         for xv, var in zip(xs, self.x):
             B, D = self._panel_shape(var)
             panels.append(xv.view(B, D))
-        # the MLP optimizee is evaluated at x * scale and its gradient is scale * grad (DM/meta_dm_train.py:384)
-        self._mlp_scales = [sc if self.term_of[v.decl.name].kind == _abi.PROB_MLP else None
+        # the MLP / conv optimizees are evaluated at x * scale and their gradient is scale * grad (DM/meta_dm_train.py:384)
+        self._mlp_scales = [sc if self.term_of[v.decl.name].kind in _SAMPLED else None
                             for v, sc in zip(self.x, scales)]
 
         # fx[0..T] of this launch.  Sharded runs all-reduce it ASYNCHRONOUSLY (the next unroll
@@ -963,6 +963,9 @@ class MetaOptimizer(object):
         # DM/meta.py:328-329: without the flag the optimizee gradients are constants of the meta-gradient
         # (tf.stop_gradient); with it dL/dx_t also receives H(x_t) . dL/dg_t (l2o_problem_hvp)
         graph.second_derivatives = bool(second_derivatives)
+        if graph.second_derivatives and any(t.kind == _abi.PROB_MNIST_CONV for t in graph.terms):
+            raise NotImplementedError("second_derivatives=True is implemented for the analytic optimizees "
+                                      "(problems.mnist_conv has no Hessian-vector product)")
         self._graph = graph
         return graph
 

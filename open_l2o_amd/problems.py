@@ -280,14 +280,19 @@ def synthetic_mnist(num_examples=2048, seed=0, label_noise=0.0):
     return {"images": images.reshape(num_examples, 28, 28, 1), "labels": labels}
 
 
-def _load_mnist(mode):
+class MnistDataMissing(FileNotFoundError, NotImplementedError):
+    """No MNIST arrays: neither ``data=`` nor L2O_MNIST_NPZ.  A FileNotFoundError (what problems.mnist raises) and a
+    NotImplementedError (what util.get_config("mnist_conv") raised before the conv net was implemented)."""
+
+
+def _load_mnist(mode, name="mnist"):
     import os
     path = os.environ.get("L2O_MNIST_NPZ")
     if not path:
-        raise FileNotFoundError(
-            "problems.mnist needs the MNIST arrays: pass data={'images': [N,28,28,1], 'labels': [N]} "
+        raise MnistDataMissing(
+            "problems.%s needs the MNIST arrays: pass data={'images': [N,28,28,1], 'labels': [N]} "
             "(problems.synthetic_mnist() gives an offline stand-in) or point L2O_MNIST_NPZ at an .npz with "
-            "'{mode}_images' / '{mode}_labels' (the reference downloads them, DM/problems.py:267-272)")
+            "'{mode}_images' / '{mode}_labels' (the reference downloads them, DM/problems.py:267-272)" % name)
     z = np.load(path)
     return {"images": z["%s_images" % mode], "labels": z["%s_labels" % mode]}
 
@@ -328,6 +333,46 @@ def mnist(layers, activation="sigmoid", batch_size=128, mode="train", data=None,
     return _Build("mnist", build)
 
 
+def mnist_conv(batch_norm=True, batch_size=128, mode="train", data=None, sampler=None):
+    """Mnist classification with a small conv net.  DM/problems.py:291-352.
+
+    conv 3x3x1x16 VALID -> [batch norm] -> ReLU -> max-pool 2 -> conv 5x5x16x32 VALID -> [batch norm] -> ReLU -> max-pool 2
+    -> fc 512x10 -> ReLU (the reference's quirk) -> mean softmax cross-entropy; batch norm is tf.layers.batch_normalization(
+    training=True): batch statistics, biased variance, eps 1e-3; its moving averages are read by nothing and are not
+    declared.  Forward and gradient: l2o_mnist_conv_fg (the step-granular path; no fused unroll).  ``data`` / ``sampler``
+    as for :func:`mnist`; a fresh uniform minibatch per evaluation by default."""
+    if data is None:
+        data = _load_mnist(mode, "mnist_conv")
+    images = np.asarray(data["images"], np.float32)
+    labels = np.asarray(data["labels"]).astype(np.int32)
+    if int(np.prod(images.shape[1:])) != 28 * 28:
+        raise ValueError("problems.mnist_conv takes 28x28x1 images (got %r)" % (images.shape,))
+    if not 2 <= int(batch_size) <= 1024:
+        raise NotImplementedError("problems.mnist_conv is implemented for minibatches of 2 to 1024 (got %d)" % batch_size)
+    images = images.reshape(len(images), 28 * 28)
+    batch_norm = bool(batch_norm)
+
+    def build():
+        w = _nn_initializers["w"]
+        vs = [get_variable("conv_layer1/weights1", [3, 3, 1, 16], initializer=w),
+              get_variable("conv_layer1/biases1", [16], initializer=zeros_initializer())]
+        if batch_norm:
+            vs += [get_variable("batch_normalization/gamma", [16], initializer=ones_initializer()),
+                   get_variable("batch_normalization/beta", [16], initializer=zeros_initializer())]
+        vs += [get_variable("conv_layer2/weights1", [5, 5, 16, 32], initializer=w),
+               get_variable("conv_layer2/biases1", [32], initializer=zeros_initializer())]
+        if batch_norm:
+            vs += [get_variable("batch_normalization_1/gamma", [32], initializer=ones_initializer()),
+                   get_variable("batch_normalization_1/beta", [32], initializer=zeros_initializer())]
+        vs += [get_variable("fc_weights", [512, 10], initializer=w),
+               get_variable("fc_bias", [10], initializer=zeros_initializer())]
+        hyper = {"images": images, "labels": labels, "batch_size": int(batch_size), "batch_norm": batch_norm,
+                 "sampler": sampler}
+        return [Term(_abi.PROB_MNIST_CONV, tuple(vs), {}, hyper, 1.0)]
+
+    return _Build("mnist_conv", build)
+
+
 def _not_on_hot_path(name, where):
     def factory(*args, **kwargs):
         raise NotImplementedError(
@@ -339,7 +384,6 @@ def _not_on_hot_path(name, where):
 
 # neural-network / data-dependent optimizees of the reference (conv nets, TF queues,
 # downloads).  Declared so that `getattr(problems, name)` fails with a clear message.
-mnist_conv = _not_on_hot_path("mnist_conv", "DM/problems.py:291")
 cifar10 = _not_on_hot_path("cifar10", "DM/problems.py:369")
 LeNet = _not_on_hot_path("LeNet", "DM/problems.py:461")
 NAS = _not_on_hot_path("NAS", "DM/problems.py:540")

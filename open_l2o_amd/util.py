@@ -193,7 +193,13 @@ def get_config(problem_name, path=None, mode=None, num_hidden_layer=None, net_na
         problem = problems.mnist(**with_defaults(layers=(20, 20), mode=mode, activation="sigmoid"))
         net_config = {"cw": get_default_net_config(path)}
         net_assignments = None
-    elif problem_name in ("mnist_conv", "cifar_conv", "lenet", "nas",
+    elif problem_name == "mnist_conv":                                   # DM/util.py:164-169
+        if mode is None:
+            mode = "train" if path is None else "test"
+        problem = problems.mnist_conv(**with_defaults(mode=mode, batch_norm=True))
+        net_config = {"cw": get_default_net_config(path)}
+        net_assignments = None
+    elif problem_name in ("cifar_conv", "lenet", "nas",
                           "vgg16", "cifar-multi", "confocal_microscopy_3d"):
         # neural-network / data-dependent optimizees of DM/util.py:144-230: the net config is
         # reproduced, the problem factory raises (out of the accelerated hot path).
