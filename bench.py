@@ -25,19 +25,24 @@ arrays on every run with the same arguments).
                                                        torch.distributed.run, one rank per GPU, 127.0.0.1)
     python bench.py --config 3 --steps 5              (the other BASELINE configs: --config 3 / 4 / 5)
     python bench.py --gpus 8 --scaling strong         (the global batch stays what --batch says)
+    python bench.py --full ...                        (everything beyond the headline figure: see below)
 
 Prints ONE JSON line (rank 0).  value = coordinate-steps per second, whole job:
     sum over ranks of B_local * D * T * steps / wall_time (max over ranks).
 --scaling weak (default): every GPU holds `--batch` problems of a global batch batch*N;
 --scaling strong: the global batch is `--batch`, every GPU holds batch/N of it.  Either way the
 loss mean is over the global batch (DM/problems.py:99) and the only collective is the all-reduce
-of T+1 floats per unroll.  For N > 1 the line also carries, under "also", the config-2 strong-scaling
-run (global batch 128) and the config-4 run (Rastrigin d=100, global batch 1024 sharded over the N
-GPUs) measured in the same job.  For N = 1 (the default run) "also" carries compact lines of the OTHER
-BASELINE configurations measured in the same process right after the primary one: config 3, config 4 on
-one GPU, config 4's shard of 8 (128 of the 1024 problems, 1/B_global = 1/1024, no communication:
---emulate-world 8 on its own) and config 5 -- each with value, kernel_ms, roofline.frac and a bounded
-cpu_baseline (--no-also skips them; budget <= 90 s).  The oracle is imported by the cpu_baseline legs only.
+of T+1 floats per unroll.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.
+--full adds what takes runs of its own: the replays of one instance behind `roofline` and `value_replayed_problem`,
+the device-copy figure, the bounded cpu_baseline (the oracle is imported by those legs only) and the `also` block.
+For N > 1 "also" carries the config-2 strong-scaling run (global batch 128) and the config-4 run (Rastrigin d=100,
+global batch 1024 sharded over the N GPUs) measured in the same job.  For N = 1 "also" carries compact lines of the
+OTHER BASELINE configurations measured in the same process right after the primary one: config 3, config 4 on one GPU,
+config 4's shard of 8 (128 of the 1024 problems, 1/B_global = 1/1024, no communication: --emulate-world 8 on its own)
+and config 5 -- each with value, kernel_ms, roofline.frac and a bounded cpu_baseline (--no-also skips them; budget
+<= 90 s).
 """
 import argparse
 import glob
@@ -425,14 +430,17 @@ def parse_args(argv=None):
                     help="problems per GPU (--scaling weak) / in the whole job (--scaling strong)")
     ap.add_argument("--unroll", type=int, default=100, help="T")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (replays of one instance, PMC files), "
+                         "the device-copy figure, cpu_baseline and the `also` block of other configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline legs")
     ap.add_argument("--untrained", action="store_true", help="random Sonnet-default weights even where a trained "
                                                              "optimizer is committed (the round-1/2 bench)")
     ap.add_argument("--unrolls-per-step", dest="reps", type=int, default=None,
                     help="complete unrolls (each on a fresh problem instance) per bench step; default per config so "
                          "that 20 steps are >= --min-timed-seconds of GPU work, whatever --steps says")
     ap.add_argument("--instances", type=int, default=4, help="ring of pre-sampled problem instances resident in HBM")
-    ap.add_argument("--no-also", action="store_true", help="skip the extra runs of the `also` block (N > 1: strong scaling / "
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the extra runs of the `also` block (N > 1: strong scaling / "
                                                            "config 4; N = 1: configs 3, 4, 4's shard of 8, 5)")
     ap.add_argument("--also-budget", dest="also_budget", type=float, default=75.0, help="seconds after which no further also-run starts")
     ap.add_argument("--also-cpu-seconds", dest="also_cpu_seconds", type=float, default=4.0,
@@ -757,18 +765,20 @@ def run_case(args, eng, world, rank, Bg, B, label):
     eng.check_unroll_status()
     n_unrolls = args.steps * reps
     unroll_all_ms = ev_all_ms / n_unrolls
-    # ---- (outside the timed region) the dominant kernel on its own: the SAME instance replayed, so no preparation
-    # runs between the launches -- the time base of the roofline block
-    one_unroll(None, fresh=False)
-    ev_rep[0].record()
-    for _ in range(max(10, reps)):
+    kern_all = kern_min = None
+    if args.full:
+        # ---- (outside the timed region, --full) the dominant kernel on its own: the SAME instance replayed, so no
+        # preparation runs between the launches -- the time base of the roofline block
         one_unroll(None, fresh=False)
-    ev_rep[1].record()
-    for i in range(n_extra):
-        one_unroll(i, fresh=False)
-    torch.cuda.synchronize()
-    kt = [a.elapsed_time(b) for a, b in ev]
-    kern_all = ev_rep[0].elapsed_time(ev_rep[1]) / max(10, reps)
+        ev_rep[0].record()
+        for _ in range(max(10, reps)):
+            one_unroll(None, fresh=False)
+        ev_rep[1].record()
+        for i in range(n_extra):
+            one_unroll(i, fresh=False)
+        torch.cuda.synchronize()
+        kern_min = float(np.min([a.elapsed_time(b) for a, b in ev]))
+        kern_all = float(ev_rep[0].elapsed_time(ev_rep[1]) / max(10, reps))
     coord_steps = (n_rep if args.problem == "mnist" else B) * D * T     # per GPU per unroll
     Mrows = B if args.problem == "mnist" else (args.rows or D)
     shared = args.problem == "lasso" and args.shared_matrix
@@ -779,7 +789,8 @@ def run_case(args, eng, world, rank, Bg, B, label):
     # no mirror of the selection logic here), and the step-loop cycle count that kernel left in the workspace header
     form, dispatches = eng.last_unroll_form() if graph.last_path in ("fused", "mlp_unroll") else (None, 1)
     dispatches = max(1, dispatches)
-    loop_ticks = eng.last_loop_ticks() if form in ("k_unroll_pair", "k_unroll_lds") or (form or "").startswith("k_mlp_") else None
+    loop_ticks = (eng.last_loop_ticks() if kern_all is not None and (form in ("k_unroll_pair", "k_unroll_lds")
+                                                                    or (form or "").startswith("k_mlp_")) else None)
     streaming = form in ("k_unroll_cu", "k_unroll_cu8")
     notes = {"k_unroll_pair": "every problem on two CUs, one wave per SIMD", "k_unroll_lds": "one problem per CU, two waves per "
              "SIMD, fragments in LDS", "k_unroll_cu8": "streaming, eight waves, fragments in LDS, LSTM state in registers",
@@ -805,8 +816,8 @@ def run_case(args, eng, world, rank, Bg, B, label):
             "step_ms_min": float(np.min(step_ms)), "step_ms_max": float(np.max(step_ms)),
             "n_inst": n_inst, "fx_instance": fx_instance, "fx_ranks": fx_ranks,
             "host_enqueue_ms_per_unroll": t_enqueue / n_unrolls * 1e3,
-            "value_replayed": world * coord_steps / (float(kern_all) * 1e-3),
-            "kern_ms": float(kern_all), "kern_ms_min": float(np.min(kt)), "coord_steps": coord_steps,
+            "value_replayed": None if kern_all is None else world * coord_steps / (kern_all * 1e-3),
+            "kern_ms": kern_all, "kern_ms_min": kern_min, "coord_steps": coord_steps,
             "bpc": bpc, "alg_bytes": bpc * coord_steps,
             "flops": alg_flops_per_coord_step(args.problem, args.net, D, Mrows) * coord_steps,
             "fused": fused, "kernel": kernel, "dispatches": dispatches, "loop_ticks": loop_ticks,
@@ -918,9 +929,10 @@ def main(argv=None):
         write_outputs(args.dump_outputs, case["outputs"])
 
     also = {}
-    if world > 1 and not args.no_also and args.problem == "quadratic" and args.config in (None, 2):
+    if world > 1 and args.full and not args.no_also and args.problem == "quadratic" and args.config in (None, 2):
         for name, extra_argv in (("config2_strong", ["--config", "2", "--scaling", "strong"]), ("config4", ["--config", "4"])):
-            a2 = parse_args(extra_argv + ["--gpus", str(world), "--steps", str(max(5, args.steps // 2)), "--warmup", "2"])
+            a2 = parse_args(extra_argv + ["--gpus", str(world), "--steps", str(max(5, args.steps // 2)), "--warmup", "2",
+                                          "--full"])
             s2 = sizes(a2)
             if s2 is None:
                 continue
@@ -933,7 +945,7 @@ def main(argv=None):
             del c2
 
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # achievable-copy figure of this box: device-to-device copy of 512 MiB, read + write counted
         src = torch.empty(128 << 20, dtype=torch.float32, device=eng.device).normal_()
         dst = torch.empty_like(src)
@@ -950,12 +962,12 @@ def main(argv=None):
 
     build_id = _abi.build_id()
 
-    def _cpu_leg(a, c, Bg_, B_, D, T, full):
+    def _cpu_leg(a, c, Bg_, B_, D, T, primary):
         """The CPU leg of one workload: the oracle's C port (NumPy oracle for the MLP optimizee), timed on this host.
         N > 1 (rank 0 only, while the other ranks wait at the final barrier): a bounded SAMPLE of rank 0's shard -- the
         launcher gives every rank a slice of the host's threads (torch.distributed.run: OMP_NUM_THREADS = 1 unless set),
         so the sample is as many problems as ~8 s of those threads step, at least one per thread."""
-        secs = 20.0 if full else args.also_cpu_seconds
+        secs = 20.0 if primary else args.also_cpu_seconds
         if a.problem == "mnist":
             return cpu_baseline_mnist(c["weights"], B_, T, max_seconds=min(secs, 15.0))
         names = {"quadratic": ("w", "y", None), "lasso": ("w", "y", None), "rastrigin": ("A", "B", "C")}[a.problem]
@@ -975,14 +987,15 @@ def main(argv=None):
         # (the GPU's final loss is comparable with the port's only when both ran the same problems: the whole local batch)
         gpu_fx = float(c["fx_host"][-1]) if world == 1 else None   # (an emulated shard: both sides sum the shard / B_global)
         cpu = cpu_baseline(a.problem, a.net, arrays, c["weights"], x0h, T, max_seconds=secs, B_global=Bg_,
-                           numpy_leg=full and world == 1, gpu_fx_T=gpu_fx)
+                           numpy_leg=primary and world == 1, gpu_fx_T=gpu_fx)
         if note:
             cpu["sample"] += "; " + note
             cpu.pop("fx_T", None)                               # (a sub-sample's partial loss: not comparable with the job's)
         return cpu
 
-    def describe(a, c, Bg_, B_, full):
-        """The measurement of one workload as a dict: the whole contract line (full) or its compact form (also)."""
+    def describe(a, c, Bg_, B_, primary):
+        """The measurement of one workload as a dict: the whole contract line (primary) or its compact form (also).
+        roofline and cpu_baseline only with --full (an also-run always has it)."""
         D, T, Mrows, shared = c["D"], c["T"], c["Mrows"], c["shared"]
         netname, probname = workload_names(a, D, B_, Bg_, T, Mrows, shared)
         is_c2 = (a.problem, a.net, D, B_, Bg_, T) == ("quadratic", "dm", 128, 128, 128 * world, 100)
@@ -1000,23 +1013,24 @@ def main(argv=None):
             if a.replicas > 1 or a.xcd_form:
                 baseline_config = ("BASELINE.json configs[4], %d independent replica(s) per GPU in one launch, one per XCD "
                                    "(k_mlp_xcd)" % a.replicas)
-        counters = None
-        if world == 1 and not shared:
+        counters = roof = None
+        if a.full and world == 1 and not shared:
             counters = counters_for([a.problem, a.net, D, B_, T] + ([Mrows] if a.problem == "lasso" else [])
                                     + (["replicas", a.replicas] if a.problem == "mnist" and (a.replicas > 1 or a.xcd_form) else []),
                                     c["kernel"].split(" ")[0] if c["fused"] or "k_mlp_" in c["kernel"] else "", build_id)
-        roof = roofline_block(c, a, counters)
+        if a.full:
+            roof = roofline_block(c, a, counters)
         cpu = None
-        if not a.no_cpu_baseline and not shared and (not full or world > 1):
+        if a.full and not a.no_cpu_baseline and not shared and (not primary or world > 1):
             try:
-                cpu = _cpu_leg(a, c, Bg_, B_, D, T, full)
+                cpu = _cpu_leg(a, c, Bg_, B_, D, T, primary)
             except Exception as e:                          # noqa: BLE001  (an also-run's / an N > 1 run's CPU leg: recorded, not fatal)
                 cpu = None
                 cpu_error = "%s: %s" % (type(e).__name__, str(e)[:200])
             else:
                 cpu_error = None
-        elif not a.no_cpu_baseline and not shared:
-            cpu, cpu_error = _cpu_leg(a, c, Bg_, B_, D, T, full), None
+        elif a.full and not a.no_cpu_baseline and not shared:
+            cpu, cpu_error = _cpu_leg(a, c, Bg_, B_, D, T, primary), None
         else:
             cpu_error = None
         workload = "%s on %s, batch=%d per GPU (global %d), T=%d%s" % (netname, probname, B_, Bg_, T,
@@ -1028,7 +1042,7 @@ def main(argv=None):
                      "last_over_first": c["step_ms_first_tenth"] / c["step_ms_last_tenth"],
                      "step_ms_min": c["step_ms_min"], "step_ms_max": c["step_ms_max"],
                      "note": "per-step HIP events inside the timed region (this rank): the first and the last tenth of the steps"}
-        if not full:
+        if not primary:
             keep = ("kernel", "kernel_ms_avg", "bound", "frac", "frac_guide_peak", "frac_measured_pipe", "active_frac",
                     "wait_inst_frac", "wait_any_frac", "achieved", "peak", "unit", "traffic", "traffic_over_model",
                     "cycles_per_step", "cycles_per_step_in_kernel", "frac_in_kernel_cycles", "cycles_source", "clock_hz", "pipe_floor_cycles_per_step", "tiles_per_simd", "valu_active_frac",
@@ -1043,17 +1057,11 @@ def main(argv=None):
             if a.emulate_world > 1:
                 out["loss_note"] = "fx are the SHARD's partial sums / B_global (no all-reduce under --emulate-world)"
         else:
-            roof.update(hbm_copy_measured_GBps=copy_gbps, reset_ms=c["t_reset"] * 1e3)   # MetaLoss.reset: the problem re-sampled on the device
-            roof.update(time_base="kernel_ms_avg: HIP events on the launch stream of THIS run around replays of one problem "
-                                  "instance (the unroll kernel + its epilogue); cycles_per_step: counted inside the kernel; "
-                                  "counters (traffic, valu_active_frac): the rocprofv3 --pmc passes named in counters_source, "
-                                  "matched to this library by build id (counters = same_build) or not (stale)",
-                        build_id=build_id)
             scaling_note = None
             if world > 1 or a.scaling == "strong":
                 scaling_note = ("weak: %d problems per GPU, global batch %d (config 2 cannot strong-scale: a T-step unroll "
                                 "is a serial chain of T x ~1.8 us per problem whatever the number of problems per GPU -- "
-                                "see also.config2_strong; config 4's 1024 problems do, see also.config4)" % (B_, Bg_)
+                                "see also.config2_strong of --full; config 4's 1024 problems do, see also.config4)" % (B_, Bg_)
                                 if a.scaling == "weak" else "strong: global batch %d, %d per GPU" % (Bg_, B_))
             out = {
                 "metric": "unroll-steps/sec (batch x params x T), %s on %s" % (netname.split(" ")[0], probname),
@@ -1085,12 +1093,19 @@ def main(argv=None):
                            "scaling_note": scaling_note},
                 "final_loss_fx_T": float(c["fx_host"][-1]), "fx_0": float(c["fx_host"][0]),
                 "final_loss_fx_T_per_rank": c["fx_ranks"],
-                "value_replayed_problem": c["value_replayed"],
-                "value_replayed_note": "the same instance replayed (the round-1/2 figure); not the headline",
                 "parity_pin": PARITY_PIN,
                 "sustained": sustained,
-                "roofline": roof,
             }
+            if roof is not None:                            # (--full)
+                roof.update(hbm_copy_measured_GBps=copy_gbps, reset_ms=c["t_reset"] * 1e3)   # MetaLoss.reset: the problem re-sampled on the device
+                roof.update(time_base="kernel_ms_avg: HIP events on the launch stream of THIS run around replays of one problem "
+                                      "instance (the unroll kernel + its epilogue); cycles_per_step: counted inside the kernel; "
+                                      "counters (traffic, valu_active_frac): the rocprofv3 --pmc passes named in counters_source, "
+                                      "matched to this library by build id (counters = same_build) or not (stale)",
+                            build_id=build_id)
+                out.update(value_replayed_problem=c["value_replayed"],
+                           value_replayed_note="the same instance replayed (the round-1/2 figure); not the headline",
+                           roofline=roof)
         if cpu_error:
             out["cpu_baseline_error"] = cpu_error
         if cpu is not None:
@@ -1104,8 +1119,8 @@ def main(argv=None):
         return out
 
     out = describe(args, case, Bg, B, True) if rank == 0 else None
-    # ---- N = 1, the default run: the other BASELINE configurations, driver-timed in the same process
-    if world == 1 and not args.no_also and args.config in (None, 2) and args.problem == "quadratic" and args.emulate_world <= 1 \
+    # ---- N = 1, --full: the other BASELINE configurations, driver-timed in the same process
+    if world == 1 and args.full and not args.no_also and args.config in (None, 2) and args.problem == "quadratic" and args.emulate_world <= 1 \
             and (args.dims, args.batch, args.unroll, args.net) == (128, 128, 100, "dm"):
         del case
         torch.cuda.empty_cache()
@@ -1133,7 +1148,7 @@ def main(argv=None):
             if time.perf_counter() - t_also > args.also_budget:
                 also[name] = {"skipped": "the also-block's time budget (%g s) was spent" % args.also_budget}
                 continue
-            a2 = parse_args(extra_argv + ["--warmup", "2"] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []))
+            a2 = parse_args(extra_argv + ["--warmup", "2", "--full"] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []))
             a2.also_cpu_seconds = args.also_cpu_seconds
             a2.timed_regions = 2                            # (the faster of two timed regions: see run_case)
             # (an also-run must never take the primary line down with it: a failure is recorded, the line still prints)

@@ -22,7 +22,7 @@ cd "$(dirname "$0")/.."
 # run LABEL <bench.py arguments>: one bench line -> one summary line (options in effect are part of the label)
 run() {
   local lbl=$1; shift
-  python bench.py --warmup 3 --no-cpu-baseline --no-also "$@" 2>>$O/err.txt | LBL="$lbl" ARGS="$*" python -c "
+  python bench.py --full --warmup 3 --no-cpu-baseline --no-also "$@" 2>>$O/err.txt | LBL="$lbl" ARGS="$*" python -c "
 import json,os,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; T=d['config'].get('T',100) if isinstance(d.get('config'),dict) else 100
 print('%-34s %-44s kernel_ms=%.4f  value=%.4g G  fx_T=%r  [%s]' % (os.environ['LBL'], os.environ['ARGS'], r['kernel_ms_avg'], d['value']/1e9, d['final_loss_fx_T'], r['kernel'][:36]))" | tee -a $O/$NAME.txt

@@ -8,7 +8,7 @@
 #   tests[:PYTEST_ARGS]      python -m pytest tests -m gpu  (extra args after the colon, '+' separates words, '%' is a
 #                            space INSIDE a word: tests:-s+-k+teacher_forced%or%c5_trained)
 #   smoke                    __graft_entry__.smoke()
-#   bench:CFG[:ARGS]         python bench.py --config CFG (CFG = 2|3|4|5; 2 = default line incl. cpu_baseline)
+#   bench:CFG[:ARGS]         python bench.py --full --config CFG (CFG = 2|3|4|5; 2 = default line incl. cpu_baseline)
 #   trace:CFG[:ARGS]         rocprofv3 --kernel-trace --stats of the same bench command -> kernel_trace_cCFG.txt
 #   counters:CFG[:ARGS]      the PMC passes of scripts/gpu_counters.sh for that bench command -> counters_cCFG.json
 #   final:CFG[:ARGS]         bench + trace + counters of ONE config back to back in this lease (same build, same box):
@@ -75,7 +75,7 @@ for job in "$@"; do
     smoke)
       (timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1) | tee $O/smoke.log ;;
     bench)
-      extra=$([ "$a1" = 2 ] || echo --no-cpu-baseline)
+      extra="--full $([ "$a1" = 2 ] || echo --no-cpu-baseline)"
       # (a bench job with extra arguments is a different workload: its own file, bench_cN_xK.json)
       n=$((n+1)); out=$O/bench_c$a1.json; [ -n "$a2" ] && out=$O/bench_c${a1}_x$n.json
       timeout 600 python bench.py $(bench_args $a1) $extra $(words "$a2") 2>>$O/bench.err | tee $out | cut -c1-300 ;;
@@ -88,7 +88,7 @@ for job in "$@"; do
     counters)
       bash scripts/gpu_counters.sh $O c$a1 "$(kernel_of $a1)" "$(workload_json $a1)" $(prof_args $a1) $(words "$a2") ;;
     final)
-      extra=$([ "$a1" = 2 ] || echo --no-cpu-baseline)
+      extra="--full $([ "$a1" = 2 ] || echo --no-cpu-baseline)"
       bash scripts/gpu_counters.sh $O c$a1 "$(kernel_of $a1)" "$(workload_json $a1)" $(prof_args $a1) $(words "$a2")
       # the bench line AFTER the counters exist in this lease: its roofline block reads gpurun_out/TAG/counters_cN.json
       L2O_COUNTERS_DIR=$O timeout 600 python bench.py $(bench_args $a1) $extra $(words "$a2") 2>>$O/bench.err | tee $O/bench_c$a1.json | cut -c1-300 ;;
@@ -100,7 +100,7 @@ for job in "$@"; do
       if [ -z "${rest#*=}" ]; then unset "${rest%%=*}"; else export "$rest"; fi ;;
     bench2ranks)
       L2O_BENCH_BACKEND=gloo L2O_BENCH_ONE_DEVICE=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 10 --warmup 2 2>$O/bench2.err | tee $O/bench_2ranks_one_device.json | cut -c1-260 ;;
+        --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 10 --warmup 2 --full 2>$O/bench2.err | tee $O/bench_2ranks_one_device.json | cut -c1-260 ;;
     py)
       (timeout 1200 python $a1 $(words "$a2") 2>&1 | grep -v "amdgpu.ids\|UserWarning") | tee $O/$(basename ${a1%.py}).txt | tail -40 ;;
     sh)

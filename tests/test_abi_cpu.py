@@ -228,7 +228,7 @@ def test_bench_cli_presets_parse():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
                          timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--config", "--no-cpu-baseline", "--scaling"):
+    for flag in ("--gpus", "--steps", "--warmup", "--config", "--no-cpu-baseline", "--scaling", "--full"):
         assert flag in out.stdout
     sys.path.insert(0, ROOT)
     import bench
@@ -236,6 +236,7 @@ def test_bench_cli_presets_parse():
     assert (a.problem, a.dims, a.batch, a.unroll, a.scaling) == ("rastrigin", 100, 1024, 100, "strong")
     a = bench.parse_args([])
     assert (a.gpus, a.problem, a.net, a.dims, a.batch, a.unroll, a.scaling) == (1, "quadratic", "dm", 128, 128, 100, "weak")
+    assert not a.full and bench.parse_args(["--full"]).full          # (a plain run measures the headline alone)
 
 
 def test_bench_cpu_baseline_legs_run():

@@ -59,11 +59,12 @@ def test_four_gloo_ranks_one_device_rehearse_the_config4_line():
     """The command the first driver with a multi-GPU node will run, `bench.py --gpus N --config 4`, end to end with FOUR
     ranks (gloo, all on cuda:0; with this test's own process five processes hold the device -- the suite keeps that at
     six or fewer): the primary line is BASELINE configs[3] (1024 Rastrigin problems, 256 per rank, strong
-    scaling), all four ranks hold the same all-reduced loss, the line carries `roofline` and a rank-0-only, bounded
-    `cpu_baseline`, and the whole command finishes in two minutes."""
+    scaling), all four ranks hold the same all-reduced loss, the line carries (--full) `roofline` and a rank-0-only,
+    bounded `cpu_baseline`, and the whole command finishes in two minutes."""
     import time
     t0 = time.time()
-    line = _bench(["--gpus", "4", "--config", "4", "--steps", "2", "--warmup", "1", "--unrolls-per-step", "2", "--no-also"],
+    line = _bench(["--gpus", "4", "--config", "4", "--steps", "2", "--warmup", "1", "--unrolls-per-step", "2", "--full",
+                   "--no-also"],
                   {"L2O_BENCH_BACKEND": "gloo", "L2O_BENCH_ONE_DEVICE": "1"})
     secs = time.time() - t0
     cfg = line["config"]
@@ -88,11 +89,13 @@ def test_four_gloo_ranks_one_device_rehearse_the_config4_line():
 def test_stdout_is_one_json_line_even_with_a_real_rccl_communicator():
     """The driver reads ONE JSON line from stdout.  RCCL prints a version banner through C stdio when its first
     communicator is created (seen in round 6's first lease: five lines BEHIND the JSON line): bench.py keeps fd 1 for its
-    line alone.  The run itself is config 4's shard of 8 with its all-reduce issued through a world-size-1 RCCL group."""
+    line alone.  The run itself is config 4's shard of 8 with its all-reduce issued through a world-size-1 RCCL group, with
+    --full (the replays behind `roofline` launch through the same group)."""
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "4", "--emulate-world", "8", "--real-collective",
-                        "--steps", "2", "--warmup", "1", "--unrolls-per-step", "2", "--no-cpu-baseline", "--no-also"],
+                        "--steps", "2", "--warmup", "1", "--unrolls-per-step", "2", "--full", "--no-cpu-baseline",
+                        "--no-also"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
