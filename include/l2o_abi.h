@@ -61,6 +61,7 @@ extern "C" {
 #define L2O_PROB_SQUARE_COS 4  /* problems.square_cos :959-994                                             */
 #define L2O_PROB_MLP 5         /* problems.mnist :254-288 (own entry point: l2o_mlp_fg)                    */
 #define L2O_PROB_MNIST_CONV 6  /* problems.mnist_conv :291-352 (own entry point: l2o_mnist_conv_fg)         */
+#define L2O_PROB_CIFAR_CONV 7  /* problems.cifar10 :369-458 (own entry point: l2o_cifar_conv_fg)            */
 
 /* Hyper-parameters of one optimizer network: the `net_options` dict of
  * networks.factory (DM/networks.py:34-44) as used by util.get_config
@@ -297,6 +298,32 @@ size_t l2o_mnist_conv_scratch_floats(const l2o_mnist_conv* conv);
 int l2o_mnist_conv_fg(const l2o_mnist_conv* conv, const int32_t* indices /* device [batch] rows of the minibatch */,
                       const float* const* w, float* loss /* device [1] */, float* const* g,
                       float* scratch /* device [l2o_mnist_conv_scratch_floats] */, void* stream);
+
+/* problems.cifar10 (DM/problems.py:369-458; DM/util.py:170-175 "cifar_conv"): conv 3x3x3x16 stride 2 VALID (15x15) ->
+ * [BN] -> ReLU -> max-pool 2 (7x7) -> conv 5x5x16x32 stride 2 VALID (2x2) -> [BN] -> ReLU -> max-pool 2 (1x1x32) -> fc
+ * 32x10 -> ReLU -> mean sparse softmax cross-entropy; BN as for l2o_mnist_conv_fg.  The step-granular evaluation only:
+ * loss + gradients of one minibatch, six launches (three and the loss sum when g is NULL), fixed-order reductions (two
+ * calls on the same inputs are bit-identical); no fused unroll (l2o_unroll_supported is 0 for L2O_PROB_CIFAR_CONV).
+ * w / g: HOST arrays of device pointers in the reference's variable order
+ *   batch_norm = 1 (10): conv_layer1/weights1 [3,3,3,16] (HWIO), conv_layer1/biases1 [16], batch_normalization/gamma
+ *                        [16], batch_normalization/beta [16], conv_layer2/weights1 [5,5,16,32], conv_layer2/biases1 [32],
+ *                        batch_normalization_1/gamma [32], batch_normalization_1/beta [32], fc_weights [32,10],
+ *                        fc_bias [10]
+ *   batch_norm = 0 (6):  the same without the four BN variables
+ * (g may be NULL: forward only).  batch in [2, 1024], else L2O_ERR_UNSUPPORTED.  Not in L2O_ABI_VERSION 15's list: test
+ * for the symbol. */
+typedef struct l2o_cifar_conv {
+  int32_t batch;         /* minibatch size                            */
+  int32_t n_data;        /* rows of `images`                          */
+  int32_t batch_norm;    /* 1: tf.layers.batch_normalization layers   */
+  int32_t flags;         /* 0                                         */
+  const float* images;   /* device [n_data, 3072] (NHWC 32x32x3)      */
+  const int32_t* labels; /* device [n_data]                           */
+} l2o_cifar_conv;
+size_t l2o_cifar_conv_scratch_floats(const l2o_cifar_conv* conv);
+int l2o_cifar_conv_fg(const l2o_cifar_conv* conv, const int32_t* indices /* device [batch] rows of the minibatch */,
+                      const float* const* w, float* loss /* device [1] */, float* const* g,
+                      float* scratch /* device [l2o_cifar_conv_scratch_floats] */, void* stream);
 
 /* ---- the fused unroll for the neural optimizee (ABI v6): MetaOptimizer.meta_loss's tf.while_loop
  * (DM/meta.py:338-376; RNNProp DM/meta_rnnprop_eval.py time_step) over problems.mnist (DM/problems.py:246-288) as ONE

@@ -102,6 +102,15 @@ class MnistConvDesc:
     labels: torch.Tensor      # [n_data] int32
 
 
+@dataclasses.dataclass
+class CifarConvDesc:
+    """Device-side view of problems.cifar10 (struct l2o_cifar_conv)."""
+    batch: int
+    batch_norm: bool
+    images: torch.Tensor      # [n_data, 3072] fp32 (NHWC 32x32x3)
+    labels: torch.Tensor      # [n_data] int32
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -341,6 +350,25 @@ class HipEngine(object):
         wa = (C.c_void_p * len(ws))(*[_ptr(t).value for t in ws])
         ga = None if grads is None else (C.c_void_p * len(grads))(*[_ptr(t).value for t in grads])
         _abi.check(self.lib.l2o_mnist_conv_fg(C.byref(c), C.c_void_p(indices.data_ptr()), wa, _ptr(loss), ga, _ptr(scr),
+                                              self._stream()))
+
+    def cifar_conv_fg(self, d: CifarConvDesc, indices, ws, loss, grads):
+        """Loss and gradients of the CIFAR-10 conv-net optimizee on ONE minibatch (l2o_cifar_conv_fg).  ws / grads: lists of
+        device tensors in the graph's variable order (10 with batch norm, 6 without; grads may be None: forward only)."""
+        c = _abi.CifarConv()
+        c.batch, c.n_data, c.batch_norm, c.flags = d.batch, int(d.images.shape[0]), 1 if d.batch_norm else 0, 0
+        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
+        n = int(self.lib.l2o_cifar_conv_scratch_floats(C.byref(c)))
+        if not n:
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_cifar_conv_fg: unsupported minibatch %d" % d.batch)
+        if len(ws) != (10 if d.batch_norm else 6) or (grads is not None and len(grads) != len(ws)):
+            raise ValueError("l2o_cifar_conv_fg: %d variables for batch_norm=%r" % (len(ws), d.batch_norm))
+        scr = self.__dict__.get("_cifar_conv_scratch")
+        if scr is None or scr.numel() < n:
+            scr = self._cifar_conv_scratch = self.empty(n)
+        wa = (C.c_void_p * len(ws))(*[_ptr(t).value for t in ws])
+        ga = None if grads is None else (C.c_void_p * len(grads))(*[_ptr(t).value for t in grads])
+        _abi.check(self.lib.l2o_cifar_conv_fg(C.byref(c), C.c_void_p(indices.data_ptr()), wa, _ptr(loss), ga, _ptr(scr),
                                               self._stream()))
 
     def mlp_unroll_supported(self, spec: NetSpec, d: MlpDesc):

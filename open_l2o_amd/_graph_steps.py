@@ -12,8 +12,8 @@ import torch
 from . import _abi, networks
 from ._graph_core import PackedState, _DevGrad, _LazyHost, _term_vars, _world, rng  # noqa: F401
 
-# the optimizees that draw a minibatch per evaluation (problems.mnist, problems.mnist_conv)
-_SAMPLED = (_abi.PROB_MLP, _abi.PROB_MNIST_CONV)
+# the optimizees that draw a minibatch per evaluation (problems.mnist, problems.mnist_conv, problems.cifar10)
+_SAMPLED = (_abi.PROB_MLP, _abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV)
 
 
 class StepPlanMixin(object):
@@ -217,13 +217,21 @@ class StepPlanMixin(object):
                 bufs[k] = new
 
     def _mlp_desc(self, term):
-        """Device copy of the dataset of a problems.mnist / mnist_conv term (uploaded once)."""
+        """Device copy of the dataset of a problems.mnist / mnist_conv / cifar10 term (uploaded once)."""
         cache = self.__dict__.setdefault("_mlp_cache", {})
         if term.kind == _abi.PROB_MNIST_CONV:                  # problems.mnist_conv: l2o_mnist_conv_fg
             key = (id(term.hyper["images"]), "conv", term.hyper["batch_size"], term.hyper["batch_norm"])
             if key not in cache:
                 from ._engine import MnistConvDesc
                 cache[key] = MnistConvDesc(batch=int(term.hyper["batch_size"]), batch_norm=bool(term.hyper["batch_norm"]),
+                                           images=self.engine.tensor(np.ascontiguousarray(term.hyper["images"], np.float32)),
+                                           labels=self.engine.int_tensor(term.hyper["labels"]))
+            return cache[key]
+        if term.kind == _abi.PROB_CIFAR_CONV:                  # problems.cifar10: l2o_cifar_conv_fg
+            key = (id(term.hyper["images"]), "cifar", term.hyper["batch_size"], term.hyper["batch_norm"])
+            if key not in cache:
+                from ._engine import CifarConvDesc
+                cache[key] = CifarConvDesc(batch=int(term.hyper["batch_size"]), batch_norm=bool(term.hyper["batch_norm"]),
                                            images=self.engine.tensor(np.ascontiguousarray(term.hyper["images"], np.float32)),
                                            labels=self.engine.int_tensor(term.hyper["labels"]))
             return cache[key]
@@ -275,6 +283,9 @@ class StepPlanMixin(object):
                            for j in js]
                     if term.kind == _abi.PROB_MNIST_CONV:
                         eng.mnist_conv_fg(self._mlp_desc(term), mlp_idx[k][t], xin, out,
+                                          [grads[j] for j in js] if want_grad else None)
+                    elif term.kind == _abi.PROB_CIFAR_CONV:
+                        eng.cifar_conv_fg(self._mlp_desc(term), mlp_idx[k][t], xin, out,
                                           [grads[j] for j in js] if want_grad else None)
                     elif len(js) == 4:
                         eng.mlp_fg(self._mlp_desc(term), mlp_idx[k][t], *xin, out,

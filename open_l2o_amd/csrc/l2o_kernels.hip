@@ -865,6 +865,7 @@ __global__ __launch_bounds__(CH <= 4 ? 256 : 512) void k_unroll(UnrollArgs a) {
 #include "l2o_mlp_xcd.h"
 #include "l2o_mlp_deep.h"
 #include "l2o_mnist_conv.h"
+#include "l2o_cifar_conv.h"
 
 #include "l2o_generic.h"
 
@@ -2106,6 +2107,73 @@ int l2o_mnist_conv_fg(const l2o_mnist_conv* m, const int32_t* indices, const flo
   }
   const long nthreads = g ? kCvGradThreads : 1;
   hipLaunchKernelGGL(k_cv_grad, dim3((unsigned)((nthreads + kCvThreads - 1) / kCvThreads)), blk, 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return L2O_OK;
+}
+
+// ---- problems.cifar10 (csrc/l2o_cifar_conv.h) -------------------------------------------------------------------------
+static bool cifar_conv_ok(const l2o_cifar_conv* m) {
+  return m && m->batch >= 2 && m->batch <= kCcMaxBatch && m->n_data >= 1 && (m->batch_norm == 0 || m->batch_norm == 1);
+}
+static size_t cifar_conv_per_sample() {
+  return (size_t)2 * kCcZ1 + 2 * kCcA1 + 3 * kCcZ2 + kCcNF + 16 + 1 + 2 * kCcC1 * 2 + 2 * kCcC2 * 2 + kCcPW1;
+}
+size_t l2o_cifar_conv_scratch_floats(const l2o_cifar_conv* m) {
+  if (!cifar_conv_ok(m)) return 0;
+  return (size_t)m->batch * cifar_conv_per_sample() + 2 * (kCcC1 + kCcC2);
+}
+int l2o_cifar_conv_fg(const l2o_cifar_conv* m, const int32_t* indices, const float* const* w, float* loss, float* const* g,
+                      float* scratch, void* stream) {
+  if (!cifar_conv_ok(m))
+    return fail(L2O_ERR_UNSUPPORTED, "l2o_cifar_conv_fg: batch in [2, %d], batch_norm 0 or 1, n_data >= 1", kCcMaxBatch);
+  if (!indices || !w || !loss || !scratch || !m->images || !m->labels) return fail(L2O_ERR_ARG, "l2o_cifar_conv_fg: NULL argument");
+  const int bn = m->batch_norm, nv = bn ? 10 : 6;
+  for (int k = 0; k < nv; ++k)
+    if (!w[k] || (g && !g[k])) return fail(L2O_ERR_ARG, "l2o_cifar_conv_fg: NULL buffer of variable %d", k);
+  CifarConvArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.batch = m->batch; a.bn = bn; a.want_grad = g ? 1 : 0;
+  a.images = m->images; a.labels = m->labels; a.idx = indices;
+  // variable order of the reference's graph: conv_layer1/{weights1, biases1}, [batch_normalization/{gamma, beta}],
+  // conv_layer2/{weights1, biases1}, [batch_normalization_1/{gamma, beta}], fc_weights, fc_bias
+  const int k2 = bn ? 4 : 2, kf = bn ? 8 : 4;
+  a.w1 = w[0]; a.b1 = w[1]; a.w2 = w[k2]; a.b2 = w[k2 + 1]; a.wf = w[kf]; a.bf = w[kf + 1];
+  if (bn) { a.g1 = w[2]; a.be1 = w[3]; a.g2 = w[6]; a.be2 = w[7]; }
+  if (g) {
+    a.gw1 = g[0]; a.gb1 = g[1]; a.gw2 = g[k2]; a.gb2 = g[k2 + 1]; a.gwf = g[kf]; a.gbf = g[kf + 1];
+    if (bn) { a.gg1 = g[2]; a.gbe1 = g[3]; a.gg2 = g[6]; a.gbe2 = g[7]; }
+  }
+  const size_t B = (size_t)a.batch;
+  float* p = scratch;
+  a.z1 = p; p += B * kCcZ1;
+  a.d1 = p; p += B * kCcZ1;
+  a.p1 = p; p += B * kCcA1;
+  a.am1 = reinterpret_cast<int*>(p); p += B * kCcA1;
+  a.z2 = p; p += B * kCcZ2;
+  a.d2 = p; p += B * kCcZ2;
+  a.dz2 = p; p += B * kCcZ2;
+  a.f = p; p += B * kCcNF;
+  a.dlog = p; p += B * 16;
+  a.loss_s = p; p += B;
+  a.st1 = p; p += B * kCcC1 * 2;
+  a.bw1 = p; p += B * kCcC1 * 2;
+  a.st2 = p; p += B * kCcC2 * 2;
+  a.bw2 = p; p += B * kCcC2 * 2;
+  a.pw1 = p; p += B * kCcPW1;
+  a.stat = p;
+  a.loss = loss;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(a.batch), blk(kCcThreads);
+  hipLaunchKernelGGL(k_cc_conv1, grid, blk, 0, s, a);
+  hipLaunchKernelGGL(k_cc_conv2, grid, blk, 0, s, a);
+  hipLaunchKernelGGL(k_cc_head, dim3((a.batch + kCcHeadSamples - 1) / kCcHeadSamples), blk, 0, s, a);
+  if (g) {
+    hipLaunchKernelGGL(k_cc_mid, grid, blk, 0, s, a);
+    hipLaunchKernelGGL(k_cc_first, grid, blk, 0, s, a);
+  }
+  const long nthreads = g ? kCcGradThreads : 1;
+  const unsigned nblocks = (unsigned)((nthreads + kCcThreads - 1) / kCcThreads) + (g ? kCcW2Blocks : 0);
+  hipLaunchKernelGGL(k_cc_grad, dim3(nblocks), blk, 0, s, a);
   HIP_TRY(hipGetLastError());
   return L2O_OK;
 }

@@ -373,6 +373,104 @@ def mnist_conv(batch_norm=True, batch_size=128, mode="train", data=None, sampler
     return _Build("mnist_conv", build)
 
 
+def synthetic_cifar10(num_examples=2048, seed=0, label_noise=0.0):
+    """A deterministic stand-in for the CIFAR-10 arrays (no dataset ships with this repo and there is no network): images
+    [N,32,32,3] (NHWC) in [0,1], labels [N] in 0..9.  Every class has a prototype of 8x8 colour blocks of 4x4 pixels; an
+    image is 0.6 x its class's prototype plus 0.4 x uniform noise, so the classes separate under the net's stride-2 convs
+    and pools.  ``label_noise``: that fraction of the labels is re-drawn uniformly AFTER the images were formed (as in
+    :func:`synthetic_mnist`)."""
+    rng = np.random.default_rng(seed)
+    labels = rng.integers(0, 10, size=num_examples).astype(np.int64)
+    protos = rng.random((10, 8, 8, 3)).repeat(4, axis=1).repeat(4, axis=2)
+    images = (0.6 * protos[labels] + 0.4 * rng.random((num_examples, 32, 32, 3))).astype(np.float32)
+    if label_noise > 0.0:
+        flip = rng.random(num_examples) < label_noise
+        labels = np.where(flip, rng.integers(0, 10, size=num_examples), labels).astype(np.int64)
+    return {"images": images, "labels": labels}
+
+
+class Cifar10DataMissing(FileNotFoundError, NotImplementedError):
+    """No CIFAR-10 arrays: neither ``data=`` nor the binary files.  A FileNotFoundError (the files are missing) and a
+    NotImplementedError (what util.get_config("cifar_conv") raised before the conv net was implemented)."""
+
+
+_CIFAR10_FOLDER = "cifar-10-batches-bin"          # DM/problems.py:43
+
+
+def _load_cifar10(path, mode):
+    """The reference's binary files (DM/problems.py:378-401) read with NumPy: records of one label byte and 3072 image
+    bytes in CHW order; the images come back HWC and divided by 255.  L2O_CIFAR10_DIR, when set, replaces ``path``.  Never
+    downloads."""
+    import os
+    if mode == "train":
+        names = ["data_batch_%d.bin" % i for i in range(1, 6)]
+    elif mode == "test":
+        names = ["test_batch.bin"]
+    else:
+        raise ValueError("Mode {} not recognised".format(mode))
+    root = os.environ.get("L2O_CIFAR10_DIR") or path
+    files = [os.path.join(root, _CIFAR10_FOLDER, n) for n in names]
+    missing = [f for f in files if not os.path.isfile(f)]
+    if missing:
+        raise Cifar10DataMissing(
+            "problems.cifar10 needs the CIFAR-10 binary files: %s is missing (looked under %r; set L2O_CIFAR10_DIR to the "
+            "directory that holds %s/, or pass data={'images': [N,32,32,3], 'labels': [N]} -- problems.synthetic_cifar10() "
+            "gives an offline stand-in; nothing is downloaded)" % (missing[0], root, _CIFAR10_FOLDER))
+    raw = np.concatenate([np.fromfile(f, np.uint8) for f in files])
+    if raw.size % 3073:
+        raise ValueError("CIFAR-10 binary files hold records of 3073 bytes (got %d bytes)" % raw.size)
+    rec = raw.reshape(-1, 3073)
+    images = rec[:, 1:].reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1).astype(np.float32) / 255.0
+    return {"images": images, "labels": rec[:, 0].astype(np.int64)}
+
+
+def cifar10(path, batch_norm=True, batch_size=128, num_threads=4, min_queue_examples=1000, mode="train", data=None,
+            sampler=None):
+    """Cifar10 classification with a convolutional network.  DM/problems.py:369-458.
+
+    conv 3x3x3x16 stride 2 VALID -> [batch norm] -> ReLU -> max-pool 2 -> conv 5x5x16x32 stride 2 VALID -> [batch norm] ->
+    ReLU -> max-pool 2 -> fc 32x10 -> ReLU (the reference's quirk) -> mean softmax cross-entropy; batch norm as in
+    :func:`mnist_conv`.  Forward and gradient: l2o_cifar_conv_fg (the step-granular path; no fused unroll).
+
+    The data come from ``data`` ({'images': [N,32,32,3] in [0,1], 'labels': [N]}) or else from the reference's binary files
+    under ``<path>/cifar-10-batches-bin/`` (``L2O_CIFAR10_DIR``, when set, replaces ``path``); nothing is downloaded.  Every
+    evaluation draws a fresh uniform minibatch of ``batch_size`` rows (or ``sampler(n_evals, batch, n_data)``'s); the
+    reference dequeues from a tf.RandomShuffleQueue fed by ``num_threads`` readers with ``min_queue_examples`` kept back,
+    which draws differently.  ``num_threads`` and ``min_queue_examples`` are accepted for the reference's signature and
+    have no effect."""
+    del num_threads, min_queue_examples
+    if data is None:
+        data = _load_cifar10(path, mode)
+    images = np.asarray(data["images"], np.float32)
+    labels = np.asarray(data["labels"]).astype(np.int32)
+    if int(np.prod(images.shape[1:])) != 32 * 32 * 3:
+        raise ValueError("problems.cifar10 takes 32x32x3 images (got %r)" % (images.shape,))
+    if not 2 <= int(batch_size) <= 1024:
+        raise NotImplementedError("problems.cifar10 is implemented for minibatches of 2 to 1024 (got %d)" % batch_size)
+    images = np.ascontiguousarray(images.reshape(len(images), 32 * 32 * 3))
+    batch_norm = bool(batch_norm)
+
+    def build():
+        w = _nn_initializers["w"]
+        vs = [get_variable("conv_layer1/weights1", [3, 3, 3, 16], initializer=w),
+              get_variable("conv_layer1/biases1", [16], initializer=zeros_initializer())]
+        if batch_norm:
+            vs += [get_variable("batch_normalization/gamma", [16], initializer=ones_initializer()),
+                   get_variable("batch_normalization/beta", [16], initializer=zeros_initializer())]
+        vs += [get_variable("conv_layer2/weights1", [5, 5, 16, 32], initializer=w),
+               get_variable("conv_layer2/biases1", [32], initializer=zeros_initializer())]
+        if batch_norm:
+            vs += [get_variable("batch_normalization_1/gamma", [32], initializer=ones_initializer()),
+                   get_variable("batch_normalization_1/beta", [32], initializer=zeros_initializer())]
+        vs += [get_variable("fc_weights", [32, 10], initializer=w),
+               get_variable("fc_bias", [10], initializer=zeros_initializer())]
+        hyper = {"images": images, "labels": labels, "batch_size": int(batch_size), "batch_norm": batch_norm,
+                 "sampler": sampler}
+        return [Term(_abi.PROB_CIFAR_CONV, tuple(vs), {}, hyper, 1.0)]
+
+    return _Build("cifar10", build)
+
+
 def _not_on_hot_path(name, where):
     def factory(*args, **kwargs):
         raise NotImplementedError(
@@ -384,7 +482,9 @@ def _not_on_hot_path(name, where):
 
 # neural-network / data-dependent optimizees of the reference (conv nets, TF queues,
 # downloads).  Declared so that `getattr(problems, name)` fails with a clear message.
-cifar10 = _not_on_hot_path("cifar10", "DM/problems.py:369")
+# util.get_config("cifar-multi") (DM/util.py:212-230) calls cifar10 with conv_channels / linear_layers, which the
+# reference's own cifar10 does not take
+cifar_multi = _not_on_hot_path("cifar10(conv_channels=..., linear_layers=...)", "DM/util.py:212")
 LeNet = _not_on_hot_path("LeNet", "DM/problems.py:461")
 NAS = _not_on_hot_path("NAS", "DM/problems.py:540")
 vgg16_cifar10 = _not_on_hot_path("vgg16_cifar10", "DM/problems.py:637")

@@ -63,8 +63,10 @@ def parse_flags(rnnprop):
                    help="stop after the first evaluation past this wall time (bounded GPU leases)")
     p.add_argument("--synthetic_mnist", type=int, default=0,
                    help="problems.mnist on N synthetic MNIST-shaped examples (no dataset ships offline)")
+    p.add_argument("--synthetic_cifar10", type=int, default=0,
+                   help="problems.cifar10 on N synthetic CIFAR-10-shaped examples (no dataset ships offline)")
     p.add_argument("--synthetic_label_noise", type=float, default=0.0,
-                   help="fraction of the synthetic labels re-drawn uniformly (problems.synthetic_mnist)")
+                   help="fraction of the synthetic labels re-drawn uniformly (problems.synthetic_mnist / synthetic_cifar10)")
     p.add_argument("--synthetic_seed", type=int, default=0)
     p.add_argument("--replicas", type=int, default=1,
                    help="--problem mnist: meta-train on N optimizee instances per step (the mean of their meta-gradients); "
@@ -94,6 +96,10 @@ class Trainer(object):
             from open_l2o_amd import problems
             opts["data"] = problems.synthetic_mnist(flags.synthetic_mnist, seed=getattr(flags, "synthetic_seed", 0),
                                                     label_noise=getattr(flags, "synthetic_label_noise", 0.0))
+        if getattr(flags, "synthetic_cifar10", 0):
+            from open_l2o_amd import problems
+            opts["data"] = problems.synthetic_cifar10(flags.synthetic_cifar10, seed=getattr(flags, "synthetic_seed", 0),
+                                                      label_noise=getattr(flags, "synthetic_label_noise", 0.0))
         problem, net_config, assignments = util.get_config(flags.problem, net_name="RNNprop" if rnnprop else None,
                                                            problem_options=opts)
         kw = dict(learning_rate=flags.learning_rate, net_assignments=assignments,

@@ -31,6 +31,8 @@ def main():
     flags.add_argument("--num_dims", type=int, default=None)
     flags.add_argument("--synthetic_mnist", type=int, default=0,
                        help="problems.mnist on N synthetic MNIST-shaped examples (no dataset ships offline)")
+    flags.add_argument("--synthetic_cifar10", type=int, default=0,
+                       help="problems.cifar10 on N synthetic CIFAR-10-shaped examples (no dataset ships offline)")
     flags.add_argument("--replicas", type=int, default=1,
                        help="(ours) evaluate this many independent instances of the optimizee TOGETHER (own initial weights, "
                             "own minibatches; problems.mnist with one hidden layer of 20 at --batch_size 64 or 128 (the "
@@ -46,6 +48,9 @@ def main():
     if FLAGS.synthetic_mnist:
         from open_l2o_amd import problems
         opts["data"] = problems.synthetic_mnist(FLAGS.synthetic_mnist)
+    if FLAGS.synthetic_cifar10:
+        from open_l2o_amd import problems
+        opts["data"] = problems.synthetic_cifar10(FLAGS.synthetic_cifar10)
     problem, net_config, net_assignments = util.get_config(FLAGS.problem, FLAGS.path, net_name="RNNprop",
                                                            problem_options=opts)
     if FLAGS.optimizer != "L2L":
