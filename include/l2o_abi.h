@@ -62,6 +62,7 @@ extern "C" {
 #define L2O_PROB_MLP 5         /* problems.mnist :254-288 (own entry point: l2o_mlp_fg)                    */
 #define L2O_PROB_MNIST_CONV 6  /* problems.mnist_conv :291-352 (own entry point: l2o_mnist_conv_fg)         */
 #define L2O_PROB_CIFAR_CONV 7  /* problems.cifar10 :369-458 (own entry point: l2o_cifar_conv_fg)            */
+#define L2O_PROB_LENET 8       /* problems.LeNet :461-537 (own entry point: l2o_lenet_fg)                   */
 
 /* Hyper-parameters of one optimizer network: the `net_options` dict of
  * networks.factory (DM/networks.py:34-44) as used by util.get_config
@@ -324,6 +325,35 @@ size_t l2o_cifar_conv_scratch_floats(const l2o_cifar_conv* conv);
 int l2o_cifar_conv_fg(const l2o_cifar_conv* conv, const int32_t* indices /* device [batch] rows of the minibatch */,
                       const float* const* w, float* loss /* device [1] */, float* const* g,
                       float* scratch /* device [l2o_cifar_conv_scratch_floats] */, void* stream);
+
+/* problems.LeNet (DM/problems.py:461-537; DM/util.py:176-184 "lenet"): conv 5x5x3x6 VALID (28x28) -> [BN] -> sigmoid ->
+ * max-pool 2 (14x14) -> conv 5x5x6x16 VALID (10x10) -> [BN] -> sigmoid -> max-pool 2 (5x5x16) -> flatten (NHWC, 400) ->
+ * linear 400x120 -> [BN] -> sigmoid -> linear 120x84 -> [BN] -> sigmoid -> linear 84x10 -> mean sparse softmax
+ * cross-entropy.  BN is snt.BatchNorm in training mode: batch statistics (over N, H, W after a conv; over N after a linear
+ * layer), biased variance, eps 1e-3, an offset beta and no scale.  The step-granular evaluation only: loss + gradients of
+ * one minibatch, twelve launches (seven when g is NULL), fixed-order reductions (two calls on the same inputs are
+ * bit-identical); no fused unroll (l2o_unroll_supported is 0 for L2O_PROB_LENET).
+ * w / g: HOST arrays of device pointers in the reference's variable order
+ *   batch_norm = 1 (14): conv_net_2d/conv_2d_0/w [5,5,3,6] (HWIO), conv_net_2d/conv_2d_0/b [6],
+ *                        conv_net_2d/batch_norm_0/beta [6], conv_net_2d/conv_2d_1/w [5,5,6,16], conv_net_2d/conv_2d_1/b
+ *                        [16], conv_net_2d/batch_norm_1/beta [16], mlp/linear_0/w [400,120], mlp/linear_0/b [120],
+ *                        mlp/batch_norm/beta [120], mlp/linear_1/w [120,84], mlp/linear_1/b [84], mlp/batch_norm_1/beta
+ *                        [84], mlp/linear_2/w [84,10], mlp/linear_2/b [10]
+ *   batch_norm = 0 (10): the same without the four beta
+ * (g may be NULL: forward only).  batch in [2, 1024], else L2O_ERR_UNSUPPORTED.  scratch 16-byte aligned.  Not in
+ * L2O_ABI_VERSION 15's list: test for the symbol. */
+typedef struct l2o_lenet {
+  int32_t batch;         /* minibatch size                            */
+  int32_t n_data;        /* rows of `images`                          */
+  int32_t batch_norm;    /* 1: snt.BatchNorm after every layer but the last */
+  int32_t flags;         /* 0                                         */
+  const float* images;   /* device [n_data, 3072] (NHWC 32x32x3)      */
+  const int32_t* labels; /* device [n_data]                           */
+} l2o_lenet;
+size_t l2o_lenet_scratch_floats(const l2o_lenet* net);
+int l2o_lenet_fg(const l2o_lenet* net, const int32_t* indices /* device [batch] rows of the minibatch */,
+                 const float* const* w, float* loss /* device [1] */, float* const* g,
+                 float* scratch /* device [l2o_lenet_scratch_floats] */, void* stream);
 
 /* ---- the fused unroll for the neural optimizee (ABI v6): MetaOptimizer.meta_loss's tf.while_loop
  * (DM/meta.py:338-376; RNNProp DM/meta_rnnprop_eval.py time_step) over problems.mnist (DM/problems.py:246-288) as ONE

@@ -111,6 +111,15 @@ class CifarConvDesc:
     labels: torch.Tensor      # [n_data] int32
 
 
+@dataclasses.dataclass
+class LenetDesc:
+    """Device-side view of problems.LeNet (struct l2o_lenet)."""
+    batch: int
+    batch_norm: bool
+    images: torch.Tensor      # [n_data, 3072] fp32 (NHWC 32x32x3)
+    labels: torch.Tensor      # [n_data] int32
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -370,6 +379,25 @@ class HipEngine(object):
         ga = None if grads is None else (C.c_void_p * len(grads))(*[_ptr(t).value for t in grads])
         _abi.check(self.lib.l2o_cifar_conv_fg(C.byref(c), C.c_void_p(indices.data_ptr()), wa, _ptr(loss), ga, _ptr(scr),
                                               self._stream()))
+
+    def lenet_fg(self, d: LenetDesc, indices, ws, loss, grads):
+        """Loss and gradients of the LeNet optimizee on ONE minibatch (l2o_lenet_fg).  ws / grads: lists of device tensors
+        in the graph's variable order (14 with batch norm, 10 without; grads may be None: forward only)."""
+        c = _abi.Lenet()
+        c.batch, c.n_data, c.batch_norm, c.flags = d.batch, int(d.images.shape[0]), 1 if d.batch_norm else 0, 0
+        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
+        n = int(self.lib.l2o_lenet_scratch_floats(C.byref(c)))
+        if not n:
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_lenet_fg: unsupported minibatch %d" % d.batch)
+        if len(ws) != (14 if d.batch_norm else 10) or (grads is not None and len(grads) != len(ws)):
+            raise ValueError("l2o_lenet_fg: %d variables for batch_norm=%r" % (len(ws), d.batch_norm))
+        scr = self.__dict__.get("_lenet_scratch")
+        if scr is None or scr.numel() < n:
+            scr = self._lenet_scratch = self.empty(n)
+        wa = (C.c_void_p * len(ws))(*[_ptr(t).value for t in ws])
+        ga = None if grads is None else (C.c_void_p * len(grads))(*[_ptr(t).value for t in grads])
+        _abi.check(self.lib.l2o_lenet_fg(C.byref(c), C.c_void_p(indices.data_ptr()), wa, _ptr(loss), ga, _ptr(scr),
+                                         self._stream()))
 
     def mlp_unroll_supported(self, spec: NetSpec, d: MlpDesc):
         """A fused persistent unroll exists for this (net, MLP optimizee) pair on this device (l2o_mlp_unroll)."""

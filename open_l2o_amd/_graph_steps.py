@@ -12,8 +12,9 @@ import torch
 from . import _abi, networks
 from ._graph_core import PackedState, _DevGrad, _LazyHost, _term_vars, _world, rng  # noqa: F401
 
-# the optimizees that draw a minibatch per evaluation (problems.mnist, problems.mnist_conv, problems.cifar10)
-_SAMPLED = (_abi.PROB_MLP, _abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV)
+# the optimizees that draw a minibatch per evaluation (problems.mnist, problems.mnist_conv, problems.cifar10,
+# problems.LeNet)
+_SAMPLED = (_abi.PROB_MLP, _abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV, _abi.PROB_LENET)
 
 
 class StepPlanMixin(object):
@@ -217,7 +218,7 @@ class StepPlanMixin(object):
                 bufs[k] = new
 
     def _mlp_desc(self, term):
-        """Device copy of the dataset of a problems.mnist / mnist_conv / cifar10 term (uploaded once)."""
+        """Device copy of the dataset of a problems.mnist / mnist_conv / cifar10 / LeNet term (uploaded once)."""
         cache = self.__dict__.setdefault("_mlp_cache", {})
         if term.kind == _abi.PROB_MNIST_CONV:                  # problems.mnist_conv: l2o_mnist_conv_fg
             key = (id(term.hyper["images"]), "conv", term.hyper["batch_size"], term.hyper["batch_norm"])
@@ -234,6 +235,14 @@ class StepPlanMixin(object):
                 cache[key] = CifarConvDesc(batch=int(term.hyper["batch_size"]), batch_norm=bool(term.hyper["batch_norm"]),
                                            images=self.engine.tensor(np.ascontiguousarray(term.hyper["images"], np.float32)),
                                            labels=self.engine.int_tensor(term.hyper["labels"]))
+            return cache[key]
+        if term.kind == _abi.PROB_LENET:                       # problems.LeNet: l2o_lenet_fg
+            key = (id(term.hyper["images"]), "lenet", term.hyper["batch_size"], term.hyper["batch_norm"])
+            if key not in cache:
+                from ._engine import LenetDesc
+                cache[key] = LenetDesc(batch=int(term.hyper["batch_size"]), batch_norm=bool(term.hyper["batch_norm"]),
+                                       images=self.engine.tensor(np.ascontiguousarray(term.hyper["images"], np.float32)),
+                                       labels=self.engine.int_tensor(term.hyper["labels"]))
             return cache[key]
         key = id(term.hyper["images"])
         layers = tuple(term.hyper.get("layers") or (term.var[0].shape[1],))
@@ -287,6 +296,9 @@ class StepPlanMixin(object):
                     elif term.kind == _abi.PROB_CIFAR_CONV:
                         eng.cifar_conv_fg(self._mlp_desc(term), mlp_idx[k][t], xin, out,
                                           [grads[j] for j in js] if want_grad else None)
+                    elif term.kind == _abi.PROB_LENET:
+                        eng.lenet_fg(self._mlp_desc(term), mlp_idx[k][t], xin, out,
+                                     [grads[j] for j in js] if want_grad else None)
                     elif len(js) == 4:
                         eng.mlp_fg(self._mlp_desc(term), mlp_idx[k][t], *xin, out,
                                    [grads[j] for j in js] if want_grad else None)

@@ -866,6 +866,7 @@ __global__ __launch_bounds__(CH <= 4 ? 256 : 512) void k_unroll(UnrollArgs a) {
 #include "l2o_mlp_deep.h"
 #include "l2o_mnist_conv.h"
 #include "l2o_cifar_conv.h"
+#include "l2o_lenet.h"
 
 #include "l2o_generic.h"
 
@@ -2174,6 +2175,90 @@ int l2o_cifar_conv_fg(const l2o_cifar_conv* m, const int32_t* indices, const flo
   const long nthreads = g ? kCcGradThreads : 1;
   const unsigned nblocks = (unsigned)((nthreads + kCcThreads - 1) / kCcThreads) + (g ? kCcW2Blocks : 0);
   hipLaunchKernelGGL(k_cc_grad, dim3(nblocks), blk, 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return L2O_OK;
+}
+
+// ---- problems.LeNet (csrc/l2o_lenet.h) --------------------------------------------------------------------------------
+static bool lenet_ok(const l2o_lenet* m) {
+  return m && m->batch >= 2 && m->batch <= kLnMaxBatch && m->n_data >= 1 && (m->batch_norm == 0 || m->batch_norm == 1);
+}
+// every per-sample region is a multiple of 4 floats (the kernels read some of them as float4); loss_s and stat come last
+static size_t lenet_per_sample() {
+  return (size_t)2 * kLnZ1 + 2 * kLnA1 + 2 * kLnZ2 + 2 * kLnF + 3 * kLnN1 + 3 * kLnN2 + 16 + 2 * kLnC1 * 2 + 2 * kLnC2 * 2 +
+         kLnPW1 + kLnPW2 + 1;
+}
+size_t l2o_lenet_scratch_floats(const l2o_lenet* m) {
+  if (!lenet_ok(m)) return 0;
+  return (size_t)m->batch * lenet_per_sample() + kLnStat;
+}
+int l2o_lenet_fg(const l2o_lenet* m, const int32_t* indices, const float* const* w, float* loss, float* const* g,
+                 float* scratch, void* stream) {
+  if (!lenet_ok(m))
+    return fail(L2O_ERR_UNSUPPORTED, "l2o_lenet_fg: batch in [2, %d], batch_norm 0 or 1, n_data >= 1", kLnMaxBatch);
+  if (!indices || !w || !loss || !scratch || !m->images || !m->labels) return fail(L2O_ERR_ARG, "l2o_lenet_fg: NULL argument");
+  if ((uintptr_t)scratch & 15) return fail(L2O_ERR_ARG, "l2o_lenet_fg: scratch must be 16-byte aligned");
+  const int bn = m->batch_norm, nv = bn ? 14 : 10;
+  for (int k = 0; k < nv; ++k)
+    if (!w[k] || (g && !g[k])) return fail(L2O_ERR_ARG, "l2o_lenet_fg: NULL buffer of variable %d", k);
+  LenetArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.batch = m->batch; a.bn = bn; a.want_grad = g ? 1 : 0;
+  a.images = m->images; a.labels = m->labels; a.idx = indices;
+  // variable order of the reference's graph: conv_2d_0/{w, b}, [batch_norm_0/beta], conv_2d_1/{w, b}, [batch_norm_1/beta],
+  // linear_0/{w, b}, [mlp/batch_norm/beta], linear_1/{w, b}, [mlp/batch_norm_1/beta], linear_2/{w, b}
+  const int st = bn ? 3 : 2, k2 = st, k3 = 2 * st, k4 = 3 * st, k5 = 4 * st;
+  a.w1 = w[0]; a.b1 = w[1]; a.w2 = w[k2]; a.b2 = w[k2 + 1]; a.wl0 = w[k3]; a.bl0 = w[k3 + 1]; a.wl1 = w[k4]; a.bl1 = w[k4 + 1];
+  a.wl2 = w[k5]; a.bl2 = w[k5 + 1];
+  if (bn) { a.be1 = w[2]; a.be2 = w[5]; a.bel0 = w[8]; a.bel1 = w[11]; }
+  if (g) {
+    a.gw1 = g[0]; a.gb1 = g[1]; a.gw2 = g[k2]; a.gb2 = g[k2 + 1]; a.gwl0 = g[k3]; a.gbl0 = g[k3 + 1]; a.gwl1 = g[k4];
+    a.gbl1 = g[k4 + 1]; a.gwl2 = g[k5]; a.gbl2 = g[k5 + 1];
+    if (bn) { a.gbe1 = g[2]; a.gbe2 = g[5]; a.gbel0 = g[8]; a.gbel1 = g[11]; }
+  }
+  const size_t B = (size_t)a.batch;
+  float* p = scratch;
+  a.z1 = p; p += B * kLnZ1;
+  a.d1 = p; p += B * kLnZ1;
+  a.p1 = p; p += B * kLnA1;
+  a.am1 = reinterpret_cast<int*>(p); p += B * kLnA1;
+  a.z2 = p; p += B * kLnZ2;
+  a.d2 = p; p += B * kLnZ2;
+  a.f = p; p += B * kLnF;
+  a.am2 = reinterpret_cast<int*>(p); p += B * kLnF;
+  a.h1 = p; p += B * kLnN1;
+  a.a1 = p; p += B * kLnN1;
+  a.dh1 = p; p += B * kLnN1;
+  a.h2 = p; p += B * kLnN2;
+  a.a2 = p; p += B * kLnN2;
+  a.dh2 = p; p += B * kLnN2;
+  a.dlog = p; p += B * 16;
+  a.st1 = p; p += B * kLnC1 * 2;
+  a.bw1 = p; p += B * kLnC1 * 2;
+  a.st2 = p; p += B * kLnC2 * 2;
+  a.bw2 = p; p += B * kLnC2 * 2;
+  a.pw1 = p; p += B * kLnPW1;
+  a.pw2 = p; p += B * kLnPW2;
+  a.loss_s = p; p += B;
+  a.stat = p;
+  a.loss = loss;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(a.batch), blk(kLnThreads);
+  hipLaunchKernelGGL(k_ln_conv1, grid, blk, 0, s, a);
+  hipLaunchKernelGGL(k_ln_conv2, grid, blk, 0, s, a);
+  hipLaunchKernelGGL(k_ln_pool2, grid, blk, 0, s, a);
+  hipLaunchKernelGGL(k_ln_fc<0>, dim3(kLnN1 / kLnU), blk, 0, s, a);
+  hipLaunchKernelGGL(k_ln_fc<1>, dim3(kLnN2 / kLnU), blk, 0, s, a);
+  hipLaunchKernelGGL(k_ln_out, dim3((a.batch + kLnOutSamples - 1) / kLnOutSamples), blk, 0, s, a);
+  if (g) {
+    hipLaunchKernelGGL(k_ln_fcb<1>, dim3(kLnN2 / kLnU), blk, 0, s, a);
+    hipLaunchKernelGGL(k_ln_fcb<0>, dim3(kLnN1 / kLnU), blk, 0, s, a);
+    hipLaunchKernelGGL(k_ln_mid, grid, blk, 0, s, a);
+    hipLaunchKernelGGL(k_ln_mid2, grid, blk, 0, s, a);
+    hipLaunchKernelGGL(k_ln_first, grid, blk, 0, s, a);
+  }
+  const long nthreads = g ? kLnGradThreads : 1;
+  hipLaunchKernelGGL(k_ln_grad, dim3((unsigned)((nthreads + kLnThreads - 1) / kLnThreads)), blk, 0, s, a);
   HIP_TRY(hipGetLastError());
   return L2O_OK;
 }

@@ -471,6 +471,61 @@ def cifar10(path, batch_norm=True, batch_size=128, num_threads=4, min_queue_exam
     return _Build("cifar10", build)
 
 
+def LeNet(path, conv_channels=None, linear_layers=None, batch_norm=True, batch_size=128, num_threads=4,
+          min_queue_examples=1000, mode="train", data=None, sampler=None):
+    """LeNet-5 on CIFAR-10 with sigmoids, max-pooling and Sonnet batch norm.  DM/problems.py:461-537, as
+    util.get_config("lenet") (DM/util.py:176-184) calls it: ``conv_channels=(6, 16)``, ``linear_layers=(120, 84)``.
+
+    conv 5x5x3x6 VALID -> [batch norm] -> sigmoid -> max-pool 2 -> conv 5x5x6x16 VALID -> [batch norm] -> sigmoid ->
+    max-pool 2 -> flatten (400) -> linear 400x120 -> [batch norm] -> sigmoid -> linear 120x84 -> [batch norm] -> sigmoid ->
+    linear 84x10 -> mean softmax cross-entropy.  Batch norm is snt.BatchNorm in training mode: batch statistics, biased
+    variance, eps 1e-3, an offset ``beta`` and no scale.  Sonnet keeps beta's shape with singleton axes ([1,1,1,6],
+    [1,120]); they are declared flat here ([6], [120]), which changes no arithmetic.  Its moving averages are not trainable
+    and nothing reads them in training mode: they are not declared.  Every ``w`` and ``b`` is drawn from N(0, 0.01^2).
+    Forward and gradient: l2o_lenet_fg (the step-granular path; no fused unroll).
+
+    Only ``conv_channels=(6, 16)``, ``linear_layers=(120, 84)`` is implemented (the reference cannot build the ``None``
+    defaults either).  The data and the minibatches come as in :func:`cifar10`; ``num_threads`` and ``min_queue_examples``
+    are accepted for the reference's signature and have no effect."""
+    del num_threads, min_queue_examples
+    shape = (None if conv_channels is None else tuple(conv_channels),
+             None if linear_layers is None else tuple(linear_layers))
+    if shape != ((6, 16), (120, 84)):
+        raise NotImplementedError("problems.LeNet is implemented for conv_channels=(6, 16), linear_layers=(120, 84) "
+                                  "(got conv_channels=%r, linear_layers=%r)" % (conv_channels, linear_layers))
+    if data is None:
+        data = _load_cifar10(path, mode)
+    images = np.asarray(data["images"], np.float32)
+    labels = np.asarray(data["labels"]).astype(np.int32)
+    if int(np.prod(images.shape[1:])) != 32 * 32 * 3:
+        raise ValueError("problems.LeNet takes 32x32x3 images (got %r)" % (images.shape,))
+    if not 2 <= int(batch_size) <= 1024:
+        raise NotImplementedError("problems.LeNet is implemented for minibatches of 2 to 1024 (got %d)" % batch_size)
+    images = np.ascontiguousarray(images.reshape(len(images), 32 * 32 * 3))
+    batch_norm = bool(batch_norm)
+
+    def build():
+        w, b = _nn_initializers["w"], _nn_initializers["b"]
+        vs = []
+        for i, sh in enumerate([(5, 5, 3, 6), (5, 5, 6, 16)]):
+            vs += [get_variable("conv_net_2d/conv_2d_%d/w" % i, sh, initializer=w),
+                   get_variable("conv_net_2d/conv_2d_%d/b" % i, [sh[3]], initializer=b)]
+            if batch_norm:
+                vs.append(get_variable("conv_net_2d/batch_norm_%d/beta" % i, [sh[3]], initializer=zeros_initializer()))
+        widths = [400, 120, 84, 10]
+        for i in range(3):
+            vs += [get_variable("mlp/linear_%d/w" % i, [widths[i], widths[i + 1]], initializer=w),
+                   get_variable("mlp/linear_%d/b" % i, [widths[i + 1]], initializer=b)]
+            if batch_norm and i < 2:
+                vs.append(get_variable("mlp/batch_norm%s/beta" % ("" if i == 0 else "_1"), [widths[i + 1]],
+                                       initializer=zeros_initializer()))
+        hyper = {"images": images, "labels": labels, "batch_size": int(batch_size), "batch_norm": batch_norm,
+                 "sampler": sampler}
+        return [Term(_abi.PROB_LENET, tuple(vs), {}, hyper, 1.0)]
+
+    return _Build("LeNet", build)
+
+
 def _not_on_hot_path(name, where):
     def factory(*args, **kwargs):
         raise NotImplementedError(
@@ -485,7 +540,6 @@ def _not_on_hot_path(name, where):
 # util.get_config("cifar-multi") (DM/util.py:212-230) calls cifar10 with conv_channels / linear_layers, which the
 # reference's own cifar10 does not take
 cifar_multi = _not_on_hot_path("cifar10(conv_channels=..., linear_layers=...)", "DM/util.py:212")
-LeNet = _not_on_hot_path("LeNet", "DM/problems.py:461")
 NAS = _not_on_hot_path("NAS", "DM/problems.py:540")
 vgg16_cifar10 = _not_on_hot_path("vgg16_cifar10", "DM/problems.py:637")
 confocal_microscopy_3d = _not_on_hot_path("confocal_microscopy_3d", "DM/problems.py:701-956")

@@ -205,11 +205,17 @@ def get_config(problem_name, path=None, mode=None, num_hidden_layer=None, net_na
         problem = problems.cifar10("cifar10", **with_defaults(mode=mode))
         net_config = {"cw": get_default_net_config(path)}
         net_assignments = None
-    elif problem_name in ("lenet", "nas",
+    elif problem_name == "lenet":                                        # DM/util.py:176-184
+        if mode is None:
+            mode = "train" if path is None else "test"
+        problem = problems.LeNet("cifar10", **with_defaults(conv_channels=(6, 16), linear_layers=(120, 84), mode=mode))
+        net_config = {"cw": get_default_net_config(path)}
+        net_assignments = None
+    elif problem_name in ("nas",
                           "vgg16", "cifar-multi", "confocal_microscopy_3d"):
         # neural-network / data-dependent optimizees of DM/util.py:144-230: the net config is
         # reproduced, the problem factory raises (out of the accelerated hot path).
-        problem = getattr(problems, {"lenet": "LeNet", "nas": "NAS", "vgg16": "vgg16_cifar10",
+        problem = getattr(problems, {"nas": "NAS", "vgg16": "vgg16_cifar10",
                                      "cifar-multi": "cifar_multi"}.get(problem_name, problem_name))()
         net_config = {"cw": get_default_net_config(path)}
         net_assignments = None
