@@ -31,7 +31,8 @@
 extern "C" {
 #endif
 
-#define L2O_ABI_VERSION 15   /* v15: l2o_mlp_unroll_multi(_record) also serve minibatch 128 */
+#define L2O_ABI_VERSION 15   /* v15: l2o_mlp_unroll_multi(_record) also serve minibatch 128; later within v15: option 13
+                                (L2O_OPT_PAIR_FAST_LOAD) in bits 60-63 of the options word, the L2O_OPT_BWD_BLOCKS count 12 bits */
 
 #define L2O_OK 0
 #define L2O_ERR_ARG (-1)
@@ -170,12 +171,20 @@ int l2o_last_unroll_form(void);
                                         that kernel (one workgroup per CU, fragments in registers); 1*: one problem per CU, two
                                         waves per SIMD, the gate-GEMM fragments in LDS (k_unroll_lds); 2: k_unroll_lds for every
                                         shard.  (3 was k_unroll_pair2, removed in ABI v12: it measured like 1)                  */
-#define L2O_OPT_COUNT_ 13            /* (* = default) */
+#define L2O_OPT_PAIR_FAST_LOAD 13    /* the two-CU unroll's prologue: 1*: a problem of full tiles (M = D = 32, 64 or 128) runs the
+                                        kernel with unpredicated 16-byte / strided loads of its matrix block and one drain for all
+                                        its loads; 0: the kernel with the per-element predicated gather, which every other shape
+                                        runs anyway.  The registers hold the same bits either way: results are byte-equal.
+                                        (Added within ABI v15: a caller that leaves bits 60-63 of `options` zero -- every count
+                                        below 4096 did -- gets the default.)                                                    */
+#define L2O_OPT_COUNT_ 14            /* (* = default) */
 /* an option's 4-bit field in l2o_net_cfg.options: bit 3 = "set", bits 0-2 = the value.  Fields 0..11 sit at 4 * option;
- * bits 48-63 are the L2O_OPT_BWD_BLOCKS count, so option 12 uses the field that option 5 (that count) leaves unused */
-#define L2O_OPT_FIELD_(o) ((o) == L2O_OPT_ONE_LDS ? L2O_OPT_BWD_BLOCKS : (o))
+ * bits 48-59 are the L2O_OPT_BWD_BLOCKS count (<= 4095), so option 12 uses the field that option 5 (that count) leaves
+ * unused, and option 13 sits in bits 60-63 (the top four bits of what was a 16-bit count until this option arrived) */
+#define L2O_OPT_FIELD_(o) ((o) == L2O_OPT_ONE_LDS ? L2O_OPT_BWD_BLOCKS : (o) == L2O_OPT_PAIR_FAST_LOAD ? 15 : (o))
 #define L2O_OPTW(o, v) ((uint64_t)(8u | ((unsigned)(v) & 7u)) << (4 * L2O_OPT_FIELD_(o)))
-#define L2O_OPTW_BWD_BLOCKS(n) (((uint64_t)(n) & 0xffffu) << 48)
+/* (a count above 4095 saturates: it never spills into option 13's bits) */
+#define L2O_OPTW_BWD_BLOCKS(n) ((uint64_t)((n) > 4095 ? 4095 : (n)) << 48)
 
 /* ---- co-residency (ABI v9) -------------------------------------------------
  * The two-CU unroll and l2o_mlp_unroll exchange data between workgroups that must be resident at the same time.  Before

@@ -44,10 +44,11 @@ SYMBOLS = (
 # encode into every struct they hand to the library.
 # (id 8 was OPT_PAIR_NORMAL until ABI v11; since v13 it is OPT_MLP_XCD_WAVES)
 OPT_PAIR, OPT_PAIR_PLAIN_STORES, OPT_UNROLL_CU, OPT_FG_TWO_PASS, OPT_MLP_GENERIC, OPT_BWD_BLOCKS, OPT_BWD_KERNEL, \
-    OPT_MLP_UNROLL, OPT_MLP_XCD_WAVES, OPT_EXACT_GATES, OPT_WPACK_NO_CLEAR, OPT_MLP_HIER, OPT_ONE_LDS = range(13)
+    OPT_MLP_UNROLL, OPT_MLP_XCD_WAVES, OPT_EXACT_GATES, OPT_WPACK_NO_CLEAR, OPT_MLP_HIER, OPT_ONE_LDS, \
+    OPT_PAIR_FAST_LOAD = range(14)
 OPT_DEFAULTS = {OPT_PAIR: 1, OPT_PAIR_PLAIN_STORES: 1, OPT_UNROLL_CU: 1, OPT_FG_TWO_PASS: 0, OPT_MLP_GENERIC: 0,
                 OPT_BWD_BLOCKS: 0, OPT_BWD_KERNEL: 0, OPT_MLP_UNROLL: 1, OPT_MLP_XCD_WAVES: 0, OPT_EXACT_GATES: 0,
-                OPT_WPACK_NO_CLEAR: 0, OPT_MLP_HIER: 1, OPT_ONE_LDS: 1}
+                OPT_WPACK_NO_CLEAR: 0, OPT_MLP_HIER: 1, OPT_ONE_LDS: 1, OPT_PAIR_FAST_LOAD: 1}
 # l2o_last_unroll_form(): which kernel a fused launch ran (include/l2o_abi.h L2O_FORM_*)
 FORM_NAMES = {1: "k_unroll", 2: "k_unroll_pair", 5: "k_unroll_lds", 6: "k_unroll_cu", 7: "k_unroll_cu8",
               8: "k_mlp_unroll (flat all-reduce)", 9: "k_mlp_unroll (XCD-hierarchical all-reduce)", 10: "k_mlp_unroll (generic loops)",
@@ -63,7 +64,8 @@ _options = {}
 OPTION_NAMES = {"pair": OPT_PAIR, "pair_plain_stores": OPT_PAIR_PLAIN_STORES, "unroll_cu": OPT_UNROLL_CU,
                 "fg_two_pass": OPT_FG_TWO_PASS, "mlp_generic": OPT_MLP_GENERIC, "bwd_blocks": OPT_BWD_BLOCKS,
                 "bwd_kernel": OPT_BWD_KERNEL, "mlp_unroll": OPT_MLP_UNROLL, "exact_gates": OPT_EXACT_GATES,
-                "mlp_hier": OPT_MLP_HIER, "one_lds": OPT_ONE_LDS, "mlp_xcd_waves": OPT_MLP_XCD_WAVES}
+                "mlp_hier": OPT_MLP_HIER, "one_lds": OPT_ONE_LDS, "mlp_xcd_waves": OPT_MLP_XCD_WAVES,
+                "pair_fast_load": OPT_PAIR_FAST_LOAD}
 if os.environ.get("L2O_EXACT_GATES"):
     _options[OPT_EXACT_GATES] = 1
 for _item in filter(None, os.environ.get("L2O_OPTIONS", "").split(",")):
@@ -82,7 +84,7 @@ def set_option(opt, value):
     if value == OPT_DEFAULTS[opt]:
         _options.pop(opt, None)
     else:
-        if opt != OPT_BWD_BLOCKS and not 0 <= value <= 7:
+        if not 0 <= value <= (4095 if opt == OPT_BWD_BLOCKS else 7):
             raise ValueError("option %d: value %d out of range" % (opt, value))
         _options[opt] = value
     return old
@@ -115,10 +117,11 @@ def options_word():
     w = 0
     for o, v in _options.items():
         if o == OPT_BWD_BLOCKS:
-            w |= (v & 0xffff) << 48
+            w |= (v & 0xfff) << 48
         else:
-            # (include/l2o_abi.h L2O_OPT_FIELD_: bits 48-63 are the BWD_BLOCKS count, option 12 uses that option's unused field)
-            w |= (8 | (v & 7)) << (4 * (OPT_BWD_BLOCKS if o == OPT_ONE_LDS else o))
+            # (include/l2o_abi.h L2O_OPT_FIELD_: bits 48-59 are the BWD_BLOCKS count, option 12 uses that option's unused
+            #  field, option 13 bits 60-63)
+            w |= (8 | (v & 7)) << (4 * {OPT_ONE_LDS: OPT_BWD_BLOCKS, OPT_PAIR_FAST_LOAD: 15}.get(o, o))
     return w
 
 

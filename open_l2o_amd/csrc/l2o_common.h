@@ -186,6 +186,18 @@ struct TileState {
 
 // packed HBM layout of one tile's state: [5][64 lanes][4] floats; element e = 4*j + w of a
 // lane is array a = e / 5 (h1, c1, h2, c2) slice t = e % 5.
+// (load_tile_state in two halves, for callers that issue the five loads early and use them late: fetch_ = the loads, unpack_ = the layout)
+__device__ __forceinline__ void fetch_tile_state(float4 (&v)[5], const float* __restrict__ st_tile, int lane) {
+#pragma unroll
+  for (int j = 0; j < 5; ++j) v[j] = *reinterpret_cast<const float4*>(st_tile + (j * 64 + lane) * 4);
+}
+__device__ __forceinline__ void unpack_tile_state(TileState& s, const float4 (&v)[5]) {
+  float e[20];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) { e[4 * j + 0] = v[j].x; e[4 * j + 1] = v[j].y; e[4 * j + 2] = v[j].z; e[4 * j + 3] = v[j].w; }
+#pragma unroll
+  for (int t = 0; t < kNT; ++t) { s.h1[t] = e[t]; s.c1[t] = e[5 + t]; s.h2[t] = e[10 + t]; s.c2[t] = e[15 + t]; }
+}
 __device__ __forceinline__ void load_tile_state(TileState& s, const float* __restrict__ st_tile, int lane) {
   float e[20];
 #pragma unroll

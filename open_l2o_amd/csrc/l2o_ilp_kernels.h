@@ -19,7 +19,10 @@
 #define L2O_ILP_PAIR(PRE, KIND)                                                            \
   L2O_ILP_INST __global__ void k_unroll_pair<PRE, KIND, 2, false, false>(UnrollPairArgs);  \
   L2O_ILP_INST __global__ void k_unroll_pair<PRE, KIND, 4, false, false>(UnrollPairArgs);  \
-  L2O_ILP_INST __global__ void k_unroll_pair<PRE, KIND, 8, false, false>(UnrollPairArgs);
+  L2O_ILP_INST __global__ void k_unroll_pair<PRE, KIND, 8, false, false>(UnrollPairArgs);  \
+  L2O_ILP_INST __global__ void k_unroll_pair<PRE, KIND, 2, false, false, true>(UnrollPairArgs);  \
+  L2O_ILP_INST __global__ void k_unroll_pair<PRE, KIND, 4, false, false, true>(UnrollPairArgs);  \
+  L2O_ILP_INST __global__ void k_unroll_pair<PRE, KIND, 8, false, false, true>(UnrollPairArgs);
 #define L2O_ILP_PAIR_NET(PRE) \
   L2O_ILP_PAIR(PRE, L2O_PROB_QUADRATIC) L2O_ILP_PAIR(PRE, L2O_PROB_LASSO) L2O_ILP_PAIR(PRE, L2O_PROB_RASTRIGIN) \
   L2O_ILP_PAIR(PRE, L2O_PROB_SQUARE_COS)

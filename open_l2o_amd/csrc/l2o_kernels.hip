@@ -1009,7 +1009,7 @@ static const int64_t kOptDefault[L2O_OPT_COUNT_] = {
     /* L2O_OPT_PAIR */ 1, /* L2O_OPT_PAIR_PLAIN_STORES */ 1, /* L2O_OPT_UNROLL_CU */ 1,
     /* L2O_OPT_FG_TWO_PASS */ 0, /* L2O_OPT_MLP_GENERIC */ 0, /* L2O_OPT_BWD_BLOCKS */ 0,
     /* L2O_OPT_BWD_KERNEL */ 0, /* L2O_OPT_MLP_UNROLL */ 1, /* L2O_OPT_MLP_XCD_WAVES */ 0, /* L2O_OPT_EXACT_GATES */ 0,
-    /* L2O_OPT_WPACK_NO_CLEAR */ 0, /* L2O_OPT_MLP_HIER */ 1, /* L2O_OPT_ONE_LDS */ 1};
+    /* L2O_OPT_WPACK_NO_CLEAR */ 0, /* L2O_OPT_MLP_HIER */ 1, /* L2O_OPT_ONE_LDS */ 1, /* L2O_OPT_PAIR_FAST_LOAD */ 1};
 static thread_local uint64_t t_optw = 0;
 struct OptScope {
   uint64_t saved;
@@ -1018,7 +1018,7 @@ struct OptScope {
 };
 static inline uint64_t cfg_optw(const l2o_net_cfg* cfg) { return cfg ? cfg->options : 0; }
 static inline int64_t opt(int o) {
-  if (o == L2O_OPT_BWD_BLOCKS) return (int64_t)((t_optw >> 48) & 0xffffu);     // a count: its own 16-bit field
+  if (o == L2O_OPT_BWD_BLOCKS) return (int64_t)((t_optw >> 48) & 0xfffu);      // a count: its own 12-bit field
   const unsigned nib = (unsigned)(t_optw >> (4 * L2O_OPT_FIELD_(o))) & 0xfu;
   return (nib & 8u) ? (int64_t)(nib & 7u) : kOptDefault[o];
 }
@@ -1172,11 +1172,20 @@ static int launch_unroll_ch(const UnrollArgs& a, const UnrollGeom& g, hipStream_
     {
       void (*fn)(UnrollPairArgs) = nullptr;
       const size_t dyn_lds = L.lds;
+      // full tiles (M = D = padded size) run the FAST prologue, everything else -- and L2O_OPT_PAIR_FAST_LOAD = 0 -- the gather
+      const int SQ = 16 * g.CH;
+      const bool fast = opt(L2O_OPT_PAIR_FAST_LOAD) != 0 && a.pp.M == SQ && a.pp.D == SQ;
+      pa.fast_load = fast ? 1u : 0u;
+#define L2O_PAIR_FN(C)                                                                                       \
+  (fast ? (hist ? k_unroll_pair<PRE, KIND, C, true, false, true>                                             \
+                : (exact ? k_unroll_pair<PRE, KIND, C, false, true, true> : k_unroll_pair<PRE, KIND, C, false, false, true>)) \
+        : (hist ? k_unroll_pair<PRE, KIND, C, true> : (exact ? k_unroll_pair<PRE, KIND, C, false, true> : k_unroll_pair<PRE, KIND, C, false>)))
       switch (g.CH) {
-        case 2: fn = hist ? k_unroll_pair<PRE, KIND, 2, true> : (exact ? k_unroll_pair<PRE, KIND, 2, false, true> : k_unroll_pair<PRE, KIND, 2, false>); break;
-        case 4: fn = hist ? k_unroll_pair<PRE, KIND, 4, true> : (exact ? k_unroll_pair<PRE, KIND, 4, false, true> : k_unroll_pair<PRE, KIND, 4, false>); break;
-        default: fn = hist ? k_unroll_pair<PRE, KIND, 8, true> : (exact ? k_unroll_pair<PRE, KIND, 8, false, true> : k_unroll_pair<PRE, KIND, 8, false>); break;
+        case 2: fn = L2O_PAIR_FN(2); break;
+        case 4: fn = L2O_PAIR_FN(4); break;
+        default: fn = L2O_PAIR_FN(8); break;
       }
+#undef L2O_PAIR_FN
       for (int b0 = 0; b0 < B; b0 += chunk) {
         pa.b0 = b0;
         pa.nb = B - b0 < chunk ? B - b0 : chunk;

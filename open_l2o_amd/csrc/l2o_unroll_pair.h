@@ -39,7 +39,8 @@ struct PairWs {               // header of the caller-owned workspace (never cle
                               // loop of the LAST launch on this workspace -- T steps + the final loss evaluation.  What
                               // bench.py's roofline block divides its work model by: measured cycles, no clock assumption
   long long ticks_total;      // (bytes 24..31) the same wave from kernel entry to its last store: prologue and epilogue included
-  unsigned pad[8];
+  unsigned pad[8];            // -DL2O_PROFILE_PHASES build: the launch marks of wave 0 of workgroup 0 outside the step loop, cycles
+                              // since kernel entry (L2O_LAUNCH_MARK; scripts/phase_profile.py names them); else unused
   long long phases[16];       // phase clock dump of the -DL2O_PROFILE_PHASES build (else unused)
 };
 static_assert(sizeof(PairWs) == 64 + 128, "workspace header layout (include/l2o_abi.h)");
@@ -54,6 +55,8 @@ struct UnrollPairArgs {
   unsigned plain_stores;      // L2O_OPT_PAIR_PLAIN_STORES: a confirmed same-XCD pair publishes with plain stores
   int b0, nb;                 // this launch steps problems [b0, b0 + nb) of the shard: a batch of more than #CU / 2 problems
                               // runs as consecutive launches of <= #CU / 2 (exchange granules and loss partials are per launch)
+  unsigned fast_load;         // the FAST kernel only (the launcher sets it for a problem of full tiles, M = D = SQ): load W without
+                              // predicates.  LAST: the gather kernel's argument block keeps the layout its code was tuned at
 };
 
 __device__ __forceinline__ unsigned long long pack_granule(float v, unsigned tag) {
@@ -138,9 +141,38 @@ __device__ __forceinline__ void dot4q(const l2o::f32x4 a, const l2o::f32x4 b, fl
 #endif
 // (round 4 also ran this body with the fragments in LDS and two workgroups per CU -- k_unroll_pair2; it measured like
 //  k_unroll_lds and was removed in round 5)
+// Launch marks (the -DL2O_PROFILE_PHASES build only; the product build compiles them to nothing): where wave 0 of workgroup 0
+// stands, in cycles since kernel entry, at the stations of the prologue and the epilogue.  A mark pins the schedule
+// (nothing moves across it); the `landed` form also drains the wave's outstanding memory operations first.
+//   0 salt known | 1 W / fragment loads issued | 2 every prologue load landed | 3 handshake done | 4 loop entry |
+//   5 loop exit | 6 last store issued | 7 last store acknowledged
+#ifdef L2O_PROFILE_PHASES
+#define L2O_LAUNCH_MARK(i)                                                                  \
+  do {                                                                                      \
+    __builtin_amdgcn_sched_barrier(0);                                                      \
+    launch_marks[i] = (unsigned)(__builtin_readcyclecounter() - kernel_t0);                 \
+    __builtin_amdgcn_sched_barrier(0);                                                      \
+  } while (0)
+#define L2O_LAUNCH_MARK_LANDED(i)                                                           \
+  do {                                                                                      \
+    __builtin_amdgcn_sched_barrier(0);                                                      \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                             \
+    L2O_LAUNCH_MARK(i);                                                                     \
+  } while (0)
+#else
+#define L2O_LAUNCH_MARK(i) do {} while (0)
+#define L2O_LAUNCH_MARK_LANDED(i) do {} while (0)
+#endif
+
+// Two bodies, one step loop (l2o_unroll_pair_loop.h).  unroll_pair_body_gather is the prologue every shape ran until round 8
+// and ragged shapes still run (FAST = false): per-element predicated loads of W, its load phases one behind the other.
+// unroll_pair_body (FAST = true) is the prologue of a problem of full tiles, M = D = SQ -- the launcher picks it.
 template <int PRE, int KIND, int CH, bool HIST, bool EXACT>
-__device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
+__device__ __forceinline__ void unroll_pair_body_gather(const UnrollPairArgs& pa) {
   const long long kernel_t0 = __builtin_readcyclecounter();
+#ifdef L2O_PROFILE_PHASES
+  unsigned launch_marks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
   constexpr int SQ = 16 * CH;            // padded rows (and columns) of the problem
   constexpr int NWH = CH / 2;            // waves (tiles) per half; tiles beyond the real count idle
   constexpr int NC = 16 * NWH;           // columns (coordinates) owned by a half = SQ / 2
@@ -155,6 +187,10 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
   // observed round-robin placement -- a speed choice only)
   const int bid = blockIdx.x;
   const unsigned salt = pa.use_salt ? ((pa.ws->seq + 1u) & 0x7fffu) << 16 : 0u;
+#ifdef L2O_PROFILE_PHASES
+  asm volatile("" ::"s"(salt));                         // (the mark waits for the sequence word)
+#endif
+  L2O_LAUNCH_MARK(0);
   const int half = (bid >> 3) & 1;
   const int bl = ((bid >> 4) << 3) | (bid & 7);         // problem index inside this launch's chunk
   if (bl >= pa.nb) return;                              // padding blocks of the last group of 16 (both halves)
@@ -217,6 +253,7 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
   core.pin();   // fragments -> AGPRs (MFMA reads them there): the VGPRs hold W, the state and the gate math
   __shared__ __attribute__((aligned(16))) float bias_s[Core::kBiasFloats];   // the gate biases = accumulator inits
   core.stage_bias(bias_s, a.np.wpack, tid, blockDim.x, q);   // (the handshake's __syncthreads() below orders it)
+  L2O_LAUNCH_MARK(1);
   const int j = tile_in_prob * kTile + c;
   const bool live = j < D;
   const size_t idx = (size_t)b * D + j;
@@ -250,6 +287,7 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
     dead = true;
     if (tid == 0) atomicExch(&pa.ws->status, 1u);
   }
+  L2O_LAUNCH_MARK_LANDED(2);
   // ---- handshake: do the two halves of this problem run on the same XCD?  HIP promises nothing about
   // placement (observed: block b on XCD b % 8, hence the b / b + 8 pairing above), so the halves tell each
   // other their XCC_ID once, through the coherent (agent-scope) path, in a granule slot that the step loop
@@ -276,220 +314,215 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
   }
   __syncthreads();
   const bool same_xcd = same_xcd_s != 0;
+  L2O_LAUNCH_MARK(3);
 
-  f32x4 acc1[kNT], acc2[kNT];
-  core.init(s, q);
-  core.preload(acc1, acc2);                                 // accumulator inits of the first step (the biases)
-  // (both recurrent chunks -- L1H: h1(t-1) -> layer 1, L2B: h2(t-1) -> layer 2 -- are issued inside the step loop,
-  //  in the window where the wave waits for its partner's partial residuals)
-  PhaseClock pc;
-  pc.start();
-
-  // Step order (round 4; round 3's order and the variants measured against it: docs/DESIGN_history_r04.md 3.1b): the scaled
-  // iterate goes to LDS the moment the update exists -- at the END of a step, ahead of the split of h2 (27 VALU + the
-  // register copies of the loop-carried B operands sat between the update and its LDS write: ~200 cycles of the step's
-  // critical path) -- and the split runs at the top of the next step UNDER the xs reads; the loss reduction runs under the
-  // residual reads of the g pass; the two row partials share one swap butterfly.
-  // (every q lane writes its coordinate's xs entry: the four q lanes of a coordinate hold the same bits of xv -- the
-  //  network output is a quad_q_sum, whose adds meet a + b on one lane and b + a on its partner -- so the four writes
-  //  agree, and the step loop carries no exec-masked region for them)
-  xs[wv * kTile + c] = live ? xv * sc : 0.0f;
-  const size_t hist_n = (size_t)pp.B_local * D;
-  const long long loop_t0 = __builtin_readcyclecounter();
-  for (int t = 0;; ++t) {
-    const float xsv = xv * sc;
-    const unsigned tag = salt | ((unsigned)t + 1u);     // (T + 1 < 65 535 when salt != 0; the handshake tag ends in 0xffff)
-    const int par = t & 1;
-    pc.mark(0);
-    // (recording: barriers that wait for LDS traffic only -- a __syncthreads() also waits for the write acknowledgement
-    //  of the 5 KB of history the wave has just stored)
-    if (HIST || L2O_PAIR_LDS_BARRIERS) lds_barrier(); else __syncthreads();          // B1: this half's xs complete
-    pc.mark(2);
-    // ---- partial residual over this half's columns: rows 2 x 16 per wave, all SQ rows per half
-    float part;
-    {
-      float4 r0 = {0.f, 0.f, 0.f, 0.f}, r1 = {0.f, 0.f, 0.f, 0.f};
-      Acc4pk r0p = {{0.f, 0.f}, {0.f, 0.f}}, r1p = {{0.f, 0.f}, {0.f, 0.f}};
-      l2o::f32x4 x4v[NWH];
-      lds_load_f4<NWH>(x4v, xsq);
-      core.refresh(s);                     // split h2(t-1) -> chunk L2B operand, under the LDS latency (t = 0: repeats core.init)
-      __builtin_amdgcn_sched_group_barrier(0x100, NWH, 0);     // the DS reads first ...
-      __builtin_amdgcn_sched_group_barrier(0x002, 48, 0);      // ... then the split's VALU block, then the FMAs
-#pragma unroll
-      for (int m = 0; m < NWH; ++m) {
-        if (kPk) { dot4pk(wrq[0][m], x4v[m], r0p); dot4pk(wrq[1][m], x4v[m], r1p); }
-        else { dot4v(wr[0][m], x4v[m], r0); dot4v(wr[1][m], x4v[m], r1); }
-      }
-      // both row partials through ONE butterfly: the 16-lane swap pairs row groups (0,1) and (2,3) of p0 AND p1 at once,
-      // the 32-lane swap finishes both; odd lane groups end with the p1 sum, even ones with the p0 sum -- the lanes
-      // that publish them.  Same additions in the same order as two quad_q_sum calls (bit-identical), 5 instead of 13
-      // instructions and one dependent swap chain instead of two.
-      const float h0 = kPk ? hsum4pk(r0p) : hsum4(r0), h1 = kPk ? hsum4pk(r1p) : hsum4(r1);
-      const u32x2 sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(h0), __float_as_uint(h1), false, false);
-      part = xor32_add(__uint_as_float(sw[0]) + __uint_as_float(sw[1]));
-    }
-    // ---- exchange the partial sums (one granule per row), the previous-h2 matrix work covers the latency
-    if (gq < 2) {
-      // partner on the same XCD (handshake below): a PLAIN 8-byte store keeps the granule in the XCD's L2, where
-      // the partner's sc1 (L1-bypassing) poll finds it; an agent-scope (sc1) store drops the line from L2
-      // and the poll pays the fabric round trip (profiles: 5.55 -> 5.89 G coordinate-steps/s on config 2)
-      if (same_xcd)
-        __hip_atomic_store(mine + par * SQ + myrow, pack_granule(part, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      else
-        __hip_atomic_store(mine + par * SQ + myrow, pack_granule(part, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // (round 5) cos / sin of 2 pi x s for the rastrigin / square_cos terms: computed HERE, in front of the recurrent MFMAs
-    // whose issue they interleave with, instead of behind the partner poll (the loss term) and inside the g pass (the
-    // gradient term) -- both on the step's critical path.  Same function, same argument: bit-identical results.
-    l2o::SinCos trig = {0.0f, 1.0f};
-    if (kCos) trig = l2o::sincos_f(kTwoPi * xsv);
-    pc.mark(3);                                             // partial r + publish
-    // 30 MFMAs (L2B) give the partner time to publish; the first poll load goes out THEN and its L2 round trip
-    // is covered by the other 30 MFMAs (L1H) -- in program order, a single wave issues in order
-#ifndef L2O_PAIR_POLL_AT
-#define L2O_PAIR_POLL_AT 20   // = after chunk L2B.  Packed chunks (20 MFMAs): 5 -> 7.72, 10 -> 7.86, 15 -> 7.95, 20 -> 8.02, 30 -> 7.98 G (config 2)
-#endif
-    constexpr int kPollAt = L2O_PAIR_POLL_AT < Core::kTotal ? L2O_PAIR_POLL_AT : Core::kTotal;   // MFMAs before the first poll load
-    constexpr int kPollAt1 = L2O_PAIR_POLL_AT > Core::kTotal ? L2O_PAIR_POLL_AT - Core::kTotal : 0;
-    core.template issue_l2_prev<0, kPollAt>(s, acc2);
-    if (kPollAt1 > 0) core.template issue_l1_prev<0, kPollAt1>(s, acc1);
-    const unsigned long long* src = theirs + par * SQ + (gq < 2 ? myrow : 0);
-    unsigned long long g = 0;
-#ifdef L2O_ABLATE_EXCHANGE
-    dead = true;
-#endif
-    __builtin_amdgcn_sched_barrier(0);
-    if (gq < 2 && !dead) g = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_sched_barrier(0);
-    if (kPollAt < Core::kTotal) core.template issue_l2_prev<kPollAt, Core::kTotal>(s, acc2);
-    core.template issue_l1_prev<kPollAt1, Core::kTotal>(s, acc1);
-    float contrib = 0.0f;
-    if (gq < 2) {
-      int spins = 0;
-      // The spin is the exception (the first poll load usually finds the granule): a wave whose lanes all have their
-      // granule skips it with ONE uniform branch, and the expectation moves the spin's exec-masked blocks out of the
-      // straight-line step (the asm statement keeps the compiler from merging the two conditions back into one mask)
-      const bool wait = !dead && (unsigned)(g >> 32) != tag;
-      if (__builtin_expect(__builtin_amdgcn_ballot_w64(wait) != 0, 0)) {
-        asm volatile("");
-        if (wait) {
-#pragma nounroll
-          for (;;) {
-            g = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((unsigned)(g >> 32) == tag) break;
-            if (++spins > (1 << 20)) { dead = true; atomicExch(&pa.ws->status, 1u); break; }
-#ifndef L2O_POLL_NOSLEEP
-            __builtin_amdgcn_s_sleep(1);
-#endif
-          }
-        }
-      }
-      const float r = (part + __uint_as_float((unsigned)g)) - myy;   // rows >= M: W row and y are zero -> r == 0
-      rs[myrow] = r;
-      if (row_counted) contrib = coef * r * r;
-    }
-    if (live && q == 0) {
-      if (KIND == L2O_PROB_LASSO) contrib += pp.l1 * __builtin_fabsf(xsv);
-      if (kCos) contrib += pp.alpha - pp.alpha * cj * trig.c;
-    }
-    // the state BEFORE this step's update, for the meta-gradient.  Stored HERE: the poll above is this step's last wait
-    // on vmcnt (loads and stores retire in order), the barriers of the recording kernel wait for LDS traffic only, so
-    // the 5 KB per wave drain under the gate blocks instead of sitting in front of a wait (recording kernel / plain
-    // kernel time at config-2 size: 1.26 -> 1.22, profiles/archive_r01_r03/r03t_*)
-    // (non-temporal stores for these records: 240 -> 338 us per recording unroll -- they stall the store path)
-    if (HIST && t < a.T && tile_real)
-      store_tile_state(s, a.hist_st + ((size_t)t * pp.B_local * tpp + (size_t)b * tpp + tile_in_prob) *
-                                          kStateFloatsPerTile, lane);
-    pc.mark(1);                                             // previous-h2 MFMAs + partner poll
-    if (HIST || L2O_PAIR_LDS_BARRIERS) lds_barrier(); else __syncthreads();          // B2: rs complete
-    pc.mark(4);
-    // this wave's share of f_b(x_t): reduced AFTER the barrier (the DPP chain fills the LDS latency of the g
-    // pass instead of sitting in front of the barrier) and written straight to HBM -- no LDS round, no
-    // thread-0 sum on the step's critical path; k_combine_halves adds the 2 x NWH partials per (step, problem)
-    // (round 4: the residual reads of the g pass go out FIRST; the reduction's DPP chain and the store fill their latency --
-    //  in round 3's ISA the chain sat in front of reads that carried their own wait)
-    l2o::f32x4 rv4v[CH];
-    lds_load_f4<CH>(rv4v, rsq);
-    {
-      const float fw = wave_sum64(contrib);
-      __builtin_amdgcn_sched_group_barrier(0x100, CH, 0);      // the DS reads, then the reduction's DPP chain
-      __builtin_amdgcn_sched_group_barrier(0x002, 24, 0);
-      // (every lane stores: wave_sum64 leaves the same bits on all 64 lanes, so the one address gets one value and the
-      //  store needs no exec-masked region -- 3 857 -> 3 813 cycles per step on config 2)
-      pa.fx_half[((size_t)t * pa.nb + bl) * (2 * NWH) + half * NWH + wv] = fw;
-    }
-    if (t == a.T && !HIST) break;
-
-    // ---- g = W^T r for this wave's 16 coordinates ------------------------------
-    // all CH residual reads are issued back to back (hipcc serialises them on one register
-    // quad otherwise: CH x LDS latency on the critical path), one wait, then the FMAs
-    float4 gacc4 = {0.f, 0.f, 0.f, 0.f};
-    Acc4pk gaccp = {{0.f, 0.f}, {0.f, 0.f}};
-#pragma unroll
-    for (int m = 0; m < CH; ++m) {
-      if (kPk) dot4pk(wtq[m], rv4v[m], gaccp);
-      else dot4v(wt[m], rv4v[m], gacc4);
-    }
-    float gv = quad_q_sum(kPk ? hsum4pk(gaccp) : hsum4(gacc4));
-    if (KIND == L2O_PROB_SQUARE_COS) gv *= 2.0f;            // only the ||wx-y||^2 part carries the 2
-    if (KIND == L2O_PROB_LASSO) gv += pp.l1 * (xsv > 0.f ? 1.f : (xsv < 0.f ? -1.f : 0.f));
-    if (kCos) gv += kTwoPi * pp.alpha * cj * trig.s;
-    gv = live ? gv * cg * sc : 0.0f;
-    if (HIST && live && q == 0) {
-      if (t < a.T) a.hist_g[(size_t)t * hist_n + idx] = gv;
-      else a.hist_gfinal[idx] = gv;
-    }
-    if (HIST && t == a.T) break;                            // (history mode: the gradient at x_T was still needed)
-
-    float in0, in1;
-    if (PRE == L2O_PRE_FC_ELU) {
-      rnnprop_inputs(gv, mv, vv, a.np.beta1, a.np.beta2, a.np.omb1, a.np.omb2, 1.0f - p1h, 1.0f - p2h, in0, in1);
-      if (HIST && live && q == 0) { a.hist_m[(size_t)t * hist_n + idx] = mv; a.hist_v[(size_t)t * hist_n + idx] = vv; }
-      if (!live) { in0 = 0.0f; in1 = 0.0f; }
-      {
-        float hi = p1h * a.np.beta1, er = __builtin_fmaf(p1h, a.np.beta1, -hi);
-        float lo = __builtin_fmaf(p1l, a.np.beta1, er), sum = hi + lo;
-        p1l = lo - (sum - hi); p1h = sum;
-        hi = p2h * a.np.beta2; er = __builtin_fmaf(p2h, a.np.beta2, -hi);
-        lo = __builtin_fmaf(p2l, a.np.beta2, er); sum = hi + lo;
-        p2l = lo - (sum - hi); p2h = sum;
-      }
-    } else {
-      preprocess_grad<PRE>(gv, a.np.k_inv_ln2, a.np.exp_k, in0, in1);
-    }
-    float d = core.template finish<false, bx::NoShadow, false>(s, acc1, acc2, in0, in1, q, pc);   // (re-armed below)
-    if (a.np.tanh_output) {                                 // a real (uniform) branch: as a select hipcc computes the
-      asm volatile("");                                      // exp + rcp of tanh on every step of the nets without it
-      d = tanhf_(d);
-    }
-    xv = __builtin_fmaf(d, a.np.scale, xv);
-    // the next step's scaled iterate -> LDS NOW (its readers sit behind barrier B1; this step's readers of xs all
-    // passed barrier B2 before any wave gets here)
-    __builtin_amdgcn_sched_barrier(0);
-    xs[wv * kTile + c] = live ? xv * sc : 0.0f;           // (all four q lanes, the same value: see above)
-    __builtin_amdgcn_sched_barrier(0);
-    // the next step's accumulator inits (the gate biases: 10 ds_read_b128) go out HERE: their latency overlaps the wait
-    // for barrier B1, which drains this wave's LDS queue anyway
-    core.preload_unpinned(acc1, acc2);
-    __builtin_amdgcn_sched_barrier(0);
-    pc.mark(9);
-  }
-#ifdef L2O_PROFILE_PHASES
-  if (blockIdx.x == 0 && tid == 0) pc.dump(pa.ws->phases);
-#endif
-  if (bid == 0 && tid == 0) pa.ws->ticks = __builtin_readcyclecounter() - loop_t0;
-
-  if (live && q == 0) {
-    a.x[idx] = xv;
-    if (PRE == L2O_PRE_FC_ELU) { a.m[idx] = mv; a.v[idx] = vv; }
-  }
-  if (tile_real) store_tile_state(s, st_tile, lane);
-  if (bid == 0 && tid == 0) pa.ws->ticks_total = __builtin_readcyclecounter() - kernel_t0;
+#include "l2o_unroll_pair_loop.h"
 }
 
-template <int PRE, int KIND, int CH, bool HIST, bool EXACT = false>
+// FAST: the prologue for full tiles (the launcher guarantees M = D = SQ; the kernel itself checks the matrix's alignment and
+// falls back to the gather in place): unpredicated matrix loads, every other load issued behind them, ONE drain, the
+// handshake granule published in front of it and the partner's polled behind it.
+template <int PRE, int KIND, int CH, bool HIST, bool EXACT>
+__device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
+  const long long kernel_t0 = __builtin_readcyclecounter();
+#ifdef L2O_PROFILE_PHASES
+  unsigned launch_marks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+  constexpr int SQ = 16 * CH;            // padded rows (and columns) of the problem
+  constexpr int NWH = CH / 2;            // waves (tiles) per half; tiles beyond the real count idle
+  constexpr int NC = 16 * NWH;           // columns (coordinates) owned by a half = SQ / 2
+  __shared__ __attribute__((aligned(16))) float xs[NC];   // this half's scaled iterate
+  __shared__ __attribute__((aligned(16))) float rs[SQ];   // the full residual
+  const UnrollArgs& a = pa.u;
+  const ProbParams& pp = a.pp;
+  const int D = pp.D, M = pp.M;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int c = lane & 15, q = lane >> 4;
+  // partner workgroups are blockIdx b and b + 8 inside a group of 16 (same XCD under the
+  // observed round-robin placement -- a speed choice only)
+  const int bid = blockIdx.x;
+  const int half = (bid >> 3) & 1;
+  const int bl = ((bid >> 4) << 3) | (bid & 7);         // problem index inside this launch's chunk
+  if (bl >= pa.nb) return;                              // padding blocks of the last group of 16 (both halves)
+  const int b = pa.b0 + bl;                             // problem index inside the batch shard
+  const int tile_in_prob = half * NWH + wv;             // this wave's coordinate tile
+  // GEMV role of a lane = its LSTM role: row / column gr = c, 16-byte chunk gq = q.  The four chunk partial sums
+  // of a row / column then sit on the lanes (c, 0..3) and two permlane swaps add them INTO the lanes that feed
+  // the gradient to the network -- no ds_bpermute (an LDS round trip) between the g pass and the gate math.
+  const int gq = q, gr = c;
+
+  // ---- the matrix lives in registers: no LDS bandwidth in the two GEMV passes -------------
+  //  wr[p][m] : row (2 wv + p) 16 + gr, own columns 16 m + 4 gq + {0..3}     (partial r = W xs)
+  //  wt[m]    : own column wv 16 + gr,   rows       16 m + 4 gq + {0..3}     (g = W^T r)
+  const float* Wb = pp.W + (pp.w_shared ? (size_t)0 : (size_t)b * M * D);
+  const int col0 = half * NC;
+  float4 wr[2][NWH], wt[CH];
+  // ---- prologue, part one: the matrix.
+  // Full tiles (M = D = SQ, the matrix 16-byte aligned: one uniform branch): every element is inside the matrix, so
+  // the row-major copy is 2 x NWH 16-byte loads and the column-major one 4 x CH dword loads at compile-time strides --
+  // no predicate, no exec-masked region, a tenth of the instructions of the gather below.  The same bits either way
+  // (L2O_OPT_PAIR_FAST_LOAD = 0 keeps full tiles on the gather: tests/test_pair_launch_paths.py compares the two).
+  if (pa.fast_load && M == SQ && D == SQ && (reinterpret_cast<size_t>(pp.W) & 15) == 0) {
+    const float4* Wq = reinterpret_cast<const float4*>(Wb + (size_t)(2 * wv * kTile + gr) * SQ + col0 + 4 * gq);
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int m = 0; m < NWH; ++m) wr[p][m] = Wq[(p * kTile * SQ + 16 * m) / 4];
+    const float* Wc = Wb + (size_t)(4 * gq) * SQ + col0 + wv * kTile + gr;
+#pragma unroll
+    for (int m = 0; m < CH; ++m)
+      wt[m] = make_float4(Wc[(16 * m + 0) * SQ], Wc[(16 * m + 1) * SQ], Wc[(16 * m + 2) * SQ], Wc[(16 * m + 3) * SQ]);
+  } else {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int row = (2 * wv + p) * kTile + gr;
+#pragma unroll
+      for (int m = 0; m < NWH; ++m) {
+        float e[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int col = col0 + 16 * m + 4 * gq + k;
+          e[k] = (row < M && col < D) ? Wb[(size_t)row * D + col] : 0.0f;
+        }
+        wr[p][m] = make_float4(e[0], e[1], e[2], e[3]);
+      }
+    }
+    const int col = col0 + wv * kTile + gr;
+#pragma unroll
+    for (int m = 0; m < CH; ++m) {
+      float e[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int row = 16 * m + 4 * gq + k;
+        e[k] = (row < M && col < D) ? Wb[(size_t)row * D + col] : 0.0f;
+      }
+      wt[m] = make_float4(e[0], e[1], e[2], e[3]);
+    }
+  }
+  // ---- the rest of the prologue's global loads, issued back to back behind the matrix; the wave drains them ONCE
+  // (profiles/r08_launch_fixed_cost.txt).  The two header words first: loads return in order, so the wait for the tag
+  // salt -- the handshake below publishes with it -- leaves everything behind them in flight.
+  // (read through an address the compiler cannot see to be uniform: the two words stay in vector registers, in flight,
+  //  until the readfirstlane at the handshake -- as uniform loads they are moved to scalar registers, and waited for, at once)
+  unsigned hdr_lane = 0;
+  asm volatile("" : "+v"(hdr_lane));
+  const unsigned* hdr = &pa.ws->seq + hdr_lane;
+  const unsigned seq_v = hdr[0], fault_v = hdr[1];
+  static_assert(offsetof(PairWs, fault) == offsetof(PairWs, seq) + sizeof(unsigned), "seq and fault are neighbours");
+  // the per-lane scalars: lanes outside the problem read a clamped (valid) address and drop the value with a select --
+  // no exec-masked region, no wait of their own
+  // the residual rows this lane finishes: gq == 0 -> p = 0, gq == 1 -> p = 1 (gq 2, 3 idle)
+  const int myrow = (2 * wv + (gq & 1)) * kTile + gr;
+  const float y_ld = pp.y[(size_t)b * M + (myrow < M ? myrow : 0)];
+  const bool row_counted = gq < 2 && (half == 0 ? (myrow < NC) : (myrow >= NC));   // every row once per pair
+  const int j = tile_in_prob * kTile + c;
+  const bool live = j < D;
+  const size_t idx = (size_t)b * D + j;
+  const size_t idx_ld = (size_t)b * D + (live ? j : 0);
+  const int tpp = (D + kTile - 1) / kTile;
+  const bool tile_real = tile_in_prob < tpp;            // the padded tile of an odd tile count is idle
+  // (the state tile is read whatever it holds -- the kernel stores it at the end, so the memory is there -- and dropped
+  //  below when the launch starts from the zero state: no branch around five loads)
+  float* st_tile = a.st + ((size_t)b * tpp + (tile_real ? tile_in_prob : 0)) * kStateFloatsPerTile;
+  float4 st_ld[5];
+  fetch_tile_state(st_ld, st_tile, lane);
+  const float x_ld = (a.x_in ? a.x_in : a.x)[idx_ld];
+  float sc_ld = 1.0f;
+  if (pp.x_scale) sc_ld = pp.x_scale[idx_ld];
+  constexpr bool kCos = KIND == L2O_PROB_RASTRIGIN || KIND == L2O_PROB_SQUARE_COS;
+  float cj_ld = 0.0f;
+  if (kCos) cj_ld = pp.C[idx_ld];
+  float m_ld = 0.0f, v_ld = 0.0f;
+  if (PRE == L2O_PRE_FC_ELU && !a.zero_state) { m_ld = a.m[idx_ld]; v_ld = a.v[idx_ld]; }
+
+  // ---- per-lane persistent registers -------------------------------------
+  // <= 4 waves per workgroup: bf16x3 gate GEMM, weights in VGPR + AGPR
+  using Core = LstmCore<PRE, !EXACT>;
+  Core core;
+  core.load(a.np.wpack, lane);
+  __builtin_amdgcn_sched_barrier(0);                    // (everything above is issue only; the uses start below)
+  L2O_LAUNCH_MARK(1);
+
+  // ---- handshake, first half: do the two halves of this problem run on the same XCD?  HIP promises nothing about
+  // placement (observed: block b on XCD b % 8, hence the b / b + 8 pairing above), so the halves tell each
+  // other their XCC_ID once, through the coherent (agent-scope) path, in a granule slot that the step loop
+  // does not touch before step 1.  Only a confirmed same-XCD pair uses the L2-resident plain stores.
+  // The granule is PUBLISHED here, the moment the salt is known, and POLLED in front of the loop, behind the drain:
+  // the partner's round trip runs under this wave's own loads.
+  const unsigned seq_w = __builtin_amdgcn_readfirstlane(seq_v), fault_w = __builtin_amdgcn_readfirstlane(fault_v);
+  const unsigned salt = pa.use_salt ? ((seq_w + 1u) & 0x7fffu) << 16 : 0u;
+  unsigned long long* mine = pa.xbuf + ((size_t)bl * 2 + half) * 2 * SQ;
+  const unsigned long long* theirs = pa.xbuf + ((size_t)bl * 2 + (half ^ 1)) * 2 * SQ;
+  const unsigned kHsTag = 0x80000000u | salt | 0xffffu;
+  unsigned my_xcc = 0;
+  if (tid == 0) {
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
+    my_xcc &= 0xfu;
+    __hip_atomic_store(mine + SQ, ((unsigned long long)kHsTag << 32) | my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  L2O_LAUNCH_MARK(0);
+  __builtin_amdgcn_sched_barrier(0);
+  __shared__ __attribute__((aligned(16))) float bias_s[Core::kBiasFloats];   // the gate biases = accumulator inits
+  // (64 * NWH = the workgroup size the launcher uses: a compile-time stride, one masked load per thread instead of a loop)
+  core.stage_bias(bias_s, a.np.wpack, tid, 64 * NWH, q);     // (the handshake's __syncthreads() below orders it)
+  core.pin();   // fragments -> AGPRs (MFMA reads them there): the VGPRs hold W, the state and the gate math
+  constexpr bool kPk = L2O_GEMV_PK != 0;                    // packed GEMV FMAs: one wave per SIMD (see dot4pk)
+  l2o::f32x4 wrq[2][NWH], wtq[CH];                          // (the same values as register quads for the packed FMAs)
+#pragma unroll
+  for (int m = 0; m < NWH; ++m) { wrq[0][m] = as_quad(wr[0][m]); wrq[1][m] = as_quad(wr[1][m]); }
+#pragma unroll
+  for (int m = 0; m < CH; ++m) wtq[m] = as_quad(wt[m]);
+  TileState s;
+  unpack_tile_state(s, st_ld);
+  if (!(tile_real && !a.zero_state)) {
+#pragma unroll
+    for (int t = 0; t < kNT; ++t) s.h1[t] = s.c1[t] = s.h2[t] = s.c2[t] = 0.0f;
+  }
+  const float myy = (gq < 2 && myrow < M) ? y_ld : 0.0f;
+  float xv = live ? x_ld : 0.0f;
+  const float sc = live ? sc_ld : 1.0f;
+  const float cj = live ? cj_ld : 0.0f;
+  float mv = live ? m_ld : 0.0f, vv = live ? v_ld : 0.0f;
+  float p1h = a.p1_hi, p1l = a.p1_lo, p2h = a.p2_hi, p2l = a.p2_lo;
+  constexpr bool kSq = KIND == L2O_PROB_QUADRATIC || KIND == L2O_PROB_SQUARE_COS;
+  const float coef = kSq ? 1.0f : 0.5f;
+  const float cg = (KIND == L2O_PROB_QUADRATIC ? 2.0f : 1.0f) * pp.inv_bg;   // x2 folded in (exact)
+  const float kTwoPi = pp.twopi;
+  const float* xsq = xs + 4 * gq;
+  const float* rsq = rs + 4 * gq;
+  bool dead = false;                                             // partner timed out
+  if (fault_w != 0) {                                            // (test hook: the injected timeout, see PairWs)
+    dead = true;
+    if (tid == 0) atomicExch(&pa.ws->status, 1u);
+  }
+  L2O_LAUNCH_MARK_LANDED(2);
+  // ---- handshake, second half: the partner's granule (published at ITS salt, a prologue ago)
+  __shared__ __attribute__((aligned(16))) int same_xcd_s4[4];
+  int& same_xcd_s = same_xcd_s4[0];
+  if (tid == 0) {
+    unsigned long long g = 0;
+    int spins = 0;
+    bool ok = true;
+#pragma nounroll
+    for (;;) {
+      g = __hip_atomic_load(theirs + SQ, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if ((unsigned)(g >> 32) == kHsTag) break;
+      if (dead || ++spins > (1 << 20)) { ok = false; break; }       // (the step loop reports a missing partner)
+      __builtin_amdgcn_s_sleep(1);
+    }
+    same_xcd_s = ok && pa.plain_stores && ((unsigned)g & 0xfu) == my_xcc;
+  }
+  __syncthreads();
+  const bool same_xcd = same_xcd_s != 0;
+  L2O_LAUNCH_MARK(3);
+
+#include "l2o_unroll_pair_loop.h"
+}
+
+template <int PRE, int KIND, int CH, bool HIST, bool EXACT = false, bool FAST = false>
 __global__ __launch_bounds__(256) void k_unroll_pair(UnrollPairArgs pa) {
-  unroll_pair_body<PRE, KIND, CH, HIST, EXACT>(pa);
+  if constexpr (FAST) unroll_pair_body<PRE, KIND, CH, HIST, EXACT>(pa);
+  else unroll_pair_body_gather<PRE, KIND, CH, HIST, EXACT>(pa);
 }
 
 // The epilogue of a two-CU unroll, one workgroup (64 threads) per step t; runs after every workgroup of the unroll

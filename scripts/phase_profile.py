@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Per-phase cycle breakdown of k_unroll_pair (needs build/lib_phases.so built with
 -DL2O_PROFILE_PHASES; run with L2O_HIP_LIB pointing at it).  Wave 0 of workgroup 0 dumps its
-s_memtime deltas into the workspace into the workspace header."""
+s_memtime deltas into the workspace header: the step loop's phases, and the launch marks -- where the wave
+stands outside the loop (prologue, handshake, epilogue), in cycles since kernel entry.
+    phase_profile.py [T]      (default 100; the launch marks do not depend on T)"""
 import os
 import sys
 import numpy as np
@@ -11,7 +13,7 @@ from open_l2o_amd import _abi, networks
 from open_l2o_amd._engine import HipEngine, NetSpec, ProblemDesc
 
 eng = HipEngine()
-B, D, T = 128, 128, 100
+B, D, T = 128, 128, int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = np.random.default_rng(1)
 net = networks.factory("CoordinateWiseDeepLSTM", {"layers": (20, 20)})        # Sonnet-default random weights
 params = {m: {v: np.array(a) for v, a in d.items()} for m, d in net.variables.items()}
@@ -39,3 +41,16 @@ for n, v in zip(names, raw):
     if n != "-":
         print("  %-40s %10d  %5.1f%%  (%.0f per step)" % (n, v, 100.0 * v / tot, v / T))
 print("  total %d ticks" % tot)
+# launch marks: unsigned pad[8] of the header (bytes 32..63), cycles since kernel entry
+marks = [int(v) for v in ws[32:64].cpu().numpy().view(np.uint32)]
+loop, total = (int(v) for v in ws[16:32].cpu().numpy().view(np.int64))
+names = ["tag salt (ws->seq) known, handshake granule published", "W / fragment loads issued", "every prologue load landed",
+         "handshake done (partner's granule read, barrier)", "loop entry", "loop exit (T steps + the final loss)", "last store issued",
+         "last store acknowledged"]
+print("k_unroll_pair launch marks (cycles since kernel entry, wave 0 of workgroup 0; profiling build: marks pin the schedule)")
+prev = 0
+for v, n in sorted(zip(marks, names)):                # (in the order the wave passes them)
+    print("  %-58s at %9d  (+%d)" % (n, v, v - prev))
+    prev = v
+print("  outside the loop: prologue %d + epilogue %d = %d cycles; ticks %d, ticks_total %d"
+      % (marks[4], marks[7] - marks[5], marks[4] + marks[7] - marks[5], loop, total))
