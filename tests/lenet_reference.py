@@ -115,15 +115,19 @@ class LeNet(object):
         return fg
 
 
+def pool_tie_mask(m):
+    """[B, C, H // 2, W // 2] booleans: the 2x2 pooling windows of the [B, C, H, W] array whose two largest entries are
+    equal (a last odd row / column belongs to no window, as in VALID pooling)."""
+    b, c, hh, ww = m.shape
+    m = m[:, :, :hh // 2 * 2, :ww // 2 * 2]
+    win = m.reshape(b, c, hh // 2, 2, ww // 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(b, c, hh // 2, ww // 2, 4)
+    top = np.sort(win, axis=-1)
+    return top[..., 3] == top[..., 2]
+
+
 def pool_ties(maps):
     """Number of 2x2 pooling windows of the [B, C, H, W] arrays whose two largest entries are equal."""
-    n = 0
-    for m in maps:
-        b, c, hh, ww = m.shape
-        win = m.reshape(b, c, hh // 2, 2, ww // 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(b, c, hh // 2, ww // 2, 4)
-        top = np.sort(win, axis=-1)
-        n += int((top[..., 3] == top[..., 2]).sum())
-    return n
+    return sum(int(pool_tie_mask(m).sum()) for m in maps)
 
 
 def sample_weights(batch_norm, seed):

@@ -5,6 +5,10 @@ flatten order), through torch's autograd.  Not a test module: the tests import i
     net = ConvNet(images [N, 784] or [N, 28, 28, 1], labels [N], batch_norm=True)
     f, grads = net.fg(variables, rows)          # variables / grads: the graph's order (10 with batch norm, 6 without)
     fg = net.flat_fg(shapes, idx)               # fg(x, t) of helpers.oracle_meta_grad, like helpers.mnist_fg
+
+After fg(): net.last_pre_pool holds the two [B, C, H, W] arrays in front of the ReLUs and max-pools (ReLU is non-decreasing, so
+a window's first maximum before it is the window's first maximum after it wherever that maximum is positive, and elsewhere
+the ReLU stops the gradient), for the tests' tie checks (lenet_reference.pool_ties / pool_tie_mask).
 """
 import numpy as np
 import torch
@@ -48,6 +52,7 @@ class ConvNet(object):
         x = torch.tensor(self.images[rows], dtype=dt).reshape(-1, 28, 28, 1).permute(0, 3, 1, 2)    # NHWC -> NCHW
         y = torch.tensor(self.labels[rows])
         it = iter(vs)
+        self.last_pre_pool = []
 
         def layer(h, c_out):
             w, b = next(it), next(it)
@@ -55,6 +60,7 @@ class ConvNet(object):
             if self.batch_norm:
                 gamma, beta = next(it), next(it)
                 h = F.batch_norm(h, None, None, gamma, beta, training=True, eps=EPS)
+            self.last_pre_pool.append(h.detach().numpy())
             return F.max_pool2d(F.relu(h), 2, 2)
 
         h = layer(x, 16)
