@@ -129,6 +129,26 @@ int l2o_last_unroll_form(void);
 #define L2O_FORM_MLP_UNROLL_HIER 9     /* + k_mlp_unroll, fast instantiation, XCD-hierarchical all-reduce                */
 #define L2O_FORM_MLP_UNROLL_GENERIC 10 /* + k_mlp_unroll, generic loops                                                  */
 #define L2O_FORM_MLP_XCD 11            /* + k_mlp_xcd: one optimizee instance per XCD (l2o_mlp_unroll_multi)             */
+/* l2o_last_unroll_variant (added after ABI v15 and not in L2O_ABI_VERSION 15's list: test for the symbol): which
+ * INSTANTIATION of that template the last l2o_unroll / l2o_unroll_record / l2o_unroll_reduce call of this thread launched
+ * -- the template arguments below, packed; an argument the launched template does not have is 0.  Thread-local like
+ * l2o_last_unroll_form, 0 before the first call and after an l2o_mlp_unroll* call.  The fields report what was LAUNCHED,
+ * not what was asked for: EXACT is 0 wherever L2O_OPT_EXACT_GATES does not reach (see that option).
+ *   CH    bits 0-3    k_unroll, k_unroll_pair: 16-float chunks per matrix row, 1 / 2 / 4 / 8
+ *   HIST  bit 4       every template: the recording instantiation (l2o_unroll_record, l2o_unroll_reduce with hist)
+ *   EXACT bit 5       k_unroll (CH <= 4), k_unroll_pair: the fp32-MFMA gate GEMM of L2O_OPT_EXACT_GATES
+ *   FAST  bit 6       k_unroll_pair: the unpredicated prologue of full tiles (L2O_OPT_PAIR_FAST_LOAD)
+ *   KR    bits 8-10   k_unroll_cu8: register-resident state tiles per wave, 2 / 3 / 4
+ *   NV    bits 12-13  k_unroll_cu, k_unroll_cu8: column blocks per lane, 1 (D <= 256) / 2 */
+int l2o_last_unroll_variant(void);
+#define L2O_VARIANT(ch, hist, exact, fast, kr, nv) \
+  ((ch) | ((hist) << 4) | ((exact) << 5) | ((fast) << 6) | ((kr) << 8) | ((nv) << 12))
+#define L2O_VARIANT_CH(w) ((w) & 0xf)
+#define L2O_VARIANT_HIST(w) (((w) >> 4) & 1)
+#define L2O_VARIANT_EXACT(w) (((w) >> 5) & 1)
+#define L2O_VARIANT_FAST(w) (((w) >> 6) & 1)
+#define L2O_VARIANT_KR(w) (((w) >> 8) & 7)
+#define L2O_VARIANT_NV(w) (((w) >> 12) & 3)
 
 /* ---- options (ABI v9: per call, caller-owned) -------------------------------
  * A/B switches between kernels that compute the same thing (all results stay within the parity tolerance).  The
@@ -159,7 +179,16 @@ int l2o_last_unroll_form(void);
 #define L2O_OPT_EXACT_GATES 9        /* 0*: LSTM gate GEMM as a 3-way bf16 split on v_mfma_f32_16x16x32_bf16 (fp32-level error,
                                         but the matrix pipe TRUNCATES small products inside an 8-slot group: a deterministic
                                         bias that shows as ~1e-5 drift at T = 1000); 1: v_mfma_f32_16x16x4_f32 (bit-equal to
-                                        an fmaf chain) in the fused unroll kernels -- slower, for long-horizon evaluation    */
+                                        an fmaf chain) in the fused unroll kernels -- slower, for long-horizon evaluation.
+                                        REACH: the plain (non-recording) l2o_unroll / l2o_unroll_reduce on k_unroll with at most
+                                        four tiles per problem (D <= 64) and on k_unroll_pair; with the option set a 5..8-tile
+                                        problem is routed away from k_unroll_lds to those.  k_unroll with 5..8 tiles is fp32
+                                        MFMA whatever the option says.  NOT reached -- the option is accepted and ignored, the
+                                        gates stay bf16x3: every recording launch (l2o_unroll_record, hist != NULL), the
+                                        streaming forms k_unroll_cu / k_unroll_cu8 (D > 128, or more rows than the resident
+                                        forms hold), k_unroll_lds when recording, and l2o_mlp_unroll*.
+                                        l2o_last_unroll_variant's EXACT bit says what a launch ran
+                                        (tests/test_unroll_instantiations.py pins all of this)                              */
 #define L2O_OPT_WPACK_NO_CLEAR 10     /* 0*: l2o_wpack_device clears the output buffer before it packs (the padding words of the
                                         fragment layout must be zero); 1: the caller vouches that this buffer already holds a
                                         pack of the same net configuration -- the padding is zero, the memset is skipped          */

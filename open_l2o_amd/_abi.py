@@ -26,7 +26,7 @@ PROB_LENET = 8
 
 # every symbol include/l2o_abi.h declares (tests check the library exports all of them)
 SYMBOLS = (
-    "l2o_abi_version", "l2o_last_error", "l2o_build_id", "l2o_last_unroll_form", "l2o_coresident_workgroups", "l2o_wpack_floats", "l2o_wpack_host",
+    "l2o_abi_version", "l2o_last_error", "l2o_build_id", "l2o_last_unroll_form", "l2o_last_unroll_variant", "l2o_coresident_workgroups", "l2o_wpack_floats", "l2o_wpack_host",
     "l2o_state_floats", "l2o_state_pack", "l2o_state_unpack", "l2o_problem_fg", "l2o_problem_hvp", "l2o_mlp_fg",
     "l2o_mlp_scratch_floats", "l2o_mlp_unroll", "l2o_mlp_unroll_record", "l2o_mlp_unroll_supported", "l2o_mlp_unroll_workspace_bytes",
     "l2o_mlp_unroll_multi", "l2o_mlp_unroll_multi_record", "l2o_mlp_unroll_multi_supported", "l2o_mlp_unroll_multi_workspace_bytes",
@@ -59,6 +59,11 @@ MLP_GENERIC = 1           # l2o_mlp.flags
 _options = {}
 # The library never reads the environment; this binding applies two variables ONCE, when it is imported:
 #   L2O_EXACT_GATES=1          the fmaf-chain-equal fp32 MFMA gate GEMM (an accuracy choice a user may want: DESIGN.md 4)
+#                              It reaches the plain (non-recording) fused unroll on k_unroll (D <= 64) and k_unroll_pair, and
+#                              routes 5..8-tile problems away from k_unroll_lds to those; k_unroll at 5..8 tiles is fp32 MFMA
+#                              anyway.  It is accepted and IGNORED -- the gates stay bf16x3 -- by every recording launch, the
+#                              streaming forms (k_unroll_cu / k_unroll_cu8: D > 128, or more rows than the resident forms
+#                              hold) and l2o_mlp_unroll*: last_unroll_variant()["EXACT"] says what a launch ran.
 #   L2O_OPTIONS=name=v,...     any option by name (pair, one_lds, unroll_cu, mlp_hier, ...): the A/B scripts' escape hatch.
 # (Until round 5 every option had its own variable -- thirteen of them; tests and callers use set_option / option_scope.)
 OPTION_NAMES = {"pair": OPT_PAIR, "pair_plain_stores": OPT_PAIR_PLAIN_STORES, "unroll_cu": OPT_UNROLL_CU,
@@ -287,6 +292,15 @@ def last_unroll_form():
     return FORM_NAMES.get(w & 0xff), w >> 8
 
 
+def last_unroll_variant():
+    """The template arguments of the kernel the last l2o_unroll* call of this thread launched (l2o_last_unroll_variant:
+    include/l2o_abi.h L2O_VARIANT_*), as a dict; an argument that template does not have is 0.  EXACT is what ran, not
+    what OPT_EXACT_GATES asked for."""
+    w = int(lib().l2o_last_unroll_variant())
+    return {"CH": w & 0xf, "HIST": (w >> 4) & 1, "EXACT": (w >> 5) & 1, "FAST": (w >> 6) & 1, "KR": (w >> 8) & 7,
+            "NV": (w >> 12) & 3}
+
+
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is not built."""
     global _lib
@@ -306,6 +320,8 @@ def lib():
     L.l2o_build_id.argtypes = []
     L.l2o_last_unroll_form.restype = C.c_int
     L.l2o_last_unroll_form.argtypes = []
+    L.l2o_last_unroll_variant.restype = C.c_int
+    L.l2o_last_unroll_variant.argtypes = []
     L.l2o_coresident_workgroups.restype = C.c_int32
     L.l2o_coresident_workgroups.argtypes = [C.c_void_p, C.c_void_p]
     L.l2o_wpack_floats.restype = C.c_size_t

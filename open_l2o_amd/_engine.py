@@ -827,6 +827,11 @@ class HipEngine(object):
         """(kernel name, dispatches) of the last fused unroll this thread launched (l2o_last_unroll_form)."""
         return _abi.last_unroll_form()
 
+    def last_unroll_variant(self):
+        """{CH, HIST, EXACT, FAST, KR, NV}: the template arguments of that kernel (l2o_last_unroll_variant; 0 where the
+        template has no such argument)."""
+        return _abi.last_unroll_variant()
+
     def last_unroll_exchanges(self):
         """The last fused launch ran a kernel whose workgroups wait for partner workgroups (the two-CU unroll, the
         persistent MLP unroll): the only launches that can end in L2OPartnerTimeout."""

@@ -28,7 +28,13 @@ static thread_local char g_err[512] = "";
 // which kernel form the last l2o_unroll* / l2o_mlp_unroll* call of this thread launched (l2o_last_unroll_form, ABI v12):
 // L2O_FORM_* | dispatches << 8.  Diagnostic only, like g_err -- no launch depends on it.
 static thread_local int g_last_form = 0;
-static inline void note_form(int form, int dispatches = 1) { g_last_form = form | (dispatches << 8); }
+// ... and which instantiation of that template (l2o_last_unroll_variant: the L2O_VARIANT_* fields of include/l2o_abi.h; the
+// five unroll launchers set it right after note_form, every other form leaves the 0 note_form stores)
+static thread_local int g_last_variant = 0;
+static inline void note_form(int form, int dispatches = 1) { g_last_form = form | (dispatches << 8); g_last_variant = 0; }
+static inline void note_variant(int ch, bool hist, bool exact, bool fast, int kr, int nv) {
+  g_last_variant = L2O_VARIANT(ch, hist ? 1 : 0, exact ? 1 : 0, fast ? 1 : 0, kr, nv);
+}
 
 static int fail(int code, const char* fmt, ...) {
   va_list ap;
@@ -1147,6 +1153,7 @@ static int launch_unroll_ch(const UnrollArgs& a, const UnrollGeom& g, hipStream_
       hipLaunchKernelGGL(fl, dim3(a.pp.B_local), dim3(64 * g.nw), lds, s, al);
       HIP_TRY(hipGetLastError());
       note_form(L2O_FORM_UNROLL_LDS);
+      note_variant(0, hist, false, false, 0, 0);
       return L2O_OK;
     }
   }
@@ -1169,6 +1176,7 @@ static int launch_unroll_ch(const UnrollArgs& a, const UnrollGeom& g, hipStream_
     const int B = a.pp.B_local;
     const bool one_launch = chunk >= B;
     const bool exact = opt(L2O_OPT_EXACT_GATES) != 0 && !hist;   // (the recording unroll keeps the bf16x3 core)
+    bool fast_launched = false;
     {
       void (*fn)(UnrollPairArgs) = nullptr;
       const size_t dyn_lds = L.lds;
@@ -1176,6 +1184,7 @@ static int launch_unroll_ch(const UnrollArgs& a, const UnrollGeom& g, hipStream_
       const int SQ = 16 * g.CH;
       const bool fast = opt(L2O_OPT_PAIR_FAST_LOAD) != 0 && a.pp.M == SQ && a.pp.D == SQ;
       pa.fast_load = fast ? 1u : 0u;
+      fast_launched = fast;
 #define L2O_PAIR_FN(C)                                                                                       \
   (fast ? (hist ? k_unroll_pair<PRE, KIND, C, true, false, true>                                             \
                 : (exact ? k_unroll_pair<PRE, KIND, C, false, true, true> : k_unroll_pair<PRE, KIND, C, false, false, true>)) \
@@ -1197,6 +1206,7 @@ static int launch_unroll_ch(const UnrollArgs& a, const UnrollGeom& g, hipStream_
       }
     }
     note_form(L2O_FORM_UNROLL_PAIR, (B + chunk - 1) / chunk);
+    note_variant(g.CH, hist, exact, fast_launched, 0, 0);
     if (fx_done) *fx_done = fx != nullptr && one_launch;
     return L2O_OK;
   }
@@ -1213,6 +1223,7 @@ static int launch_unroll_ch(const UnrollArgs& a, const UnrollGeom& g, hipStream_
   hipLaunchKernelGGL(fn, dim3(a.pp.B_local), dim3(64 * g.nw), g.lds, s, a);
   HIP_TRY(hipGetLastError());
   note_form(L2O_FORM_UNROLL);
+  note_variant(g.CH, hist, exact1 && g.CH <= 4, false, 0, 0);     // (CH == 8 has no EXACT instantiation: fp32 MFMA always)
   return L2O_OK;
 }
 
@@ -1247,6 +1258,7 @@ static int launch_unroll_cu8(const UnrollArgs& a, hipStream_t s) {
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
   hipLaunchKernelGGL(fn, dim3(a.pp.B_local), dim3(kCu8Threads), L.lds, s, a);
   note_form(L2O_FORM_UNROLL_CU8);
+  note_variant(0, hist, false, false, KR, a.pp.D <= 256 ? 1 : 2);
   HIP_TRY(hipGetLastError());
   return L2O_OK;
 }
@@ -1278,6 +1290,7 @@ static int launch_unroll_cu(const UnrollArgs& a_in, hipStream_t s) {
                               (int)L.lds));
   hipLaunchKernelGGL(fn, dim3(a.pp.B_local), dim3(kCuThreads), L.lds, s, a);
   note_form(L2O_FORM_UNROLL_CU);
+  note_variant(0, hist, false, false, 0, a.pp.D <= 256 ? 1 : 2);
   HIP_TRY(hipGetLastError());
   return L2O_OK;
 }
@@ -1291,6 +1304,7 @@ const char* l2o_last_error(void) { return g_err; }
 #endif
 const char* l2o_build_id(void) { return L2O_BUILD_ID; }
 int l2o_last_unroll_form(void) { return g_last_form; }
+int l2o_last_unroll_variant(void) { return g_last_variant; }
 
 size_t l2o_wpack_floats(const l2o_net_cfg* cfg) {
   if (!cfg) return 0;

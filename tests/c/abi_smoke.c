@@ -44,6 +44,7 @@ enum { B = 4, D = 16, T = 5, H = 20 };
 int main(int argc, char** argv) {
   const int host_only = argc > 1 && strcmp(argv[1], "--host") == 0;
   CHECK(l2o_abi_version() == L2O_ABI_VERSION, "ABI version %d != header %d", l2o_abi_version(), L2O_ABI_VERSION);
+  CHECK(l2o_last_unroll_form() == 0 && l2o_last_unroll_variant() == 0, "form / variant before the first unroll are not 0");
   /* (ABI v9: no process-wide option state -- the switches of a call travel in cfg.options, see (a'') below) */
 
   /* L2O-DM: CoordinateWiseDeepLSTM, layers (20, 20), identity preprocess, scale 1 (DM/util.py:138-142) */
@@ -172,6 +173,12 @@ int main(int argc, char** argv) {
       HIP(hipMemcpy(dx, x0, sizeof x0, hipMemcpyHostToDevice)); HIP(hipMemset(dst, 0, nst * 4));
       L2O(l2o_unroll_reduce(&c2, dwp, &prob, NULL, dx, dst, NULL, NULL, T, 1, 0, dfxp, dfx, k == 0 ? NULL : dws, NULL, s));
       HIP(hipStreamSynchronize(s));
+      {                                                        /* the variant word names what ran: EXACT only where asked for */
+        const int vw = l2o_last_unroll_variant();
+        CHECK(L2O_VARIANT_EXACT(vw) == k && L2O_VARIANT_HIST(vw) == 0, "options variant %d: variant word 0x%x", k, vw);
+        if ((l2o_last_unroll_form() & 0xff) == L2O_FORM_UNROLL)
+          CHECK(vw == L2O_VARIANT(D <= 16 ? 1 : 2, 0, k, 0, 0, 0), "options variant %d: variant word 0x%x", k, vw);
+      }
       HIP(hipMemcpy(fx_v, dfx, sizeof fx_v, hipMemcpyDeviceToHost));
       for (int t = 0; t <= T; ++t)
         CHECK(fabsf(fx_v[t] - fx_fused[t]) <= 1e-5f * fabsf(fx_fused[t]), "options variant %d: fx[%d] = %g vs %g", k, t, fx_v[t], fx_fused[t]);

@@ -61,6 +61,9 @@ class OracleEngine(object):
     def last_unroll_exchanges(self):
         return self._exchanged
 
+    def last_unroll_variant(self):
+        return None                                  # (no kernel templates behind this engine)
+
     def unroll_status_tensor(self):
         return self._status
 

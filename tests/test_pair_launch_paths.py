@@ -101,6 +101,9 @@ class _Setup:
             else:
                 e.unroll(self.spec, self.wpack, self.pd, x, st, m, v, T, 1 + T, fx_part, hist=hist, fx=fx)
             assert e.last_unroll_form()[0] == "k_unroll_pair"
+            full = self.pd.M == D and D in (32, 64, 128)       # (an unaligned matrix gathers INSIDE the FAST kernel)
+            assert e.last_unroll_variant() == dict(CH=(D + 31) // 32 * 2 if D <= 64 else 8, HIST=int(self.record), EXACT=0,
+                                                   FAST=int(full and _abi.get_option(_abi.OPT_PAIR_FAST_LOAD) == 1), KR=0, NV=0)
             out = {"fx": fx, "fx_part": fx_part, "x": x, "st": st}
             if m is not None:
                 out.update(m=m, v=v)

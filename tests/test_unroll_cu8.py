@@ -88,6 +88,9 @@ def test_cu8_recording_equals_plain(eng, name, D, form):
     x_rec, fx_rec = run(hist)
     want = "k_unroll_cu" if (form == 1 and rp and D > 256) else "k_unroll_cu8"
     assert eng.last_unroll_form()[0] == want, eng.last_unroll_form()
+    var = eng.last_unroll_variant()                              # the recording instantiation, no exact core in this form
+    assert (var["HIST"], var["NV"], var["EXACT"], var["CH"]) == (1, 1 if D <= 256 else 2, 0, 0), var
+    assert var["KR"] == (0 if want == "k_unroll_cu" else {1: 2 if D <= 256 else 3, 3: 4, 4: 3, 5: 2}[form]), var
     x_pl, fx_pl = run(None)
     np.testing.assert_allclose(x_rec, x_pl, rtol=1e-5, atol=1e-8)
     np.testing.assert_allclose(fx_rec, fx_pl, rtol=1e-6)
