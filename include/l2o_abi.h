@@ -64,6 +64,7 @@ extern "C" {
 #define L2O_PROB_MNIST_CONV 6  /* problems.mnist_conv :291-352 (own entry point: l2o_mnist_conv_fg)         */
 #define L2O_PROB_CIFAR_CONV 7  /* problems.cifar10 :369-458 (own entry point: l2o_cifar_conv_fg)            */
 #define L2O_PROB_LENET 8       /* problems.LeNet :461-537 (own entry point: l2o_lenet_fg)                   */
+#define L2O_PROB_CONFOCAL 9    /* problems.confocal_microscopy_3d :701-956 (own entry point: l2o_confocal_fg) */
 
 /* Hyper-parameters of one optimizer network: the `net_options` dict of
  * networks.factory (DM/networks.py:34-44) as used by util.get_config
@@ -392,6 +393,34 @@ size_t l2o_lenet_scratch_floats(const l2o_lenet* net);
 int l2o_lenet_fg(const l2o_lenet* net, const int32_t* indices /* device [batch] rows of the minibatch */,
                  const float* const* w, float* loss /* device [1] */, float* const* g,
                  float* scratch /* device [l2o_lenet_scratch_floats] */, void* stream);
+
+/* problems.confocal_microscopy_3d (DM/problems.py:701-956; DM/util.py:215-222): per batch row a sum of num_points Gaussian
+ * point-spread functions, each integrated over the voxels of a roi[0] x roi[1] x roi[2] region of interest, plus a background
+ * value, against an l2-normalised target volume: loss = mean_b sum_v (pred - target)^2 with
+ *   pred = sum_p I0 Ex[ix] Ey[iy] Ez[iz] / 8 + bg,  E[k] = erf((k + .5 - c) / (sqrt2 s)) - erf((k - .5 - c) / (sqrt2 s)),
+ *   I0 = .5 + 1.5 t, c = .5 + (R - 1.5) t per axis, s_xy = s_z = 2 + 2 t of the raw values t (not clipped; s <= 0 is not
+ *   guarded); x and y share s_xy.
+ * The target is t * rsqrt(max(sum t^2, 1e-12)) where t is the same sum over the `sim` parameters plus their background, or
+ * (inference = 1) row b of `img`, whose flat voxel index is (iy roi[0] + ix) roi[2] + iz (TF's meshgrid 'xy' order).
+ * The step-granular evaluation only: two launches (three with inference = 1), fp32, fixed-order reductions (two calls on
+ * the same inputs are bit-identical; with g == NULL -- forward only -- the loss has the same bits); stateless: nothing is
+ * cached between calls; no fused unroll (l2o_unroll_supported is 0 for L2O_PROB_CONFOCAL).
+ * theta / g / sim: HOST arrays of 6 num_points + 1 device pointers to [batch] floats in the reference's variable order: for
+ * point 0 .. num_points - 1: I, x, y, z, sigmaxy, sigmaz; then bg.  g may be NULL; sim is NULL (ignored) with inference = 1.
+ * batch in [1, 1024], num_points in [1, 8], every roi edge in [2, 32], else L2O_ERR_UNSUPPORTED (nothing is launched).
+ * Not in L2O_ABI_VERSION 15's list: test for the symbol. */
+typedef struct l2o_confocal {
+  int32_t batch;         /* problems per evaluation (rows)            */
+  int32_t num_points;    /* point-spread functions per row            */
+  int32_t roi[3];        /* Rx, Ry, Rz                                */
+  int32_t inference;     /* 1: the target is `img`                    */
+  int32_t flags;         /* 0                                         */
+  const float* img;      /* device [batch, Rx Ry Rz], or NULL         */
+} l2o_confocal;
+size_t l2o_confocal_scratch_floats(const l2o_confocal* net);
+int l2o_confocal_fg(const l2o_confocal* net, const float* const* theta, const float* const* sim,
+                    float* loss /* device [1] */, float* const* g,
+                    float* scratch /* device [l2o_confocal_scratch_floats] */, void* stream);
 
 /* ---- the fused unroll for the neural optimizee (ABI v6): MetaOptimizer.meta_loss's tf.while_loop
  * (DM/meta.py:338-376; RNNProp DM/meta_rnnprop_eval.py time_step) over problems.mnist (DM/problems.py:246-288) as ONE

@@ -23,6 +23,7 @@ PROB_SIMPLE, PROB_QUADRATIC, PROB_LASSO, PROB_RASTRIGIN, PROB_SQUARE_COS, PROB_M
 PROB_MNIST_CONV = 6
 PROB_CIFAR_CONV = 7
 PROB_LENET = 8
+PROB_CONFOCAL = 9
 
 # every symbol include/l2o_abi.h declares (tests check the library exports all of them)
 SYMBOLS = (
@@ -32,6 +33,7 @@ SYMBOLS = (
     "l2o_mlp_unroll_multi", "l2o_mlp_unroll_multi_record", "l2o_mlp_unroll_multi_supported", "l2o_mlp_unroll_multi_workspace_bytes",
     "l2o_mlp_deep_fg", "l2o_mlp_deep_scratch_floats", "l2o_mnist_conv_fg", "l2o_mnist_conv_scratch_floats",
     "l2o_cifar_conv_fg", "l2o_cifar_conv_scratch_floats", "l2o_lenet_fg", "l2o_lenet_scratch_floats",
+    "l2o_confocal_fg", "l2o_confocal_scratch_floats",
     "l2o_cwlstm_step", "l2o_cwlstm_step_multi", "l2o_cwlstm_step_generic", "l2o_cwlstm_bwd_step_generic", "l2o_gen_state_floats", "l2o_cwlstm_bwd_step", "l2o_cwlstm_bwd_multi", "l2o_cwlstm_bwd_unroll", "l2o_cwlstm_bwd_unroll_compact", "l2o_cwlstm_wgrad_compact", "l2o_unroll", "l2o_unroll_record", "l2o_unroll_reduce", "l2o_unroll_workspace_init", "l2o_unroll_workspace_layout", "l2o_cwlstm_wgrad", "l2o_cwlstm_wgrad_dims", "l2o_unroll_supported", "l2o_unroll_record_supported", "l2o_adam_step", "l2o_adam_step_guarded", "l2o_adam_step_gather", "l2o_wpack_device", "l2o_unroll_workspace_bytes",
     "l2o_unroll_status", "l2o_reduce_fx", "l2o_atb", "l2o_atb_workspace_bytes",
     "l2o_suffix_sums", "l2o_colsum", "l2o_colsum_scratch_floats", "l2o_lincomb", "l2o_rnnprop_input_adjoint",
@@ -186,6 +188,12 @@ class Lenet(C.Structure):
     """struct l2o_lenet"""
     _fields_ = [("batch", C.c_int32), ("n_data", C.c_int32), ("batch_norm", C.c_int32), ("flags", C.c_int32),
                 ("images", C.c_void_p), ("labels", C.c_void_p)]
+
+
+class Confocal(C.Structure):
+    """struct l2o_confocal"""
+    _fields_ = [("batch", C.c_int32), ("num_points", C.c_int32), ("roi", C.c_int32 * 3), ("inference", C.c_int32),
+                ("flags", C.c_int32), ("img", C.c_void_p)]
 
 
 class MlpInstance(C.Structure):        # l2o_mlp_instance: one replica of l2o_mlp_unroll_multi
@@ -367,6 +375,10 @@ def lib():
     L.l2o_lenet_scratch_floats.argtypes = [C.POINTER(Lenet)]
     L.l2o_lenet_fg.restype = C.c_int
     L.l2o_lenet_fg.argtypes = [C.POINTER(Lenet), vp, vp, vp, vp, vp, vp]
+    L.l2o_confocal_scratch_floats.restype = C.c_size_t
+    L.l2o_confocal_scratch_floats.argtypes = [C.POINTER(Confocal)]
+    L.l2o_confocal_fg.restype = C.c_int
+    L.l2o_confocal_fg.argtypes = [C.POINTER(Confocal), vp, vp, vp, vp, vp, vp]
     L.l2o_mlp_unroll_multi_supported.restype = C.c_int
     L.l2o_mlp_unroll_multi_supported.argtypes = [C.POINTER(NetCfg), C.POINTER(Mlp), i32, vp]
     L.l2o_mlp_unroll_multi_workspace_bytes.restype = C.c_size_t

@@ -120,6 +120,15 @@ class LenetDesc:
     labels: torch.Tensor      # [n_data] int32
 
 
+@dataclasses.dataclass
+class ConfocalDesc:
+    """Device-side view of problems.confocal_microscopy_3d (struct l2o_confocal)."""
+    batch: int
+    num_points: int
+    roi: tuple                # (Rx, Ry, Rz)
+    img: torch.Tensor = None  # inference: [batch, Rx Ry Rz] fp32, flat voxel index (iy Rx + ix) Rz + iz
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -398,6 +407,32 @@ class HipEngine(object):
         ga = None if grads is None else (C.c_void_p * len(grads))(*[_ptr(t).value for t in grads])
         _abi.check(self.lib.l2o_lenet_fg(C.byref(c), C.c_void_p(indices.data_ptr()), wa, _ptr(loss), ga, _ptr(scr),
                                          self._stream()))
+
+    def confocal_fg(self, d: ConfocalDesc, theta, sim, loss, grads):
+        """Loss and gradients of the confocal optimizee (l2o_confocal_fg).  theta / sim / grads: lists of 6 num_points + 1
+        device tensors of [batch] floats in the graph's variable order (per point I, x, y, z, sigmaxy, sigmaz; then bg);
+        sim is None in inference mode (d.img is the target); grads may be None: forward only."""
+        c = _abi.Confocal()
+        c.batch, c.num_points, c.inference, c.flags = d.batch, d.num_points, 0 if d.img is None else 1, 0
+        c.roi[0], c.roi[1], c.roi[2] = (int(r) for r in d.roi)
+        c.img = None if d.img is None else C.c_void_p(d.img.data_ptr())
+        n = int(self.lib.l2o_confocal_scratch_floats(C.byref(c)))
+        if not n:
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_confocal_fg: batch in [1, 1024], num_points in [1, 8], "
+                                      "ROI edges in [2, 32] (got %d, %d, %r)" % (d.batch, d.num_points, tuple(d.roi)))
+        nv = 6 * d.num_points + 1
+        if len(theta) != nv or (grads is not None and len(grads) != nv) or ((sim is None) != (d.img is not None)) \
+                or (sim is not None and len(sim) != nv):
+            raise ValueError("l2o_confocal_fg: %d variables for %d points" % (len(theta), d.num_points))
+        if any(t.numel() != d.batch for t in theta) or (d.img is not None and d.img.numel() != d.batch * int(np.prod(d.roi))):
+            raise ValueError("l2o_confocal_fg: every variable holds [batch] floats, img [batch, V]")
+        scr = self.__dict__.get("_confocal_scratch")
+        if scr is None or scr.numel() < n:
+            scr = self._confocal_scratch = self.empty(n)
+        ta = (C.c_void_p * nv)(*[_ptr(t).value for t in theta])
+        sa = None if sim is None else (C.c_void_p * nv)(*[_ptr(t).value for t in sim])
+        ga = None if grads is None else (C.c_void_p * nv)(*[_ptr(t).value for t in grads])
+        _abi.check(self.lib.l2o_confocal_fg(C.byref(c), ta, sa, _ptr(loss), ga, _ptr(scr), self._stream()))
 
     def mlp_unroll_supported(self, spec: NetSpec, d: MlpDesc):
         """A fused persistent unroll exists for this (net, MLP optimizee) pair on this device (l2o_mlp_unroll)."""

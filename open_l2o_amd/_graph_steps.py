@@ -15,6 +15,9 @@ from ._graph_core import PackedState, _DevGrad, _LazyHost, _term_vars, _world, r
 # the optimizees that draw a minibatch per evaluation (problems.mnist, problems.mnist_conv, problems.cifar10,
 # problems.LeNet)
 _SAMPLED = (_abi.PROB_MLP, _abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV, _abi.PROB_LENET)
+# the optimizees that are ONE term over several variables, evaluated by an entry point of their own with the random
+# x-scaling applied around it: the sampled ones and problems.confocal_microscopy_3d (which draws nothing per evaluation)
+_MULTIVAR = _SAMPLED + (_abi.PROB_CONFOCAL,)
 
 
 class StepPlanMixin(object):
@@ -244,6 +247,15 @@ class StepPlanMixin(object):
                                        images=self.engine.tensor(np.ascontiguousarray(term.hyper["images"], np.float32)),
                                        labels=self.engine.int_tensor(term.hyper["labels"]))
             return cache[key]
+        if term.kind == _abi.PROB_CONFOCAL:                    # problems.confocal_microscopy_3d: l2o_confocal_fg
+            key = (id(term), "confocal")
+            if key not in cache:
+                from ._engine import ConfocalDesc
+                img = term.hyper["img"]
+                cache[key] = (term, ConfocalDesc(batch=int(term.hyper["batch_size"]), num_points=int(term.hyper["num_points"]),
+                                                 roi=tuple(term.hyper["roi"]),
+                                                 img=None if img is None else self.engine.tensor(img)))
+            return cache[key][1]
         key = id(term.hyper["images"])
         layers = tuple(term.hyper.get("layers") or (term.var[0].shape[1],))
         key = (key, layers)
@@ -274,7 +286,7 @@ class StepPlanMixin(object):
         # one analytic term of weight 1: the per-problem losses of all T+1 steps are kept and
         # reduced over the batch by ONE launch at the end (like the fused path) instead of a
         # tiny reduction kernel per step
-        defer = single and self.terms[0].kind not in _SAMPLED
+        defer = single and self.terms[0].kind not in _MULTIVAR
         if defer:
             jd = index_of[self.terms[0].var.name]
             f_all = self._scratch("f_all", (T + 1) * descs[jd].B_local)
@@ -284,13 +296,17 @@ class StepPlanMixin(object):
                 fx[t:t + 1].zero_()
             for k, term in enumerate(self.terms):
                 out = fx[t:t + 1] if single else tmp
-                if term.kind in _SAMPLED:
+                if term.kind in _MULTIVAR:
                     js = [index_of[tv.name] for tv in _term_vars(term)]
                     sc = getattr(self, "_mlp_scales", None) or [None] * nvar
                     xin = [panels[j] if sc[j] is None else
                            torch.mul(panels[j], sc[j], out=self._scratch("xs%d" % j, panels[j].numel()).view(panels[j].shape))
                            for j in js]
-                    if term.kind == _abi.PROB_MNIST_CONV:
+                    if term.kind == _abi.PROB_CONFOCAL:
+                        # the simulation parameters are read from the live constants: a reset re-draws them
+                        sim = [self._by_name[c.name].value for c in term.consts["sim"]] or None
+                        eng.confocal_fg(self._mlp_desc(term), xin, sim, out, [grads[j] for j in js] if want_grad else None)
+                    elif term.kind == _abi.PROB_MNIST_CONV:
                         eng.mnist_conv_fg(self._mlp_desc(term), mlp_idx[k][t], xin, out,
                                           [grads[j] for j in js] if want_grad else None)
                     elif term.kind == _abi.PROB_CIFAR_CONV:

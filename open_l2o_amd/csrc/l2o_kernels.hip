@@ -873,6 +873,7 @@ __global__ __launch_bounds__(CH <= 4 ? 256 : 512) void k_unroll(UnrollArgs a) {
 #include "l2o_mnist_conv.h"
 #include "l2o_cifar_conv.h"
 #include "l2o_lenet.h"
+#include "l2o_confocal.h"
 
 #include "l2o_generic.h"
 
@@ -2282,6 +2283,61 @@ int l2o_lenet_fg(const l2o_lenet* m, const int32_t* indices, const float* const*
   }
   const long nthreads = g ? kLnGradThreads : 1;
   hipLaunchKernelGGL(k_ln_grad, dim3((unsigned)((nthreads + kLnThreads - 1) / kLnThreads)), blk, 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return L2O_OK;
+}
+
+// ---- problems.confocal_microscopy_3d (csrc/l2o_confocal.h) ------------------------------------------------------------
+static bool confocal_ok(const l2o_confocal* m) {
+  if (!m || m->batch < 1 || m->batch > kCfMaxBatch || m->num_points < 1 || m->num_points > kCfMaxPts) return false;
+  for (int k = 0; k < 3; ++k)
+    if (m->roi[k] < kCfMinEdge || m->roi[k] > kCfMaxEdge) return false;
+  return m->inference == 0 || m->inference == 1;
+}
+// planes of iy per workgroup: about kCfTargetWgs workgroups in all, a row never split further than one plane per slab
+static void confocal_slabs(const l2o_confocal* m, int* slab, int* nslab) {
+  int want = (kCfTargetWgs + m->batch - 1) / m->batch;
+  if (want > m->roi[1]) want = m->roi[1];
+  *slab = (m->roi[1] + want - 1) / want;
+  *nslab = (m->roi[1] + *slab - 1) / *slab;
+}
+size_t l2o_confocal_scratch_floats(const l2o_confocal* m) {
+  if (!confocal_ok(m)) return 0;
+  int slab, nslab;
+  confocal_slabs(m, &slab, &nslab);
+  return (size_t)nslab * kCfPart * m->batch + m->batch;
+}
+int l2o_confocal_fg(const l2o_confocal* m, const float* const* theta, const float* const* sim, float* loss, float* const* g,
+                    float* scratch, void* stream) {
+  if (!confocal_ok(m))
+    return fail(L2O_ERR_UNSUPPORTED, "l2o_confocal_fg: batch in [1, %d], num_points in [1, %d], roi edges in [%d, %d], "
+                "inference 0 or 1", kCfMaxBatch, kCfMaxPts, kCfMinEdge, kCfMaxEdge);
+  if (!theta || !loss || !scratch) return fail(L2O_ERR_ARG, "l2o_confocal_fg: NULL argument");
+  if (m->inference ? !m->img : !sim) return fail(L2O_ERR_ARG, "l2o_confocal_fg: inference needs img, simulation needs sim");
+  const int nv = 6 * m->num_points + 1;
+  for (int k = 0; k < nv; ++k)
+    if (!theta[k] || (g && !g[k]) || (!m->inference && !sim[k]))
+      return fail(L2O_ERR_ARG, "l2o_confocal_fg: NULL buffer of variable %d", k);
+  CfArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.batch = m->batch; a.P = m->num_points; a.rx = m->roi[0]; a.ry = m->roi[1]; a.rz = m->roi[2];
+  a.inference = m->inference; a.want_grad = g ? 1 : 0;
+  confocal_slabs(m, &a.slab, &a.nslab);
+  a.img = m->inference ? m->img : nullptr;
+  a.part = scratch;
+  a.inv = scratch + (size_t)a.nslab * kCfPart * a.batch;
+  a.loss = loss;
+  for (int k = 0; k < nv; ++k) {
+    a.th[k] = theta[k];
+    a.sim[k] = m->inference ? nullptr : sim[k];
+    a.g[k] = g ? g[k] : nullptr;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 blk(kCfThreads);
+  if (a.inference) hipLaunchKernelGGL(k_cf_norm, dim3(a.batch), blk, 0, s, a);
+  hipLaunchKernelGGL(k_cf_slab, dim3(a.batch, a.nslab), blk, 0, s, a);
+  const int nred = g ? (nv * a.batch + kCfThreads - 1) / kCfThreads : 1;
+  hipLaunchKernelGGL(k_cf_reduce, dim3(nred), blk, 0, s, a);
   HIP_TRY(hipGetLastError());
   return L2O_OK;
 }

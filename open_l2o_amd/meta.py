@@ -38,7 +38,7 @@ from ._graph_adam import AdamMixin
 from ._graph_bptt import BpttMixin
 from ._graph_core import (Fetch, Placeholder, Variable, PackedState, _make_nets, _DEFAULT_CONFIG, _DevGrad, _LazyHost,  # noqa: F401
                           _term_vars, _world, _all_reduce, synced_scale, local_slice, _Slot, set_random_seed, rng, _RngBox)
-from ._graph_steps import StepPlanMixin, _SAMPLED
+from ._graph_steps import StepPlanMixin, _SAMPLED, _MULTIVAR
 
 MetaLoss = collections.namedtuple("MetaLoss", "loss, update, reset, fx, x")     # DM/meta.py:158
 MetaStep = collections.namedtuple("MetaStep", "step, update, reset, fx, x")     # DM/meta.py:159
@@ -64,6 +64,9 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
         decls = list(loss.variables)
         batched_kinds = (_abi.PROB_QUADRATIC, _abi.PROB_LASSO, _abi.PROB_RASTRIGIN, _abi.PROB_SQUARE_COS)
         self.sharded = self.world > 1 and all(t.kind in batched_kinds for t in self.terms)
+        if self.world > 1 and any(t.kind == _abi.PROB_CONFOCAL for t in self.terms):
+            raise NotImplementedError("problems.confocal_microscopy_3d is not implemented for a sharded graph (world size "
+                                      "%d): its batch rows are not split over ranks" % self.world)
         B_global = decls[0].shape[0] if self.sharded else None
         if self.sharded:
             if any(d.shape[0] != B_global for d in decls if not getattr(d, "shared", False)):
@@ -120,7 +123,8 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
     def _panel_shape(self, var):
         """[B_local, D] view of a variable for the kernels."""
         term = self.term_of[var.decl.name]
-        if term.kind in (_abi.PROB_SIMPLE, _abi.PROB_MLP, _abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV, _abi.PROB_LENET):
+        if term.kind in (_abi.PROB_SIMPLE, _abi.PROB_MLP, _abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV, _abi.PROB_LENET,
+                         _abi.PROB_CONFOCAL):               # (confocal: [batch, 1] per variable -> one row of batch floats)
             return 1, int(np.prod(var.shape)) if len(var.shape) else 1
         B = var.shape[0]
         if self.sharded:
@@ -438,7 +442,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
 
         descs = []
         for v, sc in zip(self.x, scales):
-            if self.term_of[v.decl.name].kind in _SAMPLED:
+            if self.term_of[v.decl.name].kind in _MULTIVAR:
                 descs.append(None)                          # (its x-scale is applied around l2o_mlp_fg, see _run_steps)
             else:
                 descs.append(self._desc(v, sc))
@@ -447,7 +451,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
             B, D = self._panel_shape(var)
             panels.append(xv.view(B, D))
         # the MLP / conv optimizees are evaluated at x * scale and their gradient is scale * grad (DM/meta_dm_train.py:384)
-        self._mlp_scales = [sc if self.term_of[v.decl.name].kind in _SAMPLED else None
+        self._mlp_scales = [sc if self.term_of[v.decl.name].kind in _MULTIVAR else None
                             for v, sc in zip(self.x, scales)]
 
         # fx[0..T] of this launch.  Sharded runs all-reduce it ASYNCHRONOUSLY (the next unroll
@@ -963,10 +967,11 @@ class MetaOptimizer(object):
         # DM/meta.py:328-329: without the flag the optimizee gradients are constants of the meta-gradient
         # (tf.stop_gradient); with it dL/dx_t also receives H(x_t) . dL/dg_t (l2o_problem_hvp)
         graph.second_derivatives = bool(second_derivatives)
-        if graph.second_derivatives and any(t.kind in (_abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV, _abi.PROB_LENET)
-                                            for t in graph.terms):
+        if graph.second_derivatives and any(t.kind in (_abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV, _abi.PROB_LENET,
+                                                       _abi.PROB_CONFOCAL) for t in graph.terms):
             raise NotImplementedError("second_derivatives=True is implemented for the analytic optimizees "
-                                      "(problems.mnist_conv / problems.cifar10 / problems.LeNet have no Hessian-vector product)")
+                                      "(problems.mnist_conv / problems.cifar10 / problems.LeNet / "
+                                      "problems.confocal_microscopy_3d have no Hessian-vector product)")
         self._graph = graph
         return graph
 

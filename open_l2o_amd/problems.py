@@ -526,6 +526,61 @@ def LeNet(path, conv_channels=None, linear_layers=None, batch_norm=True, batch_s
     return _Build("LeNet", build)
 
 
+def confocal_microscopy_3d(batch_size=128, num_points=5, ROI=[28, 28, 28], stddev=0.01, dtype="float32", inference=False,
+                           data=None):
+    """3-D point-spread-function fitting.  DM/problems.py:701-956 (util.get_config: batch_size=32, num_points=5).
+
+    Per batch row, ``num_points`` Gaussian point-spread functions, each integrated over the voxels of the ``ROI`` = [Rx, Ry,
+    Rz] volume, plus a background value: pred = sum_p I0 Ex[ix] Ey[iy] Ez[iz] / 8 + bg_var with
+    E[k] = erf((k + .5 - c) / (sqrt2 sigma)) - erf((k - .5 - c) / (sqrt2 sigma)).  The trainable values are raw: I0 = 0.5 +
+    1.5 t, c = 0.5 + (R - 1.5) t per axis, sigma_xy = sigma_z = 2 + 2 t (the quantiles of uniform priors, not clipped).
+    loss = mean_b sum_v (pred - l2_normalize(target))^2, the target being the same sum over the non-trainable ``*_sim``
+    variables (re-drawn on every reset), or with ``inference=True`` a supplied volume.  Forward and gradient:
+    l2o_confocal_fg (the step-granular path; no fused unroll).
+
+    Variables as the reference declares them, each [batch_size, 1]: per point I_var_i, x_var_i, y_var_i, z_var_i,
+    sigmaxy_var_i, sigmaz_var_i ~ U[0, 1); then per point the non-trainable I_sim_i, x_sim_i, y_simi (the reference's
+    spelling), z_sim_i, sigmaxy_sim_i, sigmaz_sim_i ~ U[0, 1); then bg_var ~ N(0, stddev^2); then the non-trainable bg_sim
+    ~ U[0, 1).  With ``inference=True`` there are no ``*_sim`` variables.
+
+    ``data`` (an extension): a variable name present in the dict fixes that variable's initial value; with
+    ``inference=True`` ``data["img"]`` [batch_size, Rx Ry Rz] is required (the reference feeds a placeholder there), its
+    flat voxel index being (iy Rx + ix) Rz + iz, TF's default meshgrid order.
+    Implemented for batch_size in [1, 1024], num_points in [1, 8] and ROI edges in [2, 32]."""
+    roi = tuple(int(r) for r in ROI)
+    batch_size, num_points, inference = int(batch_size), int(num_points), bool(inference)
+    if len(roi) != 3 or not (1 <= batch_size <= 1024 and 1 <= num_points <= 8 and all(2 <= r <= 32 for r in roi)):
+        raise NotImplementedError("problems.confocal_microscopy_3d is implemented for batch_size in [1, 1024], num_points "
+                                  "in [1, 8] and three ROI edges in [2, 32] (got batch_size=%d, num_points=%d, ROI=%r)"
+                                  % (batch_size, num_points, list(ROI)))
+    img = None
+    if inference:
+        if data is None or "img" not in data:
+            raise ValueError("problems.confocal_microscopy_3d(inference=True) needs data['img'] of shape [batch_size, "
+                             "Rx * Ry * Rz] (the reference feeds a placeholder)")
+        img = np.ascontiguousarray(np.asarray(data["img"], np.float32).reshape(batch_size, roi[0] * roi[1] * roi[2]))
+
+    def build():
+        parts = ("I", "x", "y", "z", "sigmaxy", "sigmaz")
+
+        def var(name, default, trainable):
+            return get_variable(name, shape=[batch_size, 1], dtype=dtype, trainable=trainable,
+                                initializer=_maybe_const(data, name, [batch_size, 1], default))
+
+        tr = [var("%s_var_%d" % (p, i), random_uniform_initializer(), True) for i in range(num_points) for p in parts]
+        sim = []
+        if not inference:
+            sim = [var(("y_sim%d" if p == "y" else p + "_sim_%d") % i, random_uniform_initializer(), False)
+                   for i in range(num_points) for p in parts]
+        tr.append(var("bg_var", random_normal_initializer(stddev=stddev), True))
+        if not inference:
+            sim.append(var("bg_sim", random_uniform_initializer(), False))
+        hyper = {"batch_size": batch_size, "num_points": num_points, "roi": roi, "inference": inference, "img": img}
+        return [Term(_abi.PROB_CONFOCAL, tuple(tr), {"sim": tuple(sim)}, hyper, 1.0)]
+
+    return _Build("confocal_microscopy_3d", build)
+
+
 def _not_on_hot_path(name, where):
     def factory(*args, **kwargs):
         raise NotImplementedError(
@@ -542,4 +597,3 @@ def _not_on_hot_path(name, where):
 cifar_multi = _not_on_hot_path("cifar10(conv_channels=..., linear_layers=...)", "DM/util.py:212")
 NAS = _not_on_hot_path("NAS", "DM/problems.py:540")
 vgg16_cifar10 = _not_on_hot_path("vgg16_cifar10", "DM/problems.py:637")
-confocal_microscopy_3d = _not_on_hot_path("confocal_microscopy_3d", "DM/problems.py:701-956")
