@@ -172,22 +172,22 @@ class MlpDeep(C.Structure):
                 ("images", C.c_void_p), ("labels", C.c_void_p)]
 
 
-class MnistConv(C.Structure):
+class ImageNet(C.Structure):
+    """What struct l2o_mnist_conv, l2o_cifar_conv and l2o_lenet all are: the header declares the same fields three times."""
+    _fields_ = [("batch", C.c_int32), ("n_data", C.c_int32), ("batch_norm", C.c_int32), ("flags", C.c_int32),
+                ("images", C.c_void_p), ("labels", C.c_void_p)]
+
+
+class MnistConv(ImageNet):
     """struct l2o_mnist_conv"""
-    _fields_ = [("batch", C.c_int32), ("n_data", C.c_int32), ("batch_norm", C.c_int32), ("flags", C.c_int32),
-                ("images", C.c_void_p), ("labels", C.c_void_p)]
 
 
-class CifarConv(C.Structure):
+class CifarConv(ImageNet):
     """struct l2o_cifar_conv"""
-    _fields_ = [("batch", C.c_int32), ("n_data", C.c_int32), ("batch_norm", C.c_int32), ("flags", C.c_int32),
-                ("images", C.c_void_p), ("labels", C.c_void_p)]
 
 
-class Lenet(C.Structure):
+class Lenet(ImageNet):
     """struct l2o_lenet"""
-    _fields_ = [("batch", C.c_int32), ("n_data", C.c_int32), ("batch_norm", C.c_int32), ("flags", C.c_int32),
-                ("images", C.c_void_p), ("labels", C.c_void_p)]
 
 
 class Confocal(C.Structure):
@@ -199,6 +199,12 @@ class Confocal(C.Structure):
 class MlpInstance(C.Structure):        # l2o_mlp_instance: one replica of l2o_mlp_unroll_multi
     _fields_ = [("indices", C.c_void_p), ("x", C.c_void_p * 4), ("st", C.c_void_p * 4), ("m", C.c_void_p * 4),
                 ("v", C.c_void_p * 4), ("x_scale", C.c_void_p * 4), ("fx", C.c_void_p)]
+
+
+# the step-path optimizees: (descriptor struct, symbol stem).  Every one exports <stem>_scratch_floats(const struct *) ->
+# size_t and <stem>_fg(const struct *, 6 pointers) -> int: lib() declares both from this list
+STEP_FG = ((MlpDeep, "l2o_mlp_deep"), (MnistConv, "l2o_mnist_conv"), (CifarConv, "l2o_cifar_conv"), (Lenet, "l2o_lenet"),
+           (Confocal, "l2o_confocal"))
 
 
 class GenNet(C.Structure):
@@ -359,26 +365,10 @@ def lib():
     L.l2o_mlp_unroll_record.restype = C.c_int
     L.l2o_mlp_unroll_record.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Mlp), vp, vp, vp, vp, vp, vp, i32, i32, vp,
                                         C.POINTER(MlpHist), vp, vp]
-    L.l2o_mlp_deep_scratch_floats.restype = C.c_size_t
-    L.l2o_mlp_deep_scratch_floats.argtypes = [C.POINTER(MlpDeep)]
-    L.l2o_mlp_deep_fg.restype = C.c_int
-    L.l2o_mlp_deep_fg.argtypes = [C.POINTER(MlpDeep), vp, vp, vp, vp, vp, vp]
-    L.l2o_mnist_conv_scratch_floats.restype = C.c_size_t
-    L.l2o_mnist_conv_scratch_floats.argtypes = [C.POINTER(MnistConv)]
-    L.l2o_mnist_conv_fg.restype = C.c_int
-    L.l2o_mnist_conv_fg.argtypes = [C.POINTER(MnistConv), vp, vp, vp, vp, vp, vp]
-    L.l2o_cifar_conv_scratch_floats.restype = C.c_size_t
-    L.l2o_cifar_conv_scratch_floats.argtypes = [C.POINTER(CifarConv)]
-    L.l2o_cifar_conv_fg.restype = C.c_int
-    L.l2o_cifar_conv_fg.argtypes = [C.POINTER(CifarConv), vp, vp, vp, vp, vp, vp]
-    L.l2o_lenet_scratch_floats.restype = C.c_size_t
-    L.l2o_lenet_scratch_floats.argtypes = [C.POINTER(Lenet)]
-    L.l2o_lenet_fg.restype = C.c_int
-    L.l2o_lenet_fg.argtypes = [C.POINTER(Lenet), vp, vp, vp, vp, vp, vp]
-    L.l2o_confocal_scratch_floats.restype = C.c_size_t
-    L.l2o_confocal_scratch_floats.argtypes = [C.POINTER(Confocal)]
-    L.l2o_confocal_fg.restype = C.c_int
-    L.l2o_confocal_fg.argtypes = [C.POINTER(Confocal), vp, vp, vp, vp, vp, vp]
+    for struct, stem in STEP_FG:
+        floats, fg = getattr(L, stem + "_scratch_floats"), getattr(L, stem + "_fg")
+        floats.restype, floats.argtypes = C.c_size_t, [C.POINTER(struct)]
+        fg.restype, fg.argtypes = C.c_int, [C.POINTER(struct)] + [vp] * 6
     L.l2o_mlp_unroll_multi_supported.restype = C.c_int
     L.l2o_mlp_unroll_multi_supported.argtypes = [C.POINTER(NetCfg), C.POINTER(Mlp), i32, vp]
     L.l2o_mlp_unroll_multi_workspace_bytes.restype = C.c_size_t

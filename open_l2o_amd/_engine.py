@@ -9,6 +9,7 @@ the package itself contains no CPU compute path.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import dataclasses
 from typing import Optional
@@ -94,30 +95,24 @@ class MlpDeepDesc:
 
 
 @dataclasses.dataclass
-class MnistConvDesc:
-    """Device-side view of problems.mnist_conv (struct l2o_mnist_conv)."""
+class ImageNetDesc:
+    """Device-side view of an image-net optimizee: a data set and how it is sampled and normalised."""
     batch: int
     batch_norm: bool
-    images: torch.Tensor      # [n_data, 784] fp32 (NHWC 28x28x1)
+    images: torch.Tensor      # [n_data, pixels] fp32 (NHWC, flattened)
     labels: torch.Tensor      # [n_data] int32
 
 
-@dataclasses.dataclass
-class CifarConvDesc:
-    """Device-side view of problems.cifar10 (struct l2o_cifar_conv)."""
-    batch: int
-    batch_norm: bool
-    images: torch.Tensor      # [n_data, 3072] fp32 (NHWC 32x32x3)
-    labels: torch.Tensor      # [n_data] int32
+class MnistConvDesc(ImageNetDesc):
+    """problems.mnist_conv (struct l2o_mnist_conv): images [n_data, 784] (28x28x1)"""
 
 
-@dataclasses.dataclass
-class LenetDesc:
-    """Device-side view of problems.LeNet (struct l2o_lenet)."""
-    batch: int
-    batch_norm: bool
-    images: torch.Tensor      # [n_data, 3072] fp32 (NHWC 32x32x3)
-    labels: torch.Tensor      # [n_data] int32
+class CifarConvDesc(ImageNetDesc):
+    """problems.cifar10 (struct l2o_cifar_conv): images [n_data, 3072] (32x32x3)"""
+
+
+class LenetDesc(ImageNetDesc):
+    """problems.LeNet (struct l2o_lenet): images [n_data, 3072] (32x32x3)"""
 
 
 @dataclasses.dataclass
@@ -129,11 +124,37 @@ class ConfocalDesc:
     img: torch.Tensor = None  # inference: [batch, Rx Ry Rz] fp32, flat voxel index (iy Rx + ix) Rz + iz
 
 
+# The step-path optimizees: ONE term over several variables, evaluated per step by an entry point of its own.  Per problem
+# kind: the engine method the graph calls, the descriptor the graph builds for it, the C struct and the stem of its two
+# symbols (<stem>_scratch_floats, <stem>_fg), the engine attribute that caches its scratch, how many variables a descriptor
+# takes, and whether every evaluation draws a minibatch.  (PROB_MLP is here with SEVERAL hidden layers; one hidden layer has
+# mlp_fg and the fused unrolls.)
+StepOptimizee = collections.namedtuple("StepOptimizee", "method desc struct stem scratch nvars sampled")
+STEP_OPTIMIZEES = {
+    _abi.PROB_MLP: StepOptimizee("mlp_deep_fg", MlpDeepDesc, _abi.MlpDeep, "l2o_mlp_deep", "_mlp_deep_scratch",
+                                 lambda d: 2 * len(d.hidden) + 2, True),
+    _abi.PROB_MNIST_CONV: StepOptimizee("mnist_conv_fg", MnistConvDesc, _abi.MnistConv, "l2o_mnist_conv",
+                                        "_mnist_conv_scratch", lambda d: 10 if d.batch_norm else 6, True),
+    _abi.PROB_CIFAR_CONV: StepOptimizee("cifar_conv_fg", CifarConvDesc, _abi.CifarConv, "l2o_cifar_conv",
+                                        "_cifar_conv_scratch", lambda d: 10 if d.batch_norm else 6, True),
+    _abi.PROB_LENET: StepOptimizee("lenet_fg", LenetDesc, _abi.Lenet, "l2o_lenet", "_lenet_scratch",
+                                   lambda d: 14 if d.batch_norm else 10, True),
+    _abi.PROB_CONFOCAL: StepOptimizee("confocal_fg", ConfocalDesc, _abi.Confocal, "l2o_confocal", "_confocal_scratch",
+                                      lambda d: 6 * d.num_points + 1, False),
+}
+_ENTRY_OF_METHOD = {entry.method: entry for entry in STEP_OPTIMIZEES.values()}
+
+
 def _ptr(t):
     if t is None:
         return None
     assert t.dtype == torch.float32 and t.is_contiguous(), "C-ABI wants contiguous fp32"
     return C.c_void_p(t.data_ptr())
+
+
+def _ptr_array(ts):
+    """void *[len(ts)] of contiguous fp32 device tensors (None: a NULL array)."""
+    return None if ts is None else (C.c_void_p * len(ts))(*[_ptr(t).value for t in ts])
 
 
 class HipEngine(object):
@@ -330,6 +351,18 @@ class HipEngine(object):
         c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
         return c
 
+    def _step_scratch(self, entry, c):
+        """The cached scratch of one step-path optimizee, grown to what <stem>_scratch_floats asks for the struct `c`; None
+        where the library refuses the shape (a size of 0)."""
+        n = int(getattr(self.lib, entry.stem + "_scratch_floats")(C.byref(c)))
+        if not n:
+            return None
+        scr = self.__dict__.get(entry.scratch)
+        if scr is None or scr.numel() < n:
+            scr = self.empty(n)
+            setattr(self, entry.scratch, scr)
+        return scr
+
     def mlp_deep_fg(self, d: MlpDeepDesc, indices, ws, loss, grads):
         """Loss and gradients of the MLP optimizee with SEVERAL hidden layers on ONE minibatch (l2o_mlp_deep_fg).  ws / grads:
         lists [w0, b0, w1, b1, ..., wL, bL] of device tensors (grads may be None: forward only)."""
@@ -339,100 +372,61 @@ class HipEngine(object):
         for k, h in enumerate(d.hidden):
             c.hidden[k] = int(h)
         c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
-        n = int(self.lib.l2o_mlp_deep_scratch_floats(C.byref(c)))
-        if not n:
+        scr = self._step_scratch(STEP_OPTIMIZEES[_abi.PROB_MLP], c)
+        if scr is None:
             raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_mlp_deep_fg: unsupported MLP shape %r" % (d.hidden,))
-        scr = self.__dict__.get("_mlp_deep_scratch")
-        if scr is None or scr.numel() < n:
-            scr = self._mlp_deep_scratch = self.empty(n)
-        nptr = len(ws)
-        wa = (C.c_void_p * nptr)(*[t.data_ptr() for t in ws])
-        ga = None if grads is None else (C.c_void_p * nptr)(*[t.data_ptr() for t in grads])
-        _abi.check(self.lib.l2o_mlp_deep_fg(C.byref(c), C.c_void_p(indices.data_ptr()), wa, _ptr(loss), ga, _ptr(scr),
-                                            self._stream()))
+        _abi.check(self.lib.l2o_mlp_deep_fg(C.byref(c), C.c_void_p(indices.data_ptr()), _ptr_array(ws), _ptr(loss),
+                                            _ptr_array(grads), _ptr(scr), self._stream()))
+
+    def _image_net_fg(self, method, d, indices, ws, loss, grads):
+        """Loss and gradients of an image-net optimizee on ONE minibatch: <stem>_fg of the table entry of the public method
+        that delegates here.  ws / grads: lists of device tensors in the graph's variable order (grads may be None: forward
+        only)."""
+        entry = _ENTRY_OF_METHOD[method]
+        c = entry.struct()
+        c.batch, c.n_data, c.batch_norm, c.flags = d.batch, int(d.images.shape[0]), 1 if d.batch_norm else 0, 0
+        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
+        scr = self._step_scratch(entry, c)
+        if scr is None:
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "%s_fg: unsupported minibatch %d" % (entry.stem, d.batch))
+        if len(ws) != entry.nvars(d) or (grads is not None and len(grads) != len(ws)):
+            raise ValueError("%s_fg: %d variables for batch_norm=%r" % (entry.stem, len(ws), d.batch_norm))
+        _abi.check(getattr(self.lib, entry.stem + "_fg")(C.byref(c), C.c_void_p(indices.data_ptr()), _ptr_array(ws),
+                                                         _ptr(loss), _ptr_array(grads), _ptr(scr), self._stream()))
 
     def mnist_conv_fg(self, d: MnistConvDesc, indices, ws, loss, grads):
-        """Loss and gradients of the conv-net optimizee on ONE minibatch (l2o_mnist_conv_fg).  ws / grads: lists of device
-        tensors in the graph's variable order (10 with batch norm, 6 without; grads may be None: forward only)."""
-        c = _abi.MnistConv()
-        c.batch, c.n_data, c.batch_norm, c.flags = d.batch, int(d.images.shape[0]), 1 if d.batch_norm else 0, 0
-        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
-        n = int(self.lib.l2o_mnist_conv_scratch_floats(C.byref(c)))
-        if not n:
-            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_mnist_conv_fg: unsupported minibatch %d" % d.batch)
-        if len(ws) != (10 if d.batch_norm else 6) or (grads is not None and len(grads) != len(ws)):
-            raise ValueError("l2o_mnist_conv_fg: %d variables for batch_norm=%r" % (len(ws), d.batch_norm))
-        scr = self.__dict__.get("_mnist_conv_scratch")
-        if scr is None or scr.numel() < n:
-            scr = self._mnist_conv_scratch = self.empty(n)
-        wa = (C.c_void_p * len(ws))(*[_ptr(t).value for t in ws])
-        ga = None if grads is None else (C.c_void_p * len(grads))(*[_ptr(t).value for t in grads])
-        _abi.check(self.lib.l2o_mnist_conv_fg(C.byref(c), C.c_void_p(indices.data_ptr()), wa, _ptr(loss), ga, _ptr(scr),
-                                              self._stream()))
+        """problems.mnist_conv (l2o_mnist_conv_fg): 10 variables with batch norm, 6 without."""
+        self._image_net_fg("mnist_conv_fg", d, indices, ws, loss, grads)
 
     def cifar_conv_fg(self, d: CifarConvDesc, indices, ws, loss, grads):
-        """Loss and gradients of the CIFAR-10 conv-net optimizee on ONE minibatch (l2o_cifar_conv_fg).  ws / grads: lists of
-        device tensors in the graph's variable order (10 with batch norm, 6 without; grads may be None: forward only)."""
-        c = _abi.CifarConv()
-        c.batch, c.n_data, c.batch_norm, c.flags = d.batch, int(d.images.shape[0]), 1 if d.batch_norm else 0, 0
-        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
-        n = int(self.lib.l2o_cifar_conv_scratch_floats(C.byref(c)))
-        if not n:
-            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_cifar_conv_fg: unsupported minibatch %d" % d.batch)
-        if len(ws) != (10 if d.batch_norm else 6) or (grads is not None and len(grads) != len(ws)):
-            raise ValueError("l2o_cifar_conv_fg: %d variables for batch_norm=%r" % (len(ws), d.batch_norm))
-        scr = self.__dict__.get("_cifar_conv_scratch")
-        if scr is None or scr.numel() < n:
-            scr = self._cifar_conv_scratch = self.empty(n)
-        wa = (C.c_void_p * len(ws))(*[_ptr(t).value for t in ws])
-        ga = None if grads is None else (C.c_void_p * len(grads))(*[_ptr(t).value for t in grads])
-        _abi.check(self.lib.l2o_cifar_conv_fg(C.byref(c), C.c_void_p(indices.data_ptr()), wa, _ptr(loss), ga, _ptr(scr),
-                                              self._stream()))
+        """problems.cifar10 (l2o_cifar_conv_fg): 10 variables with batch norm, 6 without."""
+        self._image_net_fg("cifar_conv_fg", d, indices, ws, loss, grads)
 
     def lenet_fg(self, d: LenetDesc, indices, ws, loss, grads):
-        """Loss and gradients of the LeNet optimizee on ONE minibatch (l2o_lenet_fg).  ws / grads: lists of device tensors
-        in the graph's variable order (14 with batch norm, 10 without; grads may be None: forward only)."""
-        c = _abi.Lenet()
-        c.batch, c.n_data, c.batch_norm, c.flags = d.batch, int(d.images.shape[0]), 1 if d.batch_norm else 0, 0
-        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
-        n = int(self.lib.l2o_lenet_scratch_floats(C.byref(c)))
-        if not n:
-            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_lenet_fg: unsupported minibatch %d" % d.batch)
-        if len(ws) != (14 if d.batch_norm else 10) or (grads is not None and len(grads) != len(ws)):
-            raise ValueError("l2o_lenet_fg: %d variables for batch_norm=%r" % (len(ws), d.batch_norm))
-        scr = self.__dict__.get("_lenet_scratch")
-        if scr is None or scr.numel() < n:
-            scr = self._lenet_scratch = self.empty(n)
-        wa = (C.c_void_p * len(ws))(*[_ptr(t).value for t in ws])
-        ga = None if grads is None else (C.c_void_p * len(grads))(*[_ptr(t).value for t in grads])
-        _abi.check(self.lib.l2o_lenet_fg(C.byref(c), C.c_void_p(indices.data_ptr()), wa, _ptr(loss), ga, _ptr(scr),
-                                         self._stream()))
+        """problems.LeNet (l2o_lenet_fg): 14 variables with batch norm, 10 without."""
+        self._image_net_fg("lenet_fg", d, indices, ws, loss, grads)
 
     def confocal_fg(self, d: ConfocalDesc, theta, sim, loss, grads):
         """Loss and gradients of the confocal optimizee (l2o_confocal_fg).  theta / sim / grads: lists of 6 num_points + 1
         device tensors of [batch] floats in the graph's variable order (per point I, x, y, z, sigmaxy, sigmaz; then bg);
         sim is None in inference mode (d.img is the target); grads may be None: forward only."""
+        entry = STEP_OPTIMIZEES[_abi.PROB_CONFOCAL]
         c = _abi.Confocal()
         c.batch, c.num_points, c.inference, c.flags = d.batch, d.num_points, 0 if d.img is None else 1, 0
         c.roi[0], c.roi[1], c.roi[2] = (int(r) for r in d.roi)
         c.img = None if d.img is None else C.c_void_p(d.img.data_ptr())
-        n = int(self.lib.l2o_confocal_scratch_floats(C.byref(c)))
-        if not n:
+        scr = self._step_scratch(entry, c)
+        if scr is None:
             raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_confocal_fg: batch in [1, 1024], num_points in [1, 8], "
                                       "ROI edges in [2, 32] (got %d, %d, %r)" % (d.batch, d.num_points, tuple(d.roi)))
-        nv = 6 * d.num_points + 1
+        nv = entry.nvars(d)
         if len(theta) != nv or (grads is not None and len(grads) != nv) or ((sim is None) != (d.img is not None)) \
                 or (sim is not None and len(sim) != nv):
             raise ValueError("l2o_confocal_fg: %d variables for %d points" % (len(theta), d.num_points))
         if any(t.numel() != d.batch for t in theta) or (d.img is not None and d.img.numel() != d.batch * int(np.prod(d.roi))):
             raise ValueError("l2o_confocal_fg: every variable holds [batch] floats, img [batch, V]")
-        scr = self.__dict__.get("_confocal_scratch")
-        if scr is None or scr.numel() < n:
-            scr = self._confocal_scratch = self.empty(n)
-        ta = (C.c_void_p * nv)(*[_ptr(t).value for t in theta])
-        sa = None if sim is None else (C.c_void_p * nv)(*[_ptr(t).value for t in sim])
-        ga = None if grads is None else (C.c_void_p * nv)(*[_ptr(t).value for t in grads])
-        _abi.check(self.lib.l2o_confocal_fg(C.byref(c), ta, sa, _ptr(loss), ga, _ptr(scr), self._stream()))
+        _abi.check(self.lib.l2o_confocal_fg(C.byref(c), _ptr_array(theta), _ptr_array(sim), _ptr(loss), _ptr_array(grads),
+                                            _ptr(scr), self._stream()))
 
     def mlp_unroll_supported(self, spec: NetSpec, d: MlpDesc):
         """A fused persistent unroll exists for this (net, MLP optimizee) pair on this device (l2o_mlp_unroll)."""

@@ -10,14 +10,14 @@ import numpy as np
 import torch
 
 from . import _abi, networks
+from ._engine import STEP_OPTIMIZEES, MlpDesc
 from ._graph_core import PackedState, _DevGrad, _LazyHost, _term_vars, _world, rng  # noqa: F401
 
-# the optimizees that draw a minibatch per evaluation (problems.mnist, problems.mnist_conv, problems.cifar10,
-# problems.LeNet)
-_SAMPLED = (_abi.PROB_MLP, _abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV, _abi.PROB_LENET)
-# the optimizees that are ONE term over several variables, evaluated by an entry point of their own with the random
-# x-scaling applied around it: the sampled ones and problems.confocal_microscopy_3d (which draws nothing per evaluation)
-_MULTIVAR = _SAMPLED + (_abi.PROB_CONFOCAL,)
+# the optimizees that are ONE term over several variables, evaluated by an entry point of their own with the random x-scaling
+# applied around it (_engine.STEP_OPTIMIZEES: problems.mnist, mnist_conv, cifar10, LeNet, confocal_microscopy_3d), and those
+# of them that draw a minibatch per evaluation (all but the last)
+_MULTIVAR = tuple(sorted(STEP_OPTIMIZEES))
+_SAMPLED = tuple(k for k in _MULTIVAR if STEP_OPTIMIZEES[k].sampled)
 
 
 class StepPlanMixin(object):
@@ -221,54 +221,50 @@ class StepPlanMixin(object):
                 bufs[k] = new
 
     def _mlp_desc(self, term):
-        """Device copy of the dataset of a problems.mnist / mnist_conv / cifar10 / LeNet term (uploaded once)."""
+        """The engine's descriptor of a step-path term (the class its STEP_OPTIMIZEES entry names; MlpDesc for problems.mnist
+        with one hidden layer), its data set uploaded once per (images object, batch, batch_norm)."""
         cache = self.__dict__.setdefault("_mlp_cache", {})
-        if term.kind == _abi.PROB_MNIST_CONV:                  # problems.mnist_conv: l2o_mnist_conv_fg
-            key = (id(term.hyper["images"]), "conv", term.hyper["batch_size"], term.hyper["batch_norm"])
-            if key not in cache:
-                from ._engine import MnistConvDesc
-                cache[key] = MnistConvDesc(batch=int(term.hyper["batch_size"]), batch_norm=bool(term.hyper["batch_norm"]),
-                                           images=self.engine.tensor(np.ascontiguousarray(term.hyper["images"], np.float32)),
-                                           labels=self.engine.int_tensor(term.hyper["labels"]))
-            return cache[key]
-        if term.kind == _abi.PROB_CIFAR_CONV:                  # problems.cifar10: l2o_cifar_conv_fg
-            key = (id(term.hyper["images"]), "cifar", term.hyper["batch_size"], term.hyper["batch_norm"])
-            if key not in cache:
-                from ._engine import CifarConvDesc
-                cache[key] = CifarConvDesc(batch=int(term.hyper["batch_size"]), batch_norm=bool(term.hyper["batch_norm"]),
-                                           images=self.engine.tensor(np.ascontiguousarray(term.hyper["images"], np.float32)),
-                                           labels=self.engine.int_tensor(term.hyper["labels"]))
-            return cache[key]
-        if term.kind == _abi.PROB_LENET:                       # problems.LeNet: l2o_lenet_fg
-            key = (id(term.hyper["images"]), "lenet", term.hyper["batch_size"], term.hyper["batch_norm"])
-            if key not in cache:
-                from ._engine import LenetDesc
-                cache[key] = LenetDesc(batch=int(term.hyper["batch_size"]), batch_norm=bool(term.hyper["batch_norm"]),
-                                       images=self.engine.tensor(np.ascontiguousarray(term.hyper["images"], np.float32)),
-                                       labels=self.engine.int_tensor(term.hyper["labels"]))
-            return cache[key]
-        if term.kind == _abi.PROB_CONFOCAL:                    # problems.confocal_microscopy_3d: l2o_confocal_fg
+        entry, hyper, eng = STEP_OPTIMIZEES[term.kind], term.hyper, self.engine
+        if term.kind == _abi.PROB_CONFOCAL:                    # no data set: one descriptor per term
             key = (id(term), "confocal")
             if key not in cache:
-                from ._engine import ConfocalDesc
-                img = term.hyper["img"]
-                cache[key] = (term, ConfocalDesc(batch=int(term.hyper["batch_size"]), num_points=int(term.hyper["num_points"]),
-                                                 roi=tuple(term.hyper["roi"]),
-                                                 img=None if img is None else self.engine.tensor(img)))
+                img = hyper["img"]
+                cache[key] = (term, entry.desc(batch=int(hyper["batch_size"]), num_points=int(hyper["num_points"]),
+                                               roi=tuple(hyper["roi"]), img=None if img is None else eng.tensor(img)))
             return cache[key][1]
-        key = id(term.hyper["images"])
-        layers = tuple(term.hyper.get("layers") or (term.var[0].shape[1],))
-        key = (key, layers)
+        if term.kind != _abi.PROB_MLP:                         # the image nets
+            key = (id(hyper["images"]), entry.stem, hyper["batch_size"], hyper["batch_norm"])
+            if key not in cache:
+                cache[key] = entry.desc(batch=int(hyper["batch_size"]), batch_norm=bool(hyper["batch_norm"]),
+                                        images=eng.tensor(np.ascontiguousarray(hyper["images"], np.float32)),
+                                        labels=eng.int_tensor(hyper["labels"]))
+            return cache[key]
+        layers = tuple(hyper.get("layers") or (term.var[0].shape[1],))
+        key = (id(hyper["images"]), layers)
         if key not in cache:
-            from ._engine import MlpDeepDesc, MlpDesc
-            images = np.ascontiguousarray(term.hyper["images"], np.float32).reshape(len(term.hyper["labels"]), -1)
-            common = dict(batch=int(term.hyper["batch_size"]), activation=0 if term.hyper["activation"] == "sigmoid" else 1,
-                          images=self.engine.tensor(images), labels=self.engine.int_tensor(term.hyper["labels"]))
+            images = np.ascontiguousarray(hyper["images"], np.float32).reshape(len(hyper["labels"]), -1)
+            common = dict(batch=int(hyper["batch_size"]), activation=0 if hyper["activation"] == "sigmoid" else 1,
+                          images=eng.tensor(images), labels=eng.int_tensor(hyper["labels"]))
             if len(layers) == 1:
                 cache[key] = MlpDesc(n_in=images.shape[1], n_hidden=term.var[0].shape[1], n_out=term.var[2].shape[1], **common)
             else:                                           # "mnist_deeper": the step-granular kernels (l2o_mlp_deep_fg)
-                cache[key] = MlpDeepDesc(n_in=images.shape[1], hidden=layers, n_out=term.var[-1].shape[0], **common)
+                cache[key] = entry.desc(n_in=images.shape[1], hidden=layers, n_out=term.var[-1].shape[0], **common)
         return cache[key]
+
+    def _step_fg(self, k, term, js):
+        """fg(t, xin, out, grads): one evaluation of the step-path term number k over the variables js.  The engine method
+        and the descriptor are resolved here, once per unroll; per step there is only the call."""
+        eng, d, entry = self.engine, self._mlp_desc(term), STEP_OPTIMIZEES[term.kind]
+        if term.kind == _abi.PROB_MLP and len(js) == 4:        # one hidden layer: l2o_mlp_fg takes w1, b1, w2, b2
+            call, idx = eng.mlp_fg, self._mlp_idx[k]
+            return lambda t, xin, out, grads: call(d, idx[t], *xin, out, grads)
+        call = getattr(eng, entry.method)
+        if term.kind == _abi.PROB_CONFOCAL:
+            # no minibatch; the simulation parameters are the live constants (a reset re-draws them)
+            sim = [self._by_name[c.name].value for c in term.consts["sim"]] or None
+            return lambda t, xin, out, grads: call(d, xin, sim, out, grads)
+        idx = self._mlp_idx[k]
+        return lambda t, xin, out, grads: call(d, idx[t], xin, out, grads)
 
     def _run_steps(self, T, step0, descs, panels, slots, states, ms, vs, fx, record=None):
         """Step-granular path: per step one forward+gradient launch per loss term
@@ -282,7 +278,12 @@ class StepPlanMixin(object):
         tmp = self._scratch("fx1", 1)
         single = len(self.terms) == 1 and self.terms[0].weight == 1.0
         b1, b2 = float(np.float32(self.beta1)), float(np.float32(self.beta2))
-        mlp_idx = self.__dict__.get("_mlp_idx", {})
+        # the step-path terms: their variables and their evaluation, bound once per unroll
+        step_terms = {}
+        for k, term in enumerate(self.terms):
+            if term.kind in _MULTIVAR:
+                js = [index_of[tv.name] for tv in _term_vars(term)]
+                step_terms[k] = (js, self._step_fg(k, term, js))
         # one analytic term of weight 1: the per-problem losses of all T+1 steps are kept and
         # reduced over the batch by ONE launch at the end (like the fused path) instead of a
         # tiny reduction kernel per step
@@ -296,31 +297,13 @@ class StepPlanMixin(object):
                 fx[t:t + 1].zero_()
             for k, term in enumerate(self.terms):
                 out = fx[t:t + 1] if single else tmp
-                if term.kind in _MULTIVAR:
-                    js = [index_of[tv.name] for tv in _term_vars(term)]
+                if k in step_terms:
+                    js, fg = step_terms[k]
                     sc = getattr(self, "_mlp_scales", None) or [None] * nvar
                     xin = [panels[j] if sc[j] is None else
                            torch.mul(panels[j], sc[j], out=self._scratch("xs%d" % j, panels[j].numel()).view(panels[j].shape))
                            for j in js]
-                    if term.kind == _abi.PROB_CONFOCAL:
-                        # the simulation parameters are read from the live constants: a reset re-draws them
-                        sim = [self._by_name[c.name].value for c in term.consts["sim"]] or None
-                        eng.confocal_fg(self._mlp_desc(term), xin, sim, out, [grads[j] for j in js] if want_grad else None)
-                    elif term.kind == _abi.PROB_MNIST_CONV:
-                        eng.mnist_conv_fg(self._mlp_desc(term), mlp_idx[k][t], xin, out,
-                                          [grads[j] for j in js] if want_grad else None)
-                    elif term.kind == _abi.PROB_CIFAR_CONV:
-                        eng.cifar_conv_fg(self._mlp_desc(term), mlp_idx[k][t], xin, out,
-                                          [grads[j] for j in js] if want_grad else None)
-                    elif term.kind == _abi.PROB_LENET:
-                        eng.lenet_fg(self._mlp_desc(term), mlp_idx[k][t], xin, out,
-                                     [grads[j] for j in js] if want_grad else None)
-                    elif len(js) == 4:
-                        eng.mlp_fg(self._mlp_desc(term), mlp_idx[k][t], *xin, out,
-                                   [grads[j] for j in js] if want_grad else None)
-                    else:                                   # several hidden layers
-                        eng.mlp_deep_fg(self._mlp_desc(term), mlp_idx[k][t], xin, out,
-                                        [grads[j] for j in js] if want_grad else None)
+                    fg(t, xin, out, [grads[j] for j in js] if want_grad else None)
                     if want_grad:
                         for j in js:
                             if sc[j] is not None:

@@ -123,8 +123,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
     def _panel_shape(self, var):
         """[B_local, D] view of a variable for the kernels."""
         term = self.term_of[var.decl.name]
-        if term.kind in (_abi.PROB_SIMPLE, _abi.PROB_MLP, _abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV, _abi.PROB_LENET,
-                         _abi.PROB_CONFOCAL):               # (confocal: [batch, 1] per variable -> one row of batch floats)
+        if term.kind == _abi.PROB_SIMPLE or term.kind in _MULTIVAR:   # (confocal: [batch, 1] -> one row of batch floats)
             return 1, int(np.prod(var.shape)) if len(var.shape) else 1
         B = var.shape[0]
         if self.sharded:
@@ -967,8 +966,7 @@ class MetaOptimizer(object):
         # DM/meta.py:328-329: without the flag the optimizee gradients are constants of the meta-gradient
         # (tf.stop_gradient); with it dL/dx_t also receives H(x_t) . dL/dg_t (l2o_problem_hvp)
         graph.second_derivatives = bool(second_derivatives)
-        if graph.second_derivatives and any(t.kind in (_abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV, _abi.PROB_LENET,
-                                                       _abi.PROB_CONFOCAL) for t in graph.terms):
+        if graph.second_derivatives and any(t.kind in _MULTIVAR and t.kind != _abi.PROB_MLP for t in graph.terms):
             raise NotImplementedError("second_derivatives=True is implemented for the analytic optimizees "
                                       "(problems.mnist_conv / problems.cifar10 / problems.LeNet / "
                                       "problems.confocal_microscopy_3d have no Hessian-vector product)")

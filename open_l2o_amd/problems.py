@@ -333,6 +333,41 @@ def mnist(layers, activation="sigmoid", batch_size=128, mode="train", data=None,
     return _Build("mnist", build)
 
 
+def _image_net_data(name, shape, data, batch_size):
+    """What the image-net factories do with their arrays: images as ONE contiguous float32 [N, pixels] array (its id keys the
+    graph's upload cache) and int32 labels; refuses images that are not ``shape`` and minibatches outside 2 .. 1024."""
+    images = np.asarray(data["images"], np.float32)
+    labels = np.asarray(data["labels"]).astype(np.int32)
+    pixels = int(np.prod(shape))
+    if int(np.prod(images.shape[1:])) != pixels:
+        raise ValueError("problems.%s takes %s images (got %r)" % (name, "x".join(str(n) for n in shape), images.shape))
+    if not 2 <= int(batch_size) <= 1024:
+        raise NotImplementedError("problems.%s is implemented for minibatches of 2 to 1024 (got %d)" % (name, batch_size))
+    return np.ascontiguousarray(images.reshape(len(images), pixels)), labels
+
+
+def _conv_net_variables(in_channels, fc_rows, batch_norm):
+    """The variables of the two-conv-layer nets of mnist_conv and cifar10, in the graph's order."""
+    w = _nn_initializers["w"]
+    vs = [get_variable("conv_layer1/weights1", [3, 3, in_channels, 16], initializer=w),
+          get_variable("conv_layer1/biases1", [16], initializer=zeros_initializer())]
+    if batch_norm:
+        vs += [get_variable("batch_normalization/gamma", [16], initializer=ones_initializer()),
+               get_variable("batch_normalization/beta", [16], initializer=zeros_initializer())]
+    vs += [get_variable("conv_layer2/weights1", [5, 5, 16, 32], initializer=w),
+           get_variable("conv_layer2/biases1", [32], initializer=zeros_initializer())]
+    if batch_norm:
+        vs += [get_variable("batch_normalization_1/gamma", [32], initializer=ones_initializer()),
+               get_variable("batch_normalization_1/beta", [32], initializer=zeros_initializer())]
+    return vs + [get_variable("fc_weights", [fc_rows, 10], initializer=w),
+                 get_variable("fc_bias", [10], initializer=zeros_initializer())]
+
+
+def _image_net_term(kind, vs, images, labels, batch_size, batch_norm, sampler):
+    hyper = {"images": images, "labels": labels, "batch_size": int(batch_size), "batch_norm": batch_norm, "sampler": sampler}
+    return [Term(kind, tuple(vs), {}, hyper, 1.0)]
+
+
 def mnist_conv(batch_norm=True, batch_size=128, mode="train", data=None, sampler=None):
     """Mnist classification with a small conv net.  DM/problems.py:291-352.
 
@@ -343,32 +378,12 @@ def mnist_conv(batch_norm=True, batch_size=128, mode="train", data=None, sampler
     as for :func:`mnist`; a fresh uniform minibatch per evaluation by default."""
     if data is None:
         data = _load_mnist(mode, "mnist_conv")
-    images = np.asarray(data["images"], np.float32)
-    labels = np.asarray(data["labels"]).astype(np.int32)
-    if int(np.prod(images.shape[1:])) != 28 * 28:
-        raise ValueError("problems.mnist_conv takes 28x28x1 images (got %r)" % (images.shape,))
-    if not 2 <= int(batch_size) <= 1024:
-        raise NotImplementedError("problems.mnist_conv is implemented for minibatches of 2 to 1024 (got %d)" % batch_size)
-    images = images.reshape(len(images), 28 * 28)
+    images, labels = _image_net_data("mnist_conv", (28, 28, 1), data, batch_size)
     batch_norm = bool(batch_norm)
 
     def build():
-        w = _nn_initializers["w"]
-        vs = [get_variable("conv_layer1/weights1", [3, 3, 1, 16], initializer=w),
-              get_variable("conv_layer1/biases1", [16], initializer=zeros_initializer())]
-        if batch_norm:
-            vs += [get_variable("batch_normalization/gamma", [16], initializer=ones_initializer()),
-                   get_variable("batch_normalization/beta", [16], initializer=zeros_initializer())]
-        vs += [get_variable("conv_layer2/weights1", [5, 5, 16, 32], initializer=w),
-               get_variable("conv_layer2/biases1", [32], initializer=zeros_initializer())]
-        if batch_norm:
-            vs += [get_variable("batch_normalization_1/gamma", [32], initializer=ones_initializer()),
-                   get_variable("batch_normalization_1/beta", [32], initializer=zeros_initializer())]
-        vs += [get_variable("fc_weights", [512, 10], initializer=w),
-               get_variable("fc_bias", [10], initializer=zeros_initializer())]
-        hyper = {"images": images, "labels": labels, "batch_size": int(batch_size), "batch_norm": batch_norm,
-                 "sampler": sampler}
-        return [Term(_abi.PROB_MNIST_CONV, tuple(vs), {}, hyper, 1.0)]
+        return _image_net_term(_abi.PROB_MNIST_CONV, _conv_net_variables(1, 512, batch_norm), images, labels, batch_size,
+                               batch_norm, sampler)
 
     return _Build("mnist_conv", build)
 
@@ -441,32 +456,12 @@ def cifar10(path, batch_norm=True, batch_size=128, num_threads=4, min_queue_exam
     del num_threads, min_queue_examples
     if data is None:
         data = _load_cifar10(path, mode)
-    images = np.asarray(data["images"], np.float32)
-    labels = np.asarray(data["labels"]).astype(np.int32)
-    if int(np.prod(images.shape[1:])) != 32 * 32 * 3:
-        raise ValueError("problems.cifar10 takes 32x32x3 images (got %r)" % (images.shape,))
-    if not 2 <= int(batch_size) <= 1024:
-        raise NotImplementedError("problems.cifar10 is implemented for minibatches of 2 to 1024 (got %d)" % batch_size)
-    images = np.ascontiguousarray(images.reshape(len(images), 32 * 32 * 3))
+    images, labels = _image_net_data("cifar10", (32, 32, 3), data, batch_size)
     batch_norm = bool(batch_norm)
 
     def build():
-        w = _nn_initializers["w"]
-        vs = [get_variable("conv_layer1/weights1", [3, 3, 3, 16], initializer=w),
-              get_variable("conv_layer1/biases1", [16], initializer=zeros_initializer())]
-        if batch_norm:
-            vs += [get_variable("batch_normalization/gamma", [16], initializer=ones_initializer()),
-                   get_variable("batch_normalization/beta", [16], initializer=zeros_initializer())]
-        vs += [get_variable("conv_layer2/weights1", [5, 5, 16, 32], initializer=w),
-               get_variable("conv_layer2/biases1", [32], initializer=zeros_initializer())]
-        if batch_norm:
-            vs += [get_variable("batch_normalization_1/gamma", [32], initializer=ones_initializer()),
-                   get_variable("batch_normalization_1/beta", [32], initializer=zeros_initializer())]
-        vs += [get_variable("fc_weights", [32, 10], initializer=w),
-               get_variable("fc_bias", [10], initializer=zeros_initializer())]
-        hyper = {"images": images, "labels": labels, "batch_size": int(batch_size), "batch_norm": batch_norm,
-                 "sampler": sampler}
-        return [Term(_abi.PROB_CIFAR_CONV, tuple(vs), {}, hyper, 1.0)]
+        return _image_net_term(_abi.PROB_CIFAR_CONV, _conv_net_variables(3, 32, batch_norm), images, labels, batch_size,
+                               batch_norm, sampler)
 
     return _Build("cifar10", build)
 
@@ -495,13 +490,7 @@ def LeNet(path, conv_channels=None, linear_layers=None, batch_norm=True, batch_s
                                   "(got conv_channels=%r, linear_layers=%r)" % (conv_channels, linear_layers))
     if data is None:
         data = _load_cifar10(path, mode)
-    images = np.asarray(data["images"], np.float32)
-    labels = np.asarray(data["labels"]).astype(np.int32)
-    if int(np.prod(images.shape[1:])) != 32 * 32 * 3:
-        raise ValueError("problems.LeNet takes 32x32x3 images (got %r)" % (images.shape,))
-    if not 2 <= int(batch_size) <= 1024:
-        raise NotImplementedError("problems.LeNet is implemented for minibatches of 2 to 1024 (got %d)" % batch_size)
-    images = np.ascontiguousarray(images.reshape(len(images), 32 * 32 * 3))
+    images, labels = _image_net_data("LeNet", (32, 32, 3), data, batch_size)
     batch_norm = bool(batch_norm)
 
     def build():
@@ -519,9 +508,7 @@ def LeNet(path, conv_channels=None, linear_layers=None, batch_norm=True, batch_s
             if batch_norm and i < 2:
                 vs.append(get_variable("mlp/batch_norm%s/beta" % ("" if i == 0 else "_1"), [widths[i + 1]],
                                        initializer=zeros_initializer()))
-        hyper = {"images": images, "labels": labels, "batch_size": int(batch_size), "batch_norm": batch_norm,
-                 "sampler": sampler}
-        return [Term(_abi.PROB_LENET, tuple(vs), {}, hyper, 1.0)]
+        return _image_net_term(_abi.PROB_LENET, vs, images, labels, batch_size, batch_norm, sampler)
 
     return _Build("LeNet", build)
 

@@ -1,0 +1,244 @@
+"""Time one step-path optimizee on the GPU, in one process, with HIP events after a warm-up:
+
+  * fg_us: us per evaluation through the engine -- loss and all gradients (the image nets: of one minibatch, batch norm on,
+    the reference's default; confocal: simulation mode, and forward only as forward_only_us);
+  * step_us: us per optimizer step -- one unroll of meta_loss over util.get_config(<problem>) (its default coordinate-wise
+    net over all coordinates) on the step-granular path, divided by its length: per step the fg, the LSTM step and, for the
+    image nets, the minibatch draw;
+  * lenet and confocal, as the yardstick that is not the code under test: the same loss and gradients through float32 torch
+    autograd on the same GPU, timed the same way (lenet: conv2d / max_pool2d / matmul of the installed torch, batch norm
+    from var_mean; confocal: torch.erf on the separable tables, one einsum per point);
+  * confocal: the per-kernel split comes from the device, in a run of its own: ``--loop N`` runs N bare evaluations and
+    nothing else, for ``rocprofv3 --kernel-trace --stats -- python scripts/step_bench.py --problem confocal --loop 2000``.
+
+    python scripts/step_bench.py --problem {mnist_conv,cifar_conv,lenet} [--batch 128] [--iters 200] [--unroll 20] [--unrolls 10]
+    python scripts/step_bench.py --problem confocal [--batch 32] [--points 5] [--roi 28] [--iters 500] [--unroll 20]
+                                 [--unrolls 10] [--loop N]
+
+Prints one JSON line.  The image nets run on synthetic data (problems.synthetic_mnist / synthetic_cifar10); the arithmetic
+does not depend on it."""
+import argparse
+import functools
+import json
+import math
+import os
+import sys
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+from open_l2o_amd import _engine, meta, problems, util  # noqa: E402
+from open_l2o_amd.session import Session  # noqa: E402
+
+_CONV_SHAPES = [(16,), (16,), (16,), (5, 5, 16, 32), (32,), (32,), (32,)]
+# per image net: its data, descriptor and engine method, the variable shapes with batch norm, and which of them start at
+# a constant (gamma at 1; LeNet's batch norm has only an offset, at 0)
+IMAGE_NETS = {
+    "mnist_conv": types.SimpleNamespace(
+        data=problems.synthetic_mnist, desc=_engine.MnistConvDesc, fg="mnist_conv_fg", const=((2, 6), 1.0),
+        shapes=[(3, 3, 1, 16)] + _CONV_SHAPES + [(512, 10), (10,)]),
+    "cifar_conv": types.SimpleNamespace(
+        data=problems.synthetic_cifar10, desc=_engine.CifarConvDesc, fg="cifar_conv_fg", const=((2, 6), 1.0),
+        shapes=[(3, 3, 3, 16)] + _CONV_SHAPES + [(32, 10), (10,)]),
+    "lenet": types.SimpleNamespace(
+        data=problems.synthetic_cifar10, desc=_engine.LenetDesc, fg="lenet_fg", const=((2, 5, 8, 11), 0.0),
+        shapes=[(5, 5, 3, 6), (6,), (6,), (5, 5, 6, 16), (16,), (16,), (400, 120), (120,), (120,), (120, 84), (84,), (84,),
+                (84, 10), (10,)]),
+}
+
+
+def _timed(fn, iters, warmup=20):
+    for _ in range(warmup):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return 1e3 * e0.elapsed_time(e1) / iters
+
+
+def time_step(config, options, T, unrolls, warmup=2):
+    problem, net_config, na = util.get_config(config, problem_options=options)
+    optimizer = meta.MetaOptimizer(**net_config)
+    ml = optimizer.meta_loss(problem, T, net_assignments=na)
+    graph = optimizer.graph
+    times = []
+    with Session() as sess:
+        sess.run(ml.reset)
+        for k in range(warmup + unrolls):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            graph.launch({}, commit=True, events=(e0, e1))
+            e1.synchronize()
+            if k >= warmup:
+                times.append(1e3 * e0.elapsed_time(e1) / T)
+    return float(np.median(times)), graph
+
+
+# -- the image nets ----------------------------------------------------------------------------------------------------
+def image_net_fg(eng, net, data, batch):
+    """One evaluation as a callable, its loss buffer, and the minibatch and weights on the host (for the yardstick)."""
+    images = np.ascontiguousarray(data["images"], np.float32).reshape(len(data["labels"]), -1)
+    d = net.desc(batch, True, eng.tensor(images), eng.int_tensor(data["labels"]))
+    rng = np.random.default_rng(0)
+    rows = rng.integers(0, len(images), batch)
+    idx = eng.int_tensor(rows)
+    w = [rng.normal(0, 0.01, sh).astype(np.float32) for sh in net.shapes]
+    for k in net.const[0]:
+        w[k][:] = net.const[1]
+    ws = [eng.tensor(a) for a in w]
+    grads = [eng.zeros(*sh) for sh in net.shapes]
+    loss = eng.zeros(1)
+    fg = functools.partial(getattr(eng, net.fg), d, idx, ws, loss, grads)
+    return fg, loss, (images[rows], np.asarray(data["labels"])[rows], w)
+
+
+def lenet_torch(x, y, w, iters):
+    """LeNet through float32 torch autograd on the GPU."""
+    dev = torch.device("cuda")
+    x = torch.tensor(x, device=dev).reshape(-1, 32, 32, 3).permute(0, 3, 1, 2).contiguous()
+    y = torch.tensor(y, device=dev, dtype=torch.int64)
+    vs = [torch.tensor(a, device=dev).requires_grad_(True) for a in w]
+    out = {}
+
+    def bn(h, dims, beta):                  # batch statistics, biased variance, an offset and no scale
+        var, mean = torch.var_mean(h, dims, unbiased=False, keepdim=True)
+        return (h - mean) * torch.rsqrt(var + 1e-3) + beta
+
+    def fg():
+        h = x
+        for k in (0, 3):
+            h = F.conv2d(h, vs[k].permute(3, 2, 0, 1)) + vs[k + 1].view(1, -1, 1, 1)
+            h = F.max_pool2d(torch.sigmoid(bn(h, (0, 2, 3), vs[k + 2].view(1, -1, 1, 1))), 2, 2)
+        h = h.permute(0, 2, 3, 1).reshape(h.shape[0], -1)
+        for k in (6, 9):
+            h = torch.sigmoid(bn(h @ vs[k] + vs[k + 1], (0,), vs[k + 2]))
+        loss = F.cross_entropy(h @ vs[12] + vs[13], y)
+        out["loss"], out["grads"] = loss, torch.autograd.grad(loss, vs)
+
+    us = _timed(fg, iters)
+    return us, float(out["loss"])
+
+
+def image_net_main(eng, a):
+    net = IMAGE_NETS[a.problem]
+    data = net.data(4096, seed=0)
+    fg, loss, (x, y, w) = image_net_fg(eng, net, data, a.batch)
+    fg_us = _timed(fg, a.iters)
+    yardstick = {}
+    if a.problem == "lenet":
+        torch_us, torch_loss = lenet_torch(x, y, w, a.iters)
+        yardstick = {"torch_autograd_fg_us": round(torch_us, 2), "loss": float(eng.to_numpy(loss)[0]), "torch_loss": torch_loss}
+    step_us, graph = time_step(a.problem, {"data": data, "batch_size": a.batch}, a.unroll, a.unrolls)
+    return {"workload": a.problem, "batch": a.batch, "coordinates": sum(int(np.prod(v.shape)) for v in graph.x),
+            "fg_us": round(fg_us, 2), **yardstick, "step_us": round(step_us, 2), "unroll": a.unroll, "path": graph.last_path,
+            "device": torch.cuda.get_device_name(0)}
+
+
+# -- confocal ----------------------------------------------------------------------------------------------------------
+def confocal_fg(eng, batch, points, roi, want_grad=True):
+    rng = np.random.default_rng(0)
+    nv = 6 * points + 1
+    theta = [rng.random(batch).astype(np.float32) for _ in range(nv)]
+    sim = [rng.random(batch).astype(np.float32) for _ in range(nv)]
+    d = _engine.ConfocalDesc(batch, points, roi)
+    th, sm = [eng.tensor(a) for a in theta], [eng.tensor(a) for a in sim]
+    grads = [eng.zeros(batch) for _ in theta] if want_grad else None
+    loss = eng.zeros(1)
+    return (lambda: eng.confocal_fg(d, th, sm, loss, grads)), loss, (theta, sim)
+
+
+def confocal_torch(theta, sim, points, roi, iters):
+    """The confocal loss and gradients through float32 torch autograd on the GPU."""
+    dev = torch.device("cuda")
+    vs = [torch.tensor(a, device=dev).requires_grad_(True) for a in theta]
+    ss = [torch.tensor(a, device=dev) for a in sim]
+    ks = [torch.arange(r, device=dev, dtype=torch.float32)[None, :] for r in roi]
+    out = {}
+
+    def axis(c, sg, k):
+        den = math.sqrt(2.0) * sg[:, None]
+        return torch.erf((k + 0.5 - c[:, None]) / den) - torch.erf((k - 0.5 - c[:, None]) / den)
+
+    def volume(v):
+        vol = v[6 * points][:, None, None, None]
+        for p in range(points):
+            t_i, t_x, t_y, t_z, t_sxy, t_sz = v[6 * p:6 * p + 6]
+            sxy, sz = 2.0 + 2.0 * t_sxy, 2.0 + 2.0 * t_sz
+            ex = axis(0.5 + (roi[0] - 1.5) * t_x, sxy, ks[0])
+            ey = axis(0.5 + (roi[1] - 1.5) * t_y, sxy, ks[1])
+            ez = axis(0.5 + (roi[2] - 1.5) * t_z, sz, ks[2])
+            vol = vol + torch.einsum("b,by,bx,bz->byxz", (0.5 + 1.5 * t_i) / 8.0, ey, ex, ez)
+        return vol.reshape(vol.shape[0], -1)
+
+    def fg():
+        t = volume(ss)
+        target = t * torch.rsqrt(torch.clamp((t * t).sum(1, keepdim=True), min=1e-12))
+        loss = ((volume(vs) - target) ** 2).sum(1).mean()
+        out["loss"], out["grads"] = loss, torch.autograd.grad(loss, vs)
+
+    us = _timed(fg, iters)
+    return us, float(out["loss"].detach())
+
+
+def confocal_main(eng, a):
+    roi = (a.roi, a.roi, a.roi)
+    fg, loss, (theta, sim) = confocal_fg(eng, a.batch, a.points, roi)
+    if a.loop:
+        for _ in range(a.loop):
+            fg()
+        torch.cuda.synchronize()
+        return {"workload": "confocal_microscopy_3d", "loop": a.loop, "loss": float(eng.to_numpy(loss)[0])}
+    fg_us = _timed(fg, a.iters)
+    f_us = _timed(confocal_fg(eng, a.batch, a.points, roi, want_grad=False)[0], a.iters)
+    torch_us, torch_loss = confocal_torch(theta, sim, a.points, roi, a.iters)
+    calls = [0]
+    orig_fg = eng.confocal_fg
+
+    def counted(*args, **kw):
+        calls[0] += 1
+        return orig_fg(*args, **kw)
+    eng.confocal_fg = counted
+    step_us, graph = time_step("confocal_microscopy_3d", {"batch_size": a.batch, "num_points": a.points, "ROI": list(roi)},
+                               a.unroll, a.unrolls)
+    del eng.confocal_fg
+    assert calls[0] == (2 + a.unrolls) * (a.unroll + 1)
+    nvar = len(graph.x)
+    lstm_launches = -(-nvar // eng.MAX_STEP_SEGS)            # l2o_cwlstm_step_multi takes MAX_STEP_SEGS variables per launch
+    return {"workload": "confocal_microscopy_3d", "batch": a.batch, "points": a.points, "roi": list(roi),
+            "variables": nvar, "fg_us": round(fg_us, 2), "forward_only_us": round(f_us, 2),
+            "torch_autograd_fg_us": round(torch_us, 2), "loss": float(eng.to_numpy(loss)[0]),
+            "torch_loss": torch_loss, "step_us": round(step_us, 2), "unroll": a.unroll, "path": graph.last_path,
+            "launches_per_step": {"l2o_confocal_fg": 2, "l2o_cwlstm_step_multi": lstm_launches},
+            "device": torch.cuda.get_device_name(0)}
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--problem", required=True, choices=list(IMAGE_NETS) + ["confocal"])
+    p.add_argument("--batch", type=int, help="default: 128; confocal: 32")
+    p.add_argument("--iters", type=int, help="default: 200; confocal: 500")
+    p.add_argument("--unroll", type=int, default=20)
+    p.add_argument("--unrolls", type=int, default=10)
+    p.add_argument("--points", type=int, default=5, help="confocal")
+    p.add_argument("--roi", type=int, default=28, help="confocal")
+    p.add_argument("--loop", type=int, default=0, help="confocal: only run this many bare evaluations (for a kernel trace)")
+    a = p.parse_args()
+    confocal = a.problem == "confocal"
+    a.batch = a.batch or (32 if confocal else 128)
+    a.iters = a.iters or (500 if confocal else 200)
+    eng = _engine.HipEngine()
+    _engine.set_default_engine(eng)
+    meta.set_random_seed(0)
+    print(json.dumps((confocal_main if confocal else image_net_main)(eng, a)))
+
+
+if __name__ == "__main__":
+    main()
