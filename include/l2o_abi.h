@@ -130,6 +130,7 @@ int l2o_last_unroll_form(void);
 #define L2O_FORM_MLP_UNROLL_HIER 9     /* + k_mlp_unroll, fast instantiation, XCD-hierarchical all-reduce                */
 #define L2O_FORM_MLP_UNROLL_GENERIC 10 /* + k_mlp_unroll, generic loops                                                  */
 #define L2O_FORM_MLP_XCD 11            /* + k_mlp_xcd: one optimizee instance per XCD (l2o_mlp_unroll_multi)             */
+#define L2O_FORM_CONFOCAL_UNROLL 12    /* k_cf_unroll: one workgroup per batch row (l2o_confocal_unroll)                 */
 /* l2o_last_unroll_variant (added after ABI v15 and not in L2O_ABI_VERSION 15's list: test for the symbol): which
  * INSTANTIATION of that template the last l2o_unroll / l2o_unroll_record / l2o_unroll_reduce call of this thread launched
  * -- the template arguments below, packed; an argument the launched template does not have is 0.  Thread-local like
@@ -404,7 +405,8 @@ int l2o_lenet_fg(const l2o_lenet* net, const int32_t* indices /* device [batch] 
  * (inference = 1) row b of `img`, whose flat voxel index is (iy roi[0] + ix) roi[2] + iz (TF's meshgrid 'xy' order).
  * The step-granular evaluation only: two launches (three with inference = 1), fp32, fixed-order reductions (two calls on
  * the same inputs are bit-identical; with g == NULL -- forward only -- the loss has the same bits); stateless: nothing is
- * cached between calls; no fused unroll (l2o_unroll_supported is 0 for L2O_PROB_CONFOCAL).
+ * cached between calls.  Its fused unroll is l2o_confocal_unroll (l2o_confocal_unroll_abi.h); l2o_unroll_supported stays 0
+ * for L2O_PROB_CONFOCAL.
  * theta / g / sim: HOST arrays of 6 num_points + 1 device pointers to [batch] floats in the reference's variable order: for
  * point 0 .. num_points - 1: I, x, y, z, sigmaxy, sigmaz; then bg.  g may be NULL; sim is NULL (ignored) with inference = 1.
  * batch in [1, 1024], num_points in [1, 8], every roi edge in [2, 32], else L2O_ERR_UNSUPPORTED (nothing is launched).

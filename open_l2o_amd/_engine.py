@@ -411,10 +411,7 @@ class HipEngine(object):
         device tensors of [batch] floats in the graph's variable order (per point I, x, y, z, sigmaxy, sigmaz; then bg);
         sim is None in inference mode (d.img is the target); grads may be None: forward only."""
         entry = STEP_OPTIMIZEES[_abi.PROB_CONFOCAL]
-        c = _abi.Confocal()
-        c.batch, c.num_points, c.inference, c.flags = d.batch, d.num_points, 0 if d.img is None else 1, 0
-        c.roi[0], c.roi[1], c.roi[2] = (int(r) for r in d.roi)
-        c.img = None if d.img is None else C.c_void_p(d.img.data_ptr())
+        c = self._cconfocal(d)
         scr = self._step_scratch(entry, c)
         if scr is None:
             raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_confocal_fg: batch in [1, 1024], num_points in [1, 8], "
@@ -427,6 +424,58 @@ class HipEngine(object):
             raise ValueError("l2o_confocal_fg: every variable holds [batch] floats, img [batch, V]")
         _abi.check(self.lib.l2o_confocal_fg(C.byref(c), _ptr_array(theta), _ptr_array(sim), _ptr(loss), _ptr_array(grads),
                                             _ptr(scr), self._stream()))
+
+    def _cconfocal(self, d: ConfocalDesc):
+        c = _abi.Confocal()
+        c.batch, c.num_points, c.inference, c.flags = d.batch, d.num_points, 0 if d.img is None else 1, 0
+        c.roi[0], c.roi[1], c.roi[2] = (int(r) for r in d.roi)
+        c.img = None if d.img is None else C.c_void_p(d.img.data_ptr())
+        return c
+
+    def confocal_unroll_supported(self, spec: NetSpec, d: ConfocalDesc):
+        """A fused persistent unroll exists for this (net, confocal optimizee) pair (l2o_confocal_unroll)."""
+        cc, cm = spec.to_c(), self._cconfocal(d)
+        return int(self.lib.l2o_confocal_unroll_supported(C.byref(cc), C.byref(cm), self._stream()))
+
+    def confocal_unroll(self, spec: NetSpec, wpack, d: ConfocalDesc, xs, sts, ms, vs, scales, sim, T, step0, fx, hist=None):
+        """T optimizer steps on the confocal optimizee in ONE launch (l2o_confocal_unroll).  xs / sts / ms / vs / scales /
+        sim: lists of 6 num_points + 1 device tensors in confocal_fg's variable order (ms / vs / scales entries may be None;
+        sim is None in inference mode).  hist: None, or dict(st=, g=, m=, v=) of such lists ([T, state], [T + 1, batch],
+        [T + 1, batch] x 2; m / v None for the DM nets) that receive the history the meta-gradient needs
+        (l2o_confocal_unroll_record)."""
+        nv = 6 * d.num_points + 1
+        if any(len(ts) != nv for ts in (xs, sts, ms, vs, scales)) or ((sim is None) != (d.img is not None)) \
+                or (sim is not None and len(sim) != nv):
+            raise ValueError("l2o_confocal_unroll: %d variables for %d points" % (len(xs), d.num_points))
+        if any(t.numel() != d.batch for t in xs) or (d.img is not None and d.img.numel() != d.batch * int(np.prod(d.roi))):
+            raise ValueError("l2o_confocal_unroll: every variable holds [batch] floats, img [batch, V]")
+        cc, cm = spec.to_c(), self._cconfocal(d)
+        n = int(self.lib.l2o_confocal_unroll_scratch_floats(C.byref(cm), int(T)))
+        if not n:
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_confocal_unroll: batch in [1, 1024], num_points in [1, 8], "
+                                      "ROI edges in [2, 32] (got %d, %d, %r)" % (d.batch, d.num_points, tuple(d.roi)))
+        scr = self.__dict__.get("_confocal_unroll_scratch")
+        if scr is None or scr.numel() < n:
+            scr = self._confocal_unroll_scratch = self.empty(n)
+
+        def arr(ts, optional=False):
+            if ts is None or (optional and all(t is None for t in ts)):
+                return None
+            a = (C.c_void_p * nv)()
+            for k, t in enumerate(ts):
+                a[k] = None if t is None else _ptr(t).value
+            return a
+        args = (C.byref(cc), _ptr(wpack), C.byref(cm), arr(xs), arr(sts), arr(ms, True), arr(vs, True), arr(scales, True),
+                arr(sim), int(T), int(step0), _ptr(fx))
+        if hist is None:
+            _abi.check(self.lib.l2o_confocal_unroll(*args, _ptr(scr), self._stream()))
+            return
+        h = _abi.ConfocalHist()
+        for k in range(nv):
+            h.st[k], h.g[k] = hist["st"][k].data_ptr(), hist["g"][k].data_ptr()
+            h.m[k] = None if hist.get("m") is None or hist["m"][k] is None else hist["m"][k].data_ptr()
+            h.v[k] = None if hist.get("v") is None or hist["v"][k] is None else hist["v"][k].data_ptr()
+        _abi.check(self.lib.l2o_confocal_unroll_record(*args, C.byref(h), _ptr(scr), self._stream()))
 
     def mlp_unroll_supported(self, spec: NetSpec, d: MlpDesc):
         """A fused persistent unroll exists for this (net, MLP optimizee) pair on this device (l2o_mlp_unroll)."""

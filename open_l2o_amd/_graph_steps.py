@@ -152,6 +152,44 @@ class StepPlanMixin(object):
                 return 0
         return int(eng.mlp_unroll_supported(net.spec, self._mlp_desc(self.terms[0])))   # 2: the kernel's FAST form
 
+    def _confocal_unroll_ok(self, slots, states):
+        """l2o_confocal_unroll applies: ONE problems.confocal_microscopy_3d(fused=True) term of weight 1 whose variables are
+        all stepped by the same (20, 20) LSTM net, on an engine that has the fused kernel, for a shape the library takes."""
+        eng = self.engine
+        if not hasattr(eng, "confocal_unroll") or os.environ.get("L2O_DISABLE_FUSED") or self.sharded \
+                or self.second_derivatives:
+            return False
+        if len(self.terms) != 1 or self.terms[0].kind != _abi.PROB_CONFOCAL or self.terms[0].weight != 1.0 \
+                or not self.terms[0].hyper.get("fused"):
+            return False
+        nv = len(_term_vars(self.terms[0]))
+        if len(self.x) != nv or len(slots) != nv:
+            return False
+        net = slots[0].net
+        for s, st in zip(slots, states):
+            if s.net is not net or not isinstance(net, networks.StandardDeepLSTM) or not isinstance(st, PackedState) \
+                    or st.packed is None:
+                return False
+        return bool(eng.confocal_unroll_supported(net.spec, self._mlp_desc(self.terms[0])))
+
+    def _run_confocal_unroll(self, T, step0, panels, slots, states, ms, vs, scales, fx, record=None):
+        """The fused confocal unroll (one l2o_confocal_unroll launch); with `record`, its recording form: the history
+        buffers of _mlp_hist_plan, handed to _backward in the step path's format."""
+        eng = self.engine
+        term = self.terms[0]
+        index_of = {v.decl.name: j for j, v in enumerate(self.x)}
+        js = [index_of[tv.name] for tv in _term_vars(term)]               # the reference's variable order -> variable index
+        slot_of = {s.var_index: si for si, s in enumerate(slots)}
+        sis = [slot_of[j] for j in js]
+        net = slots[sis[0]].net
+        sim = [self._by_name[c.name].value for c in term.consts["sim"]] or None
+        plan = self._mlp_hist_plan(T, panels, slots, states, ms, vs) if record is not None else None
+        eng.confocal_unroll(net.spec, net.wpack(eng), self._mlp_desc(term), [panels[j] for j in js],
+                            [states[si].packed for si in sis], [ms[si] for si in sis], [vs[si] for si in sis],
+                            [scales[j] for j in js], sim, T, step0, fx, hist=None if plan is None else plan["hist"])
+        if record is not None:
+            record.update(g=plan["g"], st=plan["st"], m=plan["m"], v=plan["v"], g_final=plan["g_final"], plan=plan)
+
     def mlp_instance(self, feed=None, dry=False, draw=True):
         """What this graph contributes to a launch of several optimizee instances (replicas.Replicas ->
         l2o_mlp_unroll_multi): its minibatch indices (drawn here, like a launch of its own would), the live x / LSTM

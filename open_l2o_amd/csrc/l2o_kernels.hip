@@ -874,6 +874,7 @@ __global__ __launch_bounds__(CH <= 4 ? 256 : 512) void k_unroll(UnrollArgs a) {
 #include "l2o_cifar_conv.h"
 #include "l2o_lenet.h"
 #include "l2o_confocal.h"
+#include "l2o_confocal_unroll.h"
 
 #include "l2o_generic.h"
 
@@ -1292,6 +1293,16 @@ static int launch_unroll_cu(const UnrollArgs& a_in, hipStream_t s) {
   hipLaunchKernelGGL(fn, dim3(a.pp.B_local), dim3(kCuThreads), L.lds, s, a);
   note_form(L2O_FORM_UNROLL_CU);
   note_variant(0, hist, false, false, 0, a.pp.D <= 256 ? 1 : 2);
+  HIP_TRY(hipGetLastError());
+  return L2O_OK;
+}
+
+// the fused unroll of the confocal optimizee (csrc/l2o_confocal_unroll.h): one workgroup per batch row
+template <int PRE>
+static int launch_confocal_unroll(const CfUnrollArgs& a, bool hist, size_t lds, hipStream_t s) {
+  void (*fn)(CfUnrollArgs) = hist ? k_cf_unroll<PRE, true> : k_cf_unroll<PRE, false>;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(fn, dim3(a.batch), dim3(kCfThreads), lds, s, a);
   HIP_TRY(hipGetLastError());
   return L2O_OK;
 }
@@ -2340,6 +2351,89 @@ int l2o_confocal_fg(const l2o_confocal* m, const float* const* theta, const floa
   hipLaunchKernelGGL(k_cf_reduce, dim3(nred), blk, 0, s, a);
   HIP_TRY(hipGetLastError());
   return L2O_OK;
+}
+
+// ---- the fused unroll of the confocal optimizee (csrc/l2o_confocal_unroll.h) ----------------------------------------------
+static bool confocal_unroll_ok(const l2o_net_cfg* cfg, const l2o_confocal* m) {
+  return cfg && net_ok_for_mfma(cfg) && confocal_ok(m);
+}
+int l2o_confocal_unroll_supported(const l2o_net_cfg* cfg, const l2o_confocal* m, void* /*stream*/) {
+  return confocal_unroll_ok(cfg, m) ? 1 : 0;
+}
+// fx_part [T + 1][batch] (rounded up to whole pointers), then the history pointer table of a recording launch
+static size_t confocal_unroll_fx_floats(const l2o_confocal* m, int T) { return (((size_t)T + 1) * m->batch + 1) & ~(size_t)1; }
+size_t l2o_confocal_unroll_scratch_floats(const l2o_confocal* m, int32_t T) {
+  if (!confocal_ok(m) || T < 0) return 0;
+  return confocal_unroll_fx_floats(m, T) + 2 * 4 * (size_t)kCfMaxVars;
+}
+static int confocal_unroll_launch(const char* who, const l2o_net_cfg* cfg, const float* wpack, const l2o_confocal* m,
+                                  float* const* x, float* const* st, float* const* mm, float* const* vv,
+                                  const float* const* x_scale, const float* const* sim, int32_t T, int32_t step0, float* fx,
+                                  const l2o_confocal_hist* hist, float* scratch, void* stream) {
+  if (!confocal_unroll_ok(cfg, m))
+    return fail(L2O_ERR_UNSUPPORTED, "%s: the (20, 20) LSTM nets; batch in [1, %d], num_points in [1, %d], roi edges in "
+                "[%d, %d], inference 0 or 1", who, kCfMaxBatch, kCfMaxPts, kCfMinEdge, kCfMaxEdge);
+  if (!wpack || !x || !st || !fx || !scratch || T < 0) return fail(L2O_ERR_ARG, "%s: NULL argument or T < 0", who);
+  if (m->inference ? !m->img : !sim) return fail(L2O_ERR_ARG, "%s: inference needs img, simulation needs sim", who);
+  const bool rn = cfg->preprocess == L2O_PRE_FC_ELU;
+  if (rn && (!mm || !vv)) return fail(L2O_ERR_ARG, "%s: RNNProp needs m and v", who);
+  const int nv = 6 * m->num_points + 1;
+  CfUnrollArgs a;
+  std::memset(&a, 0, sizeof(a));
+  CfHistPtrs hp;
+  std::memset(&hp, 0, sizeof(hp));
+  for (int k = 0; k < nv; ++k) {
+    if (!x[k] || !st[k] || (rn && (!mm[k] || !vv[k])) || (!m->inference && !sim[k]))
+      return fail(L2O_ERR_ARG, "%s: NULL buffer of variable %d", who, k);
+    a.x[k] = x[k]; a.st[k] = st[k];
+    a.m[k] = rn ? mm[k] : nullptr; a.v[k] = rn ? vv[k] : nullptr;
+    a.xs[k] = x_scale ? x_scale[k] : nullptr;
+    a.sim[k] = m->inference ? nullptr : sim[k];
+    if (hist) {
+      if (!hist->st[k] || !hist->g[k] || (rn && (!hist->m[k] || !hist->v[k])))
+        return fail(L2O_ERR_ARG, "%s: NULL history buffer of variable %d", who, k);
+      hp.p[0][k] = hist->st[k]; hp.p[1][k] = hist->g[k];
+      hp.p[2][k] = rn ? hist->m[k] : nullptr; hp.p[3][k] = rn ? hist->v[k] : nullptr;
+    }
+  }
+  a.np = make_net_params(cfg, wpack);
+  a.batch = m->batch; a.P = m->num_points; a.rx = m->roi[0]; a.ry = m->roi[1]; a.rz = m->roi[2];
+  a.inference = m->inference; a.T = T;
+  a.rb = 1.0f / (float)m->batch;
+  pow_ff(cfg->beta1, step0, &a.p1_hi, &a.p1_lo);
+  pow_ff(cfg->beta2, step0, &a.p2_hi, &a.p2_lo);
+  a.img = m->inference ? m->img : nullptr;
+  a.fx_part = scratch;
+  float** tab = reinterpret_cast<float**>(scratch + confocal_unroll_fx_floats(m, T));
+  a.htab = hist ? tab : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  if (hist) hipLaunchKernelGGL(k_cf_hist_table, dim3(1), dim3(256), 0, s, hp, tab);
+  const size_t lds = sizeof(float) * (size_t)a.rx * a.ry * a.rz;
+  int rc;
+  switch (cfg->preprocess) {
+    case L2O_PRE_IDENTITY: rc = launch_confocal_unroll<L2O_PRE_IDENTITY>(a, hist != nullptr, lds, s); break;
+    case L2O_PRE_LOGSIGN: rc = launch_confocal_unroll<L2O_PRE_LOGSIGN>(a, hist != nullptr, lds, s); break;
+    default: rc = launch_confocal_unroll<L2O_PRE_FC_ELU>(a, hist != nullptr, lds, s);
+  }
+  if (rc != L2O_OK) return rc;
+  hipLaunchKernelGGL(k_reduce_fx, dim3(T + 1), dim3(64), 0, s, a.fx_part, (int)(T + 1), (int)a.batch, a.rb, fx);
+  HIP_TRY(hipGetLastError());
+  note_form(L2O_FORM_CONFOCAL_UNROLL);
+  return L2O_OK;
+}
+int l2o_confocal_unroll(const l2o_net_cfg* cfg, const float* wpack, const l2o_confocal* m, float* const* x, float* const* st,
+                        float* const* mm, float* const* vv, const float* const* x_scale, const float* const* sim, int32_t T,
+                        int32_t step0, float* fx, float* scratch, void* stream) {
+  return confocal_unroll_launch("l2o_confocal_unroll", cfg, wpack, m, x, st, mm, vv, x_scale, sim, T, step0, fx, nullptr,
+                                scratch, stream);
+}
+int l2o_confocal_unroll_record(const l2o_net_cfg* cfg, const float* wpack, const l2o_confocal* m, float* const* x,
+                               float* const* st, float* const* mm, float* const* vv, const float* const* x_scale,
+                               const float* const* sim, int32_t T, int32_t step0, float* fx, const l2o_confocal_hist* hist,
+                               float* scratch, void* stream) {
+  if (!hist) return fail(L2O_ERR_ARG, "l2o_confocal_unroll_record: NULL hist");
+  return confocal_unroll_launch("l2o_confocal_unroll_record", cfg, wpack, m, x, st, mm, vv, x_scale, sim, T, step0, fx, hist,
+                                scratch, stream);
 }
 
 #ifndef L2O_MLP_XCD_DEFAULT_FOUR

@@ -519,6 +519,13 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
             self._run_mlp_unroll_record(T, step0, panels, slots, states, ms, vs, scales, fx, record)
             if events is not None:
                 events[1].record()
+        elif record is not None and self._confocal_unroll_ok(slots, states):
+            # meta-gradient on the confocal optimizee (fused=True): the T steps and their history in ONE launch
+            self.last_path = "confocal_unroll"
+            record.update(step0=step0, shapes=[tuple(pn.shape) for pn in panels])
+            self._run_confocal_unroll(T, step0, panels, slots, states, ms, vs, scales, fx, record=record)
+            if events is not None:
+                events[1].record()
         elif record is not None:                           # meta-gradient: needs the per-step history
             self.last_path = "steps"
             self._draw_minibatches(T)
@@ -558,6 +565,13 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
             eng.mlp_unroll(net.spec, net.wpack(eng), self._mlp_desc(term), self._mlp_idx[0],
                            [panels[j] for j in js], [states[si].packed for si in sis], [ms[si] for si in sis],
                            [vs[si] for si in sis], [scales[j] for j in js], T, step0, fx)
+            if events is not None:
+                events[1].record()
+        elif self._confocal_unroll_ok(slots, states):
+            # the confocal optimizee (fused=True), every variable stepped by one LSTM net: one workgroup per batch row runs
+            # the T steps in ONE launch (no workgroup waits for another: no status word)
+            self.last_path = "confocal_unroll"
+            self._run_confocal_unroll(T, step0, panels, slots, states, ms, vs, scales, fx)
             if events is not None:
                 events[1].record()
         else:

@@ -514,7 +514,7 @@ def LeNet(path, conv_channels=None, linear_layers=None, batch_norm=True, batch_s
 
 
 def confocal_microscopy_3d(batch_size=128, num_points=5, ROI=[28, 28, 28], stddev=0.01, dtype="float32", inference=False,
-                           data=None):
+                           data=None, fused=False):
     """3-D point-spread-function fitting.  DM/problems.py:701-956 (util.get_config: batch_size=32, num_points=5).
 
     Per batch row, ``num_points`` Gaussian point-spread functions, each integrated over the voxels of the ``ROI`` = [Rx, Ry,
@@ -523,7 +523,11 @@ def confocal_microscopy_3d(batch_size=128, num_points=5, ROI=[28, 28, 28], stdde
     1.5 t, c = 0.5 + (R - 1.5) t per axis, sigma_xy = sigma_z = 2 + 2 t (the quantiles of uniform priors, not clipped).
     loss = mean_b sum_v (pred - l2_normalize(target))^2, the target being the same sum over the non-trainable ``*_sim``
     variables (re-drawn on every reset), or with ``inference=True`` a supplied volume.  Forward and gradient:
-    l2o_confocal_fg (the step-granular path; no fused unroll).
+    l2o_confocal_fg (the step-granular path, the default).
+
+    ``fused`` (an extension, default off): where one (20, 20) LSTM net steps every variable, run the unroll as ONE persistent
+    launch (l2o_confocal_unroll: one workgroup per batch row) instead of the step-granular launches; the graph falls back
+    to those wherever the fused form does not apply (``last_path`` tells which ran).
 
     Variables as the reference declares them, each [batch_size, 1]: per point I_var_i, x_var_i, y_var_i, z_var_i,
     sigmaxy_var_i, sigmaz_var_i ~ U[0, 1); then per point the non-trainable I_sim_i, x_sim_i, y_simi (the reference's
@@ -562,7 +566,8 @@ def confocal_microscopy_3d(batch_size=128, num_points=5, ROI=[28, 28, 28], stdde
         tr.append(var("bg_var", random_normal_initializer(stddev=stddev), True))
         if not inference:
             sim.append(var("bg_sim", random_uniform_initializer(), False))
-        hyper = {"batch_size": batch_size, "num_points": num_points, "roi": roi, "inference": inference, "img": img}
+        hyper = {"batch_size": batch_size, "num_points": num_points, "roi": roi, "inference": inference, "img": img,
+                 "fused": bool(fused)}
         return [Term(_abi.PROB_CONFOCAL, tuple(tr), {"sim": tuple(sim)}, hyper, 1.0)]
 
     return _Build("confocal_microscopy_3d", build)

@@ -57,6 +57,8 @@ def parse_flags(rnnprop):
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--batch_size", type=int, default=None)
     p.add_argument("--num_dims", type=int, default=None)
+    p.add_argument("--confocal_fused", type=int, choices=(0, 1), default=0,
+                   help="(ours) --problem confocal_microscopy_3d: 1 runs the unroll as one persistent launch (problems.confocal_microscopy_3d(fused=True))")
     p.add_argument("--num_rows", type=int, default=None, help="lasso: rows of the sensing matrix (default: num_dims)")
     p.add_argument("--l", type=float, default=None, help="lasso: l1 weight (DM/problems.py:103 default 0.005)")
     p.add_argument("--max_seconds", type=float, default=None,
@@ -92,6 +94,8 @@ class Trainer(object):
         opts = {k: v for k, v in (("batch_size", flags.batch_size), ("num_dims", flags.num_dims),
                                   ("num_rows", getattr(flags, "num_rows", None)), ("l", getattr(flags, "l", None)))
                 if v is not None}
+        if getattr(flags, "confocal_fused", 0):
+            opts["fused"] = True
         if getattr(flags, "synthetic_mnist", 0):
             from open_l2o_amd import problems
             opts["data"] = problems.synthetic_mnist(flags.synthetic_mnist, seed=getattr(flags, "synthetic_seed", 0),

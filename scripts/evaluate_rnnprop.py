@@ -29,6 +29,8 @@ def main():
     flags.add_argument("--unroll_len", type=int, default=1)
     flags.add_argument("--batch_size", type=int, default=None)
     flags.add_argument("--num_dims", type=int, default=None)
+    flags.add_argument("--confocal_fused", type=int, choices=(0, 1), default=0,
+                       help="(ours) --problem confocal_microscopy_3d: 1 runs the unroll as one persistent launch (problems.confocal_microscopy_3d(fused=True))")
     flags.add_argument("--synthetic_mnist", type=int, default=0,
                        help="problems.mnist on N synthetic MNIST-shaped examples (no dataset ships offline)")
     flags.add_argument("--synthetic_cifar10", type=int, default=0,
@@ -45,6 +47,8 @@ def main():
     if FLAGS.seed:
         meta.set_random_seed(FLAGS.seed)
     opts = {k: v for k, v in (("batch_size", FLAGS.batch_size), ("num_dims", FLAGS.num_dims)) if v is not None}
+    if FLAGS.confocal_fused:
+        opts["fused"] = True
     if FLAGS.synthetic_mnist:
         from open_l2o_amd import problems
         opts["data"] = problems.synthetic_mnist(FLAGS.synthetic_mnist)

@@ -12,7 +12,7 @@
     nothing else, for ``rocprofv3 --kernel-trace --stats -- python scripts/step_bench.py --problem confocal --loop 2000``.
 
     python scripts/step_bench.py --problem {mnist_conv,cifar_conv,lenet} [--batch 128] [--iters 200] [--unroll 20] [--unrolls 10]
-    python scripts/step_bench.py --problem confocal [--batch 32] [--points 5] [--roi 28] [--iters 500] [--unroll 20]
+    python scripts/step_bench.py --problem confocal [--batch 32] [--points 5] [--roi 28] [--iters 500] [--unroll 20] [--fused 1]
                                  [--unrolls 10] [--loop N]
 
 Prints one JSON line.  The image nets run on synthetic data (problems.synthetic_mnist / synthetic_cifar10); the arithmetic
@@ -210,12 +210,17 @@ def confocal_main(eng, a):
                                a.unroll, a.unrolls)
     del eng.confocal_fg
     assert calls[0] == (2 + a.unrolls) * (a.unroll + 1)
+    fused = {}
+    if a.fused:                                              # the same unroll as ONE launch, timed in the same process
+        fused_us, fgraph = time_step("confocal_microscopy_3d", {"batch_size": a.batch, "num_points": a.points, "ROI": list(roi),
+                                                                "fused": True}, a.unroll, a.unrolls)
+        fused = {"fused_step_us": round(fused_us, 2), "fused_path": fgraph.last_path}
     nvar = len(graph.x)
     lstm_launches = -(-nvar // eng.MAX_STEP_SEGS)            # l2o_cwlstm_step_multi takes MAX_STEP_SEGS variables per launch
     return {"workload": "confocal_microscopy_3d", "batch": a.batch, "points": a.points, "roi": list(roi),
             "variables": nvar, "fg_us": round(fg_us, 2), "forward_only_us": round(f_us, 2),
             "torch_autograd_fg_us": round(torch_us, 2), "loss": float(eng.to_numpy(loss)[0]),
-            "torch_loss": torch_loss, "step_us": round(step_us, 2), "unroll": a.unroll, "path": graph.last_path,
+            "torch_loss": torch_loss, "step_us": round(step_us, 2), "unroll": a.unroll, "path": graph.last_path, **fused,
             "launches_per_step": {"l2o_confocal_fg": 2, "l2o_cwlstm_step_multi": lstm_launches},
             "device": torch.cuda.get_device_name(0)}
 
@@ -229,6 +234,8 @@ def main():
     p.add_argument("--unrolls", type=int, default=10)
     p.add_argument("--points", type=int, default=5, help="confocal")
     p.add_argument("--roi", type=int, default=28, help="confocal")
+    p.add_argument("--fused", type=int, choices=(0, 1), default=0,
+                   help="confocal: 1 also times the fused unroll (fused_step_us) beside the step path (step_us)")
     p.add_argument("--loop", type=int, default=0, help="confocal: only run this many bare evaluations (for a kernel trace)")
     a = p.parse_args()
     confocal = a.problem == "confocal"
