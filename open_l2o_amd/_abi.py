@@ -41,6 +41,9 @@ SYMBOLS = (
 # ... and every symbol include/l2o_confocal_unroll_abi.h declares (the fused confocal unroll, added after ABI v15)
 CONFOCAL_UNROLL_SYMBOLS = ("l2o_confocal_unroll", "l2o_confocal_unroll_record", "l2o_confocal_unroll_supported",
                            "l2o_confocal_unroll_scratch_floats")
+# ... and include/l2o_confocal_multi_abi.h (several confocal instances per fused launch); bound when the library has them
+CONFOCAL_MULTI_SYMBOLS = ("l2o_confocal_unroll_multi", "l2o_confocal_unroll_multi_record",
+                          "l2o_confocal_unroll_multi_supported", "l2o_confocal_unroll_multi_scratch_floats")
 
 
 # option ids of include/l2o_abi.h ("options": per call, caller-owned -- the LIBRARY keeps no option state since ABI v9).
@@ -57,7 +60,8 @@ OPT_DEFAULTS = {OPT_PAIR: 1, OPT_PAIR_PLAIN_STORES: 1, OPT_UNROLL_CU: 1, OPT_FG_
 # l2o_last_unroll_form(): which kernel a fused launch ran (include/l2o_abi.h L2O_FORM_*)
 FORM_NAMES = {1: "k_unroll", 2: "k_unroll_pair", 5: "k_unroll_lds", 6: "k_unroll_cu", 7: "k_unroll_cu8",
               8: "k_mlp_unroll (flat all-reduce)", 9: "k_mlp_unroll (XCD-hierarchical all-reduce)", 10: "k_mlp_unroll (generic loops)",
-              11: "k_mlp_xcd (one optimizee instance per XCD)", 12: "k_cf_unroll (one workgroup per batch row)"}
+              11: "k_mlp_xcd (one optimizee instance per XCD)", 12: "k_cf_unroll (one workgroup per batch row)",
+              13: "k_cf_unroll (several instances per launch: one workgroup per row of every instance)"}
 FORMS_WITH_EXCHANGE = (2, 8, 9, 10, 11)    # workgroups wait for partner workgroups: can end in L2OPartnerTimeout
 PROB_FG_TWO_PASS = 2      # l2o_problem.flags
 MLP_GENERIC = 1           # l2o_mlp.flags
@@ -207,6 +211,14 @@ class ConfocalHist(C.Structure):       # l2o_confocal_hist: per variable history
                 ("m", C.c_void_p * CONFOCAL_MAX_VARS), ("v", C.c_void_p * CONFOCAL_MAX_VARS)]
 
 
+CONFOCAL_MAX_INSTANCES = 32     # L2O_CONFOCAL_MAX_INSTANCES
+
+
+class ConfocalInstance(C.Structure):   # l2o_confocal_instance: one replica of l2o_confocal_unroll_multi
+    _fields_ = [(n, C.c_void_p * CONFOCAL_MAX_VARS) for n in ("x", "st", "m", "v", "x_scale", "sim")] + \
+               [("img", C.c_void_p), ("fx", C.c_void_p)]
+
+
 class MlpInstance(C.Structure):        # l2o_mlp_instance: one replica of l2o_mlp_unroll_multi
     _fields_ = [("indices", C.c_void_p), ("x", C.c_void_p * 4), ("st", C.c_void_p * 4), ("m", C.c_void_p * 4),
                 ("v", C.c_void_p * 4), ("x_scale", C.c_void_p * 4), ("fx", C.c_void_p)]
@@ -292,7 +304,7 @@ def source_build_id():
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     names = ["l2o_kernels.hip", "l2o_kernels_ilp.hip", "Makefile", "../../include/l2o_abi.h",
-             "../../include/l2o_confocal_unroll_abi.h"] + [
+             "../../include/l2o_confocal_unroll_abi.h", "../../include/l2o_confocal_multi_abi.h"] + [
         os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.h"))]
     h = hashlib.sha256()
     try:
@@ -377,6 +389,17 @@ def lib():
     L.l2o_confocal_unroll_record.restype = C.c_int
     L.l2o_confocal_unroll_record.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Confocal), vp, vp, vp, vp, vp, vp, i32, i32, vp,
                                              C.POINTER(ConfocalHist), vp, vp]
+    if all(hasattr(L, name) for name in CONFOCAL_MULTI_SYMBOLS):
+        L.l2o_confocal_unroll_multi_supported.restype = C.c_int
+        L.l2o_confocal_unroll_multi_supported.argtypes = [C.POINTER(NetCfg), C.POINTER(Confocal), i32, vp]
+        L.l2o_confocal_unroll_multi_scratch_floats.restype = C.c_size_t
+        L.l2o_confocal_unroll_multi_scratch_floats.argtypes = [C.POINTER(Confocal), i32, i32]
+        L.l2o_confocal_unroll_multi.restype = C.c_int
+        L.l2o_confocal_unroll_multi.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Confocal), C.POINTER(ConfocalInstance), i32,
+                                                i32, i32, vp, vp]
+        L.l2o_confocal_unroll_multi_record.restype = C.c_int
+        L.l2o_confocal_unroll_multi_record.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Confocal),
+                                                       C.POINTER(ConfocalInstance), i32, i32, i32, C.POINTER(ConfocalHist), vp, vp]
     L.l2o_mlp_unroll_supported.restype = C.c_int
     L.l2o_mlp_unroll_supported.argtypes = [C.POINTER(NetCfg), C.POINTER(Mlp), vp]
     L.l2o_mlp_unroll_workspace_bytes.restype = C.c_size_t

@@ -477,6 +477,65 @@ class HipEngine(object):
             h.v[k] = None if hist.get("v") is None or hist["v"][k] is None else hist["v"][k].data_ptr()
         _abi.check(self.lib.l2o_confocal_unroll_record(*args, C.byref(h), _ptr(scr), self._stream()))
 
+    def confocal_unroll_multi_supported(self, spec: NetSpec, d: ConfocalDesc, n_inst):
+        """l2o_confocal_unroll_multi applies: up to CONFOCAL_MAX_INSTANCES confocal instances of one shape in one launch."""
+        if not hasattr(self.lib, "l2o_confocal_unroll_multi"):
+            return False
+        cc, cm = spec.to_c(), self._cconfocal(d)
+        return bool(self.lib.l2o_confocal_unroll_multi_supported(C.byref(cc), C.byref(cm), int(n_inst), self._stream()))
+
+    def confocal_unroll_multi(self, spec: NetSpec, wpack, d: ConfocalDesc, insts, T, step0, hists=None):
+        """T optimizer steps on up to CONFOCAL_MAX_INSTANCES independent instances of the confocal optimizee in ONE launch,
+        one workgroup per row of every instance (l2o_confocal_unroll_multi).  insts: list of dicts(xs=, sts=, ms=, vs=,
+        scales=, sim=, img=, fx=) as the arguments of confocal_unroll (sim None in inference mode, where img is THAT
+        instance's target; d.img is ignored); all instances share the network, the shape d and T / step0.  hists: None, or
+        one history dict per instance as confocal_unroll's `hist` (l2o_confocal_unroll_multi_record)."""
+        if not hasattr(self.lib, "l2o_confocal_unroll_multi"):
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "libl2o_hip.so has no l2o_confocal_unroll_multi")
+        nv = 6 * d.num_points + 1
+        inference = d.img is not None
+        V = int(np.prod(d.roi))
+        for i in insts:
+            if any(len(i[k]) != nv for k in ("xs", "sts", "ms", "vs", "scales")) \
+                    or (i.get("sim") is None) != inference or (not inference and len(i["sim"]) != nv):
+                raise ValueError("l2o_confocal_unroll_multi: %d variables for %d points" % (len(i["xs"]), d.num_points))
+            if any(t is not None and t.numel() != d.batch for t in i["xs"]) \
+                    or (inference and (i.get("img") is None or i["img"].numel() != d.batch * V)):
+                raise ValueError("l2o_confocal_unroll_multi: every variable holds [batch] floats, img [batch, V]")
+        if hists is not None and len(hists) != len(insts):
+            raise ValueError("l2o_confocal_unroll_multi: one history per instance")
+        cc, cm = spec.to_c(), self._cconfocal(d)
+        n = int(self.lib.l2o_confocal_unroll_multi_scratch_floats(C.byref(cm), len(insts), int(T)))
+        if not n:
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_confocal_unroll_multi: batch in [1, 1024], num_points in "
+                                      "[1, 8], ROI edges in [2, 32], 1 to %d instances (got %d, %d, %r, %d)"
+                                      % (_abi.CONFOCAL_MAX_INSTANCES, d.batch, d.num_points, tuple(d.roi), len(insts)))
+        scr = self.__dict__.get("_confocal_multi_scratch")
+        if scr is None or scr.numel() < n:
+            scr = self._confocal_multi_scratch = self.empty(n)
+
+        def ptr(t):
+            return None if t is None else _ptr(t).value
+        arr = (_abi.ConfocalInstance * len(insts))()
+        for j, i in enumerate(insts):
+            arr[j].fx = ptr(i["fx"])
+            arr[j].img = ptr(i.get("img")) if inference else None
+            for k in range(nv):
+                arr[j].x[k], arr[j].st[k] = ptr(i["xs"][k]), ptr(i["sts"][k])
+                arr[j].m[k], arr[j].v[k], arr[j].x_scale[k] = ptr(i["ms"][k]), ptr(i["vs"][k]), ptr(i["scales"][k])
+                arr[j].sim[k] = None if inference else ptr(i["sim"][k])
+        args = (C.byref(cc), _ptr(wpack), C.byref(cm), arr, len(insts), int(T), int(step0))
+        if hists is None:
+            _abi.check(self.lib.l2o_confocal_unroll_multi(*args, _ptr(scr), self._stream()))
+            return
+        harr = (_abi.ConfocalHist * len(hists))()
+        for j, h in enumerate(hists):
+            for k in range(nv):
+                harr[j].st[k], harr[j].g[k] = h["st"][k].data_ptr(), h["g"][k].data_ptr()
+                harr[j].m[k] = None if h.get("m") is None or h["m"][k] is None else h["m"][k].data_ptr()
+                harr[j].v[k] = None if h.get("v") is None or h["v"][k] is None else h["v"][k].data_ptr()
+        _abi.check(self.lib.l2o_confocal_unroll_multi_record(*args, harr, _ptr(scr), self._stream()))
+
     def mlp_unroll_supported(self, spec: NetSpec, d: MlpDesc):
         """A fused persistent unroll exists for this (net, MLP optimizee) pair on this device (l2o_mlp_unroll)."""
         cc, cm = spec.to_c(), self._cmlp(d)

@@ -227,6 +227,41 @@ class StepPlanMixin(object):
                     sts=[states[si].packed for si in sis], ms=[slots[si].m for si in sis], vs=[slots[si].v for si in sis],
                     scales=[None] * 4, fx=ring["bufs"][0])
 
+    def confocal_instance(self, feed=None, dry=False):
+        """mlp_instance's counterpart for problems.confocal_microscopy_3d(fused=True) (replicas.Replicas ->
+        l2o_confocal_unroll_multi): the live x / LSTM state / moment buffers in the term's variable order, the live *_sim
+        constants (None in inference mode, where `img` is this instance's target) and the loss buffer -- or None when the
+        fused confocal unroll does not apply to this graph.  dry: no buffers -- only whether it applies."""
+        self._ensure_init()
+        T = self.len_unroll
+        feed = feed or {}
+        if any(ph in feed for ph in self.scale):
+            return None
+        slots = self.slots
+        states = [s.state for s in slots]
+        if not self._confocal_unroll_ok(slots, states):
+            return None
+        term = self.terms[0]
+        net = slots[0].net
+        desc = self._mlp_desc(term)
+        if dry:
+            return dict(net=net, desc=desc)
+        if self.rnnprop and self.step not in feed:
+            raise ValueError("You must feed a value for placeholder 'step' (DM/util.py:59-60)")
+        index_of = {v.decl.name: j for j, v in enumerate(self.x)}
+        js = [index_of[tv.name] for tv in _term_vars(term)]               # the reference's variable order -> variable index
+        slot_of = {s.var_index: si for si, s in enumerate(slots)}
+        sis = [slot_of[j] for j in js]
+        panels = [v.value.view(*self._panel_shape(v)) for v in self.x]
+        sim = [self._by_name[c.name].value for c in term.consts["sim"]] or None
+        ring = self._fx_cache.get(T)
+        if ring is None:
+            store = self.engine.zeros(1, T + 1)
+            ring = self._fx_cache[T] = {"store": store, "bufs": [store[0]], "work": [None], "i": 0, "pending": []}
+        return dict(net=net, desc=desc, xs=[panels[j] for j in js], sts=[states[si].packed for si in sis],
+                    ms=[slots[si].m for si in sis], vs=[slots[si].v for si in sis], scales=[None] * len(js), sim=sim,
+                    img=desc.img, fx=ring["bufs"][0])
+
     def _draw_minibatches(self, T):
         """A fresh uniform minibatch per evaluation of a neural optimizee (DM/problems.py:282-286: tf.random_uniform
         indices -- a device op there): indices [T+1, batch] in a PERSISTENT device buffer (so that a captured launch

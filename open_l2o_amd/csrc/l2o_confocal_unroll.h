@@ -27,16 +27,25 @@
 // the 6P + 1 gradients and the row loss into LDS in a fixed order (no atomics: two launches give the same bits) ->
 // fx_part[t][b] -> waves w < ceil((6P + 1) / 16): g = grad s / batch, preprocess / RNNProp inputs, the LSTM, x += delta.
 // Dead lanes (coordinate >= 6P + 1) feed zeros and write nothing; a wave with no tile skips the optimizer phase.
+//
+// SEVERAL INSTANCES (l2o_confocal_unroll_multi, include/l2o_confocal_multi_abi.h): the same kernel body with MULTI = true --
+// workgroup i serves row i % batch of instance i / batch and reads its pointers from the instance's table in device memory
+// (CfPtrs) instead of the kernel arguments.  Everything after the prologue is the same code, so the bits are the same.
 #pragma once
-#include "../../include/l2o_confocal_unroll_abi.h"
+#include "../../include/l2o_confocal_multi_abi.h"
 
 namespace l2o {
 
-struct CfUnrollArgs {
+// what every form of the unroll takes: the network, the shape (ONE descriptor for all instances), the step count
+struct CfUnrollCommon {
   NetParams np;
   int batch, P, rx, ry, rz, inference, T;
   float rb;                           // 1 / batch
   float p1_hi, p1_lo, p2_hi, p2_lo;   // beta^step0 as float-float
+};
+
+// one instance: its buffers are kernel arguments
+struct CfUnrollArgs : CfUnrollCommon {
   const float* img;                   // inference: [batch][ry][rx][rz]
   float* fx_part;                     // [T + 1][batch]
   // recording: device table [4][kCfMaxVars] of the history buffers st / g / m / v (k_cf_hist_table fills it)
@@ -49,6 +58,55 @@ struct CfUnrollArgs {
   const float* sim[kCfMaxVars];       // simulation parameters [batch] (unused with inference)
 };
 
+// several instances (l2o_confocal_unroll_multi): N x six tables of 49 pointers cannot be kernel arguments, so every
+// instance has a table of kCfInstPtrs pointers in device scratch -- [x | st | m | v | xs | sim][kCfMaxVars], the history
+// table [st | g | m | v][kCfMaxVars] of a recording launch (the single form's htab), then img, fx_part and fx.
+// k_cf_inst_table / k_cf_hist_table write it ahead of the unroll, in stream order.
+constexpr int kCfTabHist = 6 * kCfMaxVars, kCfTabImg = 10 * kCfMaxVars, kCfTabFxPart = kCfTabImg + 1, kCfTabFx = kCfTabImg + 2;
+constexpr int kCfInstPtrs = kCfTabImg + 4;
+struct CfUnrollMultiArgs : CfUnrollCommon {
+  float* const* tab;                  // [n_inst][kCfInstPtrs]
+};
+
+// where the kernel's pointers come from -- the ONE difference between the two forms.  row(): the batch row of this workgroup
+// (several instances: workgroup i serves row i % batch of instance i / batch).
+template <bool MULTI> struct CfPtrs;
+template <> struct CfPtrs<false> {
+  typedef CfUnrollArgs Args;
+  const CfUnrollArgs& a;
+  __device__ explicit CfPtrs(const CfUnrollArgs& a_) : a(a_) {}
+  __device__ int row() const { return blockIdx.x; }
+  __device__ float* x(int k) const { return a.x[k]; }
+  __device__ float* st(int k) const { return a.st[k]; }
+  __device__ float* m(int k) const { return a.m[k]; }
+  __device__ float* v(int k) const { return a.v[k]; }
+  __device__ const float* xs(int k) const { return a.xs[k]; }
+  __device__ const float* sim(int k) const { return a.sim[k]; }
+  __device__ const float* img() const { return a.img; }
+  __device__ float* fx_part() const { return a.fx_part; }
+  __device__ float* const* htab() const { return a.htab; }
+};
+template <> struct CfPtrs<true> {
+  typedef CfUnrollMultiArgs Args;
+  float* const* tab;                  // this instance's table
+  int b;
+  __device__ explicit CfPtrs(const CfUnrollMultiArgs& a) {
+    const int inst = blockIdx.x / a.batch;
+    b = blockIdx.x - inst * a.batch;
+    tab = a.tab + (size_t)inst * kCfInstPtrs;
+  }
+  __device__ int row() const { return b; }
+  __device__ float* x(int k) const { return tab[k]; }
+  __device__ float* st(int k) const { return tab[kCfMaxVars + k]; }
+  __device__ float* m(int k) const { return tab[2 * kCfMaxVars + k]; }
+  __device__ float* v(int k) const { return tab[3 * kCfMaxVars + k]; }
+  __device__ const float* xs(int k) const { return tab[4 * kCfMaxVars + k]; }
+  __device__ const float* sim(int k) const { return tab[5 * kCfMaxVars + k]; }
+  __device__ const float* img() const { return tab[kCfTabImg]; }
+  __device__ float* fx_part() const { return tab[kCfTabFxPart]; }
+  __device__ float* const* htab() const { return tab + kCfTabHist; }
+};
+
 // the history pointers of a recording launch do not fit the kernel arguments beside the six tables above: a launch of
 // its own leaves them in device scratch ahead of the unroll (stream order)
 struct CfHistPtrs { float* p[4][kCfMaxVars]; };
@@ -57,8 +115,47 @@ __global__ void k_cf_hist_table(CfHistPtrs h, float** tab) {
   if (i < 4 * kCfMaxVars) tab[i] = h.p[i / kCfMaxVars][i % kCfMaxVars];
 }
 
-template <int PRE, bool HIST>
-__global__ __launch_bounds__(kCfThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_cf_unroll(CfUnrollArgs a) {
+// the multi form's tables: one instance's pointers arrive as kernel arguments and are written out (as k_cf_hist_table)
+struct CfInstPtrs { float* p[6][kCfMaxVars]; float* img; float* fx_part; float* fx; };
+__global__ void k_cf_inst_table(CfInstPtrs h, float** tab) {
+  const int i = threadIdx.x;
+  if (i < 6 * kCfMaxVars) tab[i] = h.p[i / kCfMaxVars][i % kCfMaxVars];
+  else if (i == 6 * kCfMaxVars) tab[kCfTabImg] = h.img;
+  else if (i == 6 * kCfMaxVars + 1) tab[kCfTabFxPart] = h.fx_part;
+  else if (i == 6 * kCfMaxVars + 2) tab[kCfTabFx] = h.fx;
+}
+
+// every instance's batch mean, in k_reduce_fx's order (the same bits): block (t, instance)
+__global__ void k_cf_reduce_fx_multi(float* const* tab, int B, float inv_b) {
+  float* const* it = tab + (size_t)blockIdx.y * kCfInstPtrs;
+  const float* fx_part = it[kCfTabFxPart];
+  const int t = blockIdx.x, lane = threadIdx.x;   // 64 threads
+  float acc = 0.0f;
+  for (int b = lane; b < B; b += 64) acc += fx_part[(size_t)t * B + b];
+  acc = wave_sum64(acc);
+  if (lane == 0) it[kCfTabFx][t] = acc * inv_b;
+}
+
+// rnnprop_inputs (l2o_common.h) with the two moment updates' multiply-adds SPELLED OUT.  `beta1 * m + omb1 * g` leaves the
+// compiler the choice of which product to fuse, and it chose differently in the MULTI = true instantiation than in the
+// single form (1-ulp moments, measured); written as the fmaf the single form has always been compiled to, both forms --
+// and any later instantiation -- round alike.  The rest is rnnprop_inputs' arithmetic, which has no such choice in it.
+__device__ __forceinline__ void cf_rnnprop_inputs(float g, float& m, float& v, float beta1, float beta2, float omb1,
+                                                  float omb2, float om1, float om2, float& m_tilde, float& g_tilde) {
+  const float mg = omb1 * g, vg = omb2 * g * g;
+  m = __builtin_fmaf(beta1, m, mg);
+  v = __builtin_fmaf(beta2, v, vg);
+  const float m_hat = m * fast_rcp(om1);
+  const float v_hat = v * fast_rcp(om2);
+  const float inv = fast_rcp(__builtin_amdgcn_sqrtf(v_hat) + 1e-8f);
+  m_tilde = m_hat * inv;
+  g_tilde = g * inv;
+}
+
+template <int PRE, bool HIST, bool MULTI = false>
+__global__ __launch_bounds__(kCfThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_cf_unroll(
+    typename CfPtrs<MULTI>::Args a) {
+  const CfPtrs<MULTI> pt(a);
   extern __shared__ float cf_tg[];                                                     // [ry][rx][rz] target / its norm
   __shared__ float sE[3][kCfMaxPts][32], sDc[3][kCfMaxPts][32], sDs[3][kCfMaxPts][32];   // the fitted points' tables
   __shared__ float sT[3][kCfMaxPts][32];                                               // the simulated points' E (prologue)
@@ -73,7 +170,7 @@ __global__ __launch_bounds__(kCfThreads) __attribute__((amdgpu_waves_per_eu(1, 1
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = lane & 15, q = lane >> 4;
-  const int b = blockIdx.x, B = a.batch;
+  const int b = pt.row(), B = a.batch;
   const int P = a.P, nv = 6 * P + 1, rx = a.rx, ry = a.ry, rz = a.rz;
   const int V = rx * ry * rz;
   const bool sim = !a.inference;
@@ -81,14 +178,14 @@ __global__ __launch_bounds__(kCfThreads) __attribute__((amdgpu_waves_per_eu(1, 1
   // ---- the row's values, scales and moments ------------------------------------------------------------------------------
   if (tid < 64) {
     const bool live = tid < nv;
-    const float xv = live ? a.x[tid][b] : 0.f;
-    const float sc = (live && a.xs[tid]) ? a.xs[tid][b] : 1.f;
+    const float xv = live ? pt.x(tid)[b] : 0.f;
+    const float sc = (live && pt.xs(tid)) ? pt.xs(tid)[b] : 1.f;
     xL[tid] = xv; scL[tid] = sc; xsL[tid] = xv * sc;
-    mL[tid] = (PRE == L2O_PRE_FC_ELU && live) ? a.m[tid][b] : 0.f;
-    vL[tid] = (PRE == L2O_PRE_FC_ELU && live) ? a.v[tid][b] : 0.f;
+    mL[tid] = (PRE == L2O_PRE_FC_ELU && live) ? pt.m(tid)[b] : 0.f;
+    vL[tid] = (PRE == L2O_PRE_FC_ELU && live) ? pt.v(tid)[b] : 0.f;
     sG[tid] = 0.f;
   } else if (sim && tid < 64 + nv) {
-    sSim[tid - 64] = a.sim[tid - 64][b];
+    sSim[tid - 64] = pt.sim(tid - 64)[b];
   }
   // ---- the LSTM: weights, and the state of this lane's coordinate out of the variable's own packed buffer ------------------
   const int var = 16 * wv + c;
@@ -100,7 +197,7 @@ __global__ __launch_bounds__(kCfThreads) __attribute__((amdgpu_waves_per_eu(1, 1
   TileState s;
 #pragma unroll
   for (int t5 = 0; t5 < kNT; ++t5) { s.h1[t5] = 0.f; s.c1[t5] = 0.f; s.h2[t5] = 0.f; s.c2[t5] = 0.f; }
-  if (live) load_tile_state(s, a.st[var] + st_tile, st_lane);
+  if (live) load_tile_state(s, pt.st(var) + st_tile, st_lane);
   constexpr bool PK = bx::packed_default(PRE);
   bx::NetWB<PRE, PK> w;
   bx::load_netw<PRE, true, PK>(w, a.np.wpack, lane);
@@ -157,7 +254,7 @@ __global__ __launch_bounds__(kCfThreads) __attribute__((amdgpu_waves_per_eu(1, 1
         }
     }
   } else {
-    const float* row = a.img + (size_t)b * V;
+    const float* row = pt.img() + (size_t)b * V;
     float n2 = 0.f;
     for (int i = tid; i < V; i += kCfThreads) { const float t = row[i]; cf_tg[i] = t; n2 = fmaf(t, t, n2); }
     n2 = cf_block_sum(n2, red);
@@ -166,7 +263,7 @@ __global__ __launch_bounds__(kCfThreads) __attribute__((amdgpu_waves_per_eu(1, 1
   }
   __syncthreads();
 
-  float* const* htab = a.htab;
+  float* const* htab = pt.htab();
   const int pp = tid >> 5, k = tid & 31;                                                // contraction role: point pp, index k
   for (int t = 0;; ++t) {
     const bool want_g = t < a.T || HIST;                                                // (recording: the gradient at x_T too)
@@ -212,7 +309,7 @@ __global__ __launch_bounds__(kCfThreads) __attribute__((amdgpu_waves_per_eu(1, 1
     }
     // ---- the row loss and the 6P + 1 gradients, fixed order ------------------------------------------------------------
     const float loss = cf_block_sum(acc_l, red);
-    if (tid == 0) a.fx_part[(size_t)t * B + b] = loss;
+    if (tid == 0) pt.fx_part()[(size_t)t * B + b] = loss;
     if (!want_g) break;                                                                 // (uniform)
     const float sum_r = cf_block_sum(acc_b, red);
     {
@@ -261,7 +358,7 @@ __global__ __launch_bounds__(kCfThreads) __attribute__((amdgpu_waves_per_eu(1, 1
         if (PRE == L2O_PRE_FC_ELU) {
           om1 = 1.0f - p1h; om2 = 1.0f - p2h;
           float m = mL[var], v = vL[var];
-          rnnprop_inputs(gv, m, v, a.np.beta1, a.np.beta2, a.np.omb1, a.np.omb2, om1, om2, in0, in1);
+          cf_rnnprop_inputs(gv, m, v, a.np.beta1, a.np.beta2, a.np.omb1, a.np.omb2, om1, om2, in0, in1);
           if (!live) { in0 = 0.0f; in1 = 0.0f; }
           if (live && q == 0) {
             mL[var] = m; vL[var] = v;
@@ -294,10 +391,10 @@ __global__ __launch_bounds__(kCfThreads) __attribute__((amdgpu_waves_per_eu(1, 1
   // ---- write back: x, moments, LSTM state (the coordinates of this row only) ---------------------------------------------
   __syncthreads();
   if (tid < nv) {
-    a.x[tid][b] = xL[tid];
-    if (PRE == L2O_PRE_FC_ELU) { a.m[tid][b] = mL[tid]; a.v[tid][b] = vL[tid]; }
+    pt.x(tid)[b] = xL[tid];
+    if (PRE == L2O_PRE_FC_ELU) { pt.m(tid)[b] = mL[tid]; pt.v(tid)[b] = vL[tid]; }
   }
-  if (live) store_tile_state(s, a.st[var] + st_tile, st_lane);
+  if (live) store_tile_state(s, pt.st(var) + st_tile, st_lane);
 }
 
 }  // namespace l2o

@@ -1307,6 +1307,16 @@ static int launch_confocal_unroll(const CfUnrollArgs& a, bool hist, size_t lds, 
   return L2O_OK;
 }
 
+// ... and several instances per launch: n_inst x batch workgroups, the pointers out of the tables in device scratch
+template <int PRE>
+static int launch_confocal_unroll_multi(const CfUnrollMultiArgs& a, int n_inst, bool hist, size_t lds, hipStream_t s) {
+  void (*fn)(CfUnrollMultiArgs) = hist ? k_cf_unroll<PRE, true, true> : k_cf_unroll<PRE, false, true>;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(fn, dim3(n_inst * a.batch), dim3(kCfThreads), lds, s, a);
+  HIP_TRY(hipGetLastError());
+  return L2O_OK;
+}
+
 extern "C" {
 
 int l2o_abi_version(void) { return L2O_ABI_VERSION; }
@@ -2434,6 +2444,102 @@ int l2o_confocal_unroll_record(const l2o_net_cfg* cfg, const float* wpack, const
   if (!hist) return fail(L2O_ERR_ARG, "l2o_confocal_unroll_record: NULL hist");
   return confocal_unroll_launch("l2o_confocal_unroll_record", cfg, wpack, m, x, st, mm, vv, x_scale, sim, T, step0, fx, hist,
                                 scratch, stream);
+}
+
+// ---- several confocal instances per fused launch (include/l2o_confocal_multi_abi.h) ------------------------------------------
+static bool confocal_unroll_multi_ok(const l2o_net_cfg* cfg, const l2o_confocal* m, int32_t n_inst) {
+  return confocal_unroll_ok(cfg, m) && n_inst >= 1 && n_inst <= L2O_CONFOCAL_MAX_INSTANCES;
+}
+int l2o_confocal_unroll_multi_supported(const l2o_net_cfg* cfg, const l2o_confocal* m, int32_t n_inst, void* /*stream*/) {
+  return confocal_unroll_multi_ok(cfg, m, n_inst) ? 1 : 0;
+}
+// n_inst x fx_part [T + 1][batch] (each rounded up to whole pointers), then the n_inst pointer tables
+size_t l2o_confocal_unroll_multi_scratch_floats(const l2o_confocal* m, int32_t n_inst, int32_t T) {
+  if (!confocal_ok(m) || T < 0 || n_inst < 1 || n_inst > L2O_CONFOCAL_MAX_INSTANCES) return 0;
+  return (size_t)n_inst * (confocal_unroll_fx_floats(m, T) + 2 * (size_t)kCfInstPtrs);
+}
+static int confocal_unroll_multi_launch(const char* who, const l2o_net_cfg* cfg, const float* wpack, const l2o_confocal* m,
+                                        const l2o_confocal_instance* inst, int32_t n_inst, int32_t T, int32_t step0,
+                                        const l2o_confocal_hist* hist, float* scratch, void* stream) {
+  if (!confocal_unroll_multi_ok(cfg, m, n_inst))
+    return fail(L2O_ERR_UNSUPPORTED, "%s: the (20, 20) LSTM nets; batch in [1, %d], num_points in [1, %d], roi edges in "
+                "[%d, %d], inference 0 or 1; 1 to %d instances", who, kCfMaxBatch, kCfMaxPts, kCfMinEdge, kCfMaxEdge,
+                L2O_CONFOCAL_MAX_INSTANCES);
+  if (!wpack || !inst || !scratch || T < 0) return fail(L2O_ERR_ARG, "%s: NULL argument or T < 0", who);
+  const bool rn = cfg->preprocess == L2O_PRE_FC_ELU;
+  const int nv = 6 * m->num_points + 1;
+  // every instance is checked before anything is launched
+  for (int i = 0; i < n_inst; ++i) {
+    const l2o_confocal_instance& in = inst[i];
+    if (!in.fx || (m->inference && !in.img)) return fail(L2O_ERR_ARG, "%s: instance %d: NULL fx, or inference without img", who, i);
+    for (int k = 0; k < nv; ++k) {
+      if (!in.x[k] || !in.st[k] || (rn && (!in.m[k] || !in.v[k])) || (!m->inference && !in.sim[k]))
+        return fail(L2O_ERR_ARG, "%s: instance %d: NULL buffer of variable %d", who, i, k);
+      if (hist && (!hist[i].st[k] || !hist[i].g[k] || (rn && (!hist[i].m[k] || !hist[i].v[k]))))
+        return fail(L2O_ERR_ARG, "%s: instance %d: NULL history buffer of variable %d", who, i, k);
+    }
+  }
+  const size_t fx_floats = confocal_unroll_fx_floats(m, T);
+  float** tab = reinterpret_cast<float**>(scratch + (size_t)n_inst * fx_floats);
+  hipStream_t s = (hipStream_t)stream;
+  for (int i = 0; i < n_inst; ++i) {
+    const l2o_confocal_instance& in = inst[i];
+    CfInstPtrs ip;
+    std::memset(&ip, 0, sizeof(ip));
+    CfHistPtrs hp;
+    std::memset(&hp, 0, sizeof(hp));
+    for (int k = 0; k < nv; ++k) {
+      ip.p[0][k] = in.x[k]; ip.p[1][k] = in.st[k];
+      ip.p[2][k] = rn ? in.m[k] : nullptr; ip.p[3][k] = rn ? in.v[k] : nullptr;
+      ip.p[4][k] = const_cast<float*>(in.x_scale[k]);
+      ip.p[5][k] = m->inference ? nullptr : const_cast<float*>(in.sim[k]);
+      if (hist) {
+        hp.p[0][k] = hist[i].st[k]; hp.p[1][k] = hist[i].g[k];
+        hp.p[2][k] = rn ? hist[i].m[k] : nullptr; hp.p[3][k] = rn ? hist[i].v[k] : nullptr;
+      }
+    }
+    ip.img = m->inference ? const_cast<float*>(in.img) : nullptr;
+    ip.fx_part = scratch + (size_t)i * fx_floats;
+    ip.fx = in.fx;
+    float** it = tab + (size_t)i * kCfInstPtrs;
+    hipLaunchKernelGGL(k_cf_inst_table, dim3(1), dim3(320), 0, s, ip, it);
+    if (hist) hipLaunchKernelGGL(k_cf_hist_table, dim3(1), dim3(256), 0, s, hp, it + kCfTabHist);
+  }
+  HIP_TRY(hipGetLastError());
+  CfUnrollMultiArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.np = make_net_params(cfg, wpack);
+  a.batch = m->batch; a.P = m->num_points; a.rx = m->roi[0]; a.ry = m->roi[1]; a.rz = m->roi[2];
+  a.inference = m->inference; a.T = T;
+  a.rb = 1.0f / (float)m->batch;
+  pow_ff(cfg->beta1, step0, &a.p1_hi, &a.p1_lo);
+  pow_ff(cfg->beta2, step0, &a.p2_hi, &a.p2_lo);
+  a.tab = tab;
+  const size_t lds = sizeof(float) * (size_t)a.rx * a.ry * a.rz;
+  int rc;
+  switch (cfg->preprocess) {
+    case L2O_PRE_IDENTITY: rc = launch_confocal_unroll_multi<L2O_PRE_IDENTITY>(a, n_inst, hist != nullptr, lds, s); break;
+    case L2O_PRE_LOGSIGN: rc = launch_confocal_unroll_multi<L2O_PRE_LOGSIGN>(a, n_inst, hist != nullptr, lds, s); break;
+    default: rc = launch_confocal_unroll_multi<L2O_PRE_FC_ELU>(a, n_inst, hist != nullptr, lds, s);
+  }
+  if (rc != L2O_OK) return rc;
+  hipLaunchKernelGGL(k_cf_reduce_fx_multi, dim3(T + 1, n_inst), dim3(64), 0, s, tab, (int)a.batch, a.rb);
+  HIP_TRY(hipGetLastError());
+  note_form(L2O_FORM_CONFOCAL_MULTI);
+  return L2O_OK;
+}
+int l2o_confocal_unroll_multi(const l2o_net_cfg* cfg, const float* wpack, const l2o_confocal* m,
+                              const l2o_confocal_instance* inst, int32_t n_inst, int32_t T, int32_t step0, float* scratch,
+                              void* stream) {
+  return confocal_unroll_multi_launch("l2o_confocal_unroll_multi", cfg, wpack, m, inst, n_inst, T, step0, nullptr, scratch,
+                                      stream);
+}
+int l2o_confocal_unroll_multi_record(const l2o_net_cfg* cfg, const float* wpack, const l2o_confocal* m,
+                                     const l2o_confocal_instance* inst, int32_t n_inst, int32_t T, int32_t step0,
+                                     const l2o_confocal_hist* hist, float* scratch, void* stream) {
+  if (!hist) return fail(L2O_ERR_ARG, "l2o_confocal_unroll_multi_record: NULL hist");
+  return confocal_unroll_multi_launch("l2o_confocal_unroll_multi_record", cfg, wpack, m, inst, n_inst, T, step0, hist,
+                                      scratch, stream);
 }
 
 #ifndef L2O_MLP_XCD_DEFAULT_FOUR

@@ -527,7 +527,9 @@ def confocal_microscopy_3d(batch_size=128, num_points=5, ROI=[28, 28, 28], stdde
 
     ``fused`` (an extension, default off): where one (20, 20) LSTM net steps every variable, run the unroll as ONE persistent
     launch (l2o_confocal_unroll: one workgroup per batch row) instead of the step-granular launches; the graph falls back
-    to those wherever the fused form does not apply (``last_path`` tells which ran).
+    to those wherever the fused form does not apply (``last_path`` tells which ran).  Several such instances of one shape
+    (replicas.Replicas, run and train_step) share launches of up to 32 -- one workgroup per row of EVERY instance, form
+    "rows" (l2o_confocal_unroll_multi) --, with results bit-identical to their own launches.
 
     Variables as the reference declares them, each [batch_size, 1]: per point I_var_i, x_var_i, y_var_i, z_var_i,
     sigmaxy_var_i, sigmaz_var_i ~ U[0, 1); then per point the non-trainable I_sim_i, x_sim_i, y_simi (the reference's

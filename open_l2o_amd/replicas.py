@@ -7,8 +7,15 @@ MI355X the neural optimizee (problems.mnist, 784-20-10) has two kernel forms (DE
     form "chip"  k_mlp_unroll: ONE instance on all 8 XCDs -- the lowest latency of a single unroll
     form "xcd"   k_mlp_xcd:    one instance per XCD, up to 8 per launch -- 3-4 x the throughput
 
+and problems.confocal_microscopy_3d(fused=True), whose batch rows are independent problems, has a third:
+
+    form "rows"  k_cf_unroll:  one workgroup per row of EVERY instance, up to 32 instances of one shape per launch
+                               (l2o_confocal_unroll_multi) -- a single instance of batch 32 keeps 32 of the 256 CUs busy.
+                               No workgroup waits for another: no snapshot, no status check, no recovery; the results are
+                               bit-identical to the instances' own fused launches (which is what form "chip" runs here)
+
 ``Replicas`` builds N unroll graphs of one ``MetaOptimizer`` that share its networks and runs them in launches of up to
-eight instances (l2o_mlp_unroll_multi), or one after the other on the whole chip:
+eight (l2o_mlp_unroll_multi) / 32 (l2o_confocal_unroll_multi) instances, or one after the other on the whole chip:
 
     reps = Replicas(optimizer, [problems.mnist(...) for _ in range(8)], len_unroll=200)
     reps.reset()
@@ -28,6 +35,11 @@ import torch
 
 from . import _abi
 from ._graph_core import _DevGrad, _all_reduce, _world
+
+
+def _confocal_shape(d):
+    """What the instances of one l2o_confocal_unroll_multi launch share (ONE descriptor)."""
+    return (int(d.batch), int(d.num_points), tuple(int(r) for r in d.roi), d.img is not None)
 
 
 class Replicas(object):
@@ -85,6 +97,56 @@ class Replicas(object):
         inst = g.mlp_instance(None, dry=True)
         return inst is not None and eng.mlp_unroll_multi_supported(inst["net"].spec, inst["desc"], min(8, len(self.graphs)))
 
+    def rows_supported(self):
+        """Form "rows" applies: every replica is a problems.confocal_microscopy_3d(fused=True) term of ONE shape whose
+        variables are all stepped by one (20, 20) LSTM network, on an engine that has l2o_confocal_unroll_multi."""
+        eng = self.graphs[0].engine
+        if not hasattr(eng, "confocal_unroll_multi") or os.environ.get("L2O_DISABLE_FUSED"):
+            return False
+        first = None
+        for g in self.graphs:
+            inst = g.confocal_instance(None, dry=True)
+            if inst is None:
+                return False
+            if first is None:
+                first = inst
+            elif inst["net"] is not first["net"] or _confocal_shape(inst["desc"]) != _confocal_shape(first["desc"]):
+                return False
+        return bool(eng.confocal_unroll_multi_supported(first["net"].spec, first["desc"],
+                                                        min(_abi.CONFOCAL_MAX_INSTANCES, len(self.graphs))))
+
+    def _launch_rows(self, feed, record=False):
+        """ENQUEUE one committed unroll of every replica on form "rows": launches of up to CONFOCAL_MAX_INSTANCES instances,
+        in the replicas' order.  record: the recording form, every replica's history into its graph's record plan.
+        Returns (instances, records or None)."""
+        graphs = self.graphs
+        eng = graphs[0].engine
+        T = self.len_unroll
+        insts = [g.confocal_instance(self._feed(g, feed)) for g in graphs]
+        if any(i is None for i in insts):
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "Replicas: l2o_confocal_unroll_multi does not apply")
+        step0 = int(feed[graphs[0].step]) if graphs[0].rnnprop else 1
+        hists = recs = None
+        if record:
+            hists, recs = [], []
+            for g in graphs:
+                slots = g.slots
+                panels = [v.value.view(*g._panel_shape(v)) for v in g.x]
+                plan = g._mlp_hist_plan(T, panels, slots, [s.state for s in slots], [s.m for s in slots], [s.v for s in slots])
+                recs.append(dict(step0=step0, shapes=[tuple(p.shape) for p in panels], g=plan["g"], st=plan["st"], m=plan["m"],
+                                 v=plan["v"], g_final=plan["g_final"], plan=plan))
+                hists.append(plan["hist"])
+        net, desc = insts[0]["net"], insts[0]["desc"]
+        wpack = net.wpack(eng)
+        n = _abi.CONFOCAL_MAX_INSTANCES
+        for k in range(0, len(insts), n):
+            eng.confocal_unroll_multi(net.spec, wpack, desc, insts[k:k + n], T, step0,
+                                      hists=None if hists is None else hists[k:k + n])
+        self.last_form = "rows"
+        for g in graphs:
+            g.last_path = "confocal_multi"
+        return insts, recs
+
     def _draw_all(self):
         """The minibatch indices of ALL replicas in one device draw (one torch generator call instead of one per replica;
         every replica still gets its own independent index sequence) -- when no replica has a host `sampler` and the engine
@@ -107,9 +169,12 @@ class Replicas(object):
     def launch(self, feed=None):
         """ENQUEUE one committed unroll of every replica on the one-instance-per-XCD kernel (launches of up to eight) without
         synchronising the host, without a recovery snapshot and without a status check -- the caller syncs and calls
-        engine.check_unroll_status() itself (bench.py's timed region).  Returns the replicas' loss buffers (device, [T + 1])."""
+        engine.check_unroll_status() itself (bench.py's timed region).  Confocal replicas (rows_supported()) go out on
+        form "rows" instead, which has no status to check.  Returns the replicas' loss buffers (device, [T + 1])."""
         graphs = self.graphs
         eng = graphs[0].engine
+        if self.rows_supported():
+            return [i["fx"] for i in self._launch_rows(feed or {})[0]]
         drew = self._draw_all()
         insts = [g.mlp_instance(self._feed(g, feed), draw=not drew) for g in graphs]
         if any(i is None for i in insts):
@@ -126,12 +191,21 @@ class Replicas(object):
 
     def run(self, feed=None, form="auto"):
         """One committed unroll of every replica from its current variables (== N x sess.run([fx, update])).
-        form: "xcd" (launches of up to eight instances, one per XCD), "chip" (one instance after the other on the whole
-        chip) or "auto" (xcd for two or more replicas where the kernel applies).  Returns the N final losses (host)."""
-        if form not in ("auto", "xcd", "chip"):
-            raise ValueError("form must be auto, xcd or chip")
+        form: "xcd" (launches of up to eight instances, one per XCD), "rows" (confocal replicas: launches of up to 32
+        instances, one workgroup per row of every instance), "chip" (one instance after the other on the whole chip) or
+        "auto" (xcd / rows for two or more replicas where that kernel applies).  Returns the N final losses (host)."""
+        if form not in ("auto", "xcd", "rows", "chip"):
+            raise ValueError("form must be auto, xcd, rows or chip")
         graphs = self.graphs
         eng = graphs[0].engine
+        if form == "rows" or (form == "auto" and len(graphs) > 1 and self.rows_supported()):
+            if not self.rows_supported():
+                raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "Replicas.run(form='rows'): l2o_confocal_unroll_multi does "
+                                          "not apply to these optimizees / this network / engine")
+            insts, _ = self._launch_rows(feed or {})
+            fx_host = [eng.to_numpy(i["fx"]) for i in insts]    # host sync; nothing to check or to recover from
+            self.fx_arrays = fx_host
+            return np.array([f[self.len_unroll] for f in fx_host], np.float32)
         use_xcd = form == "xcd" or (form == "auto" and len(graphs) > 1 and self.xcd_supported())
         if use_xcd and not self.xcd_supported():
             raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "Replicas.run(form='xcd'): l2o_mlp_unroll_multi does not apply to "
@@ -192,8 +266,17 @@ class Replicas(object):
 
     # -- meta-training (DM/meta.py:398-414, DM/meta_rnnprop_train.py:559-593) on all replicas at once -----------------------
     def _check_shared(self):
-        """The replicas of a train step: problems.mnist over ONE data set, all variables stepped by ONE network."""
+        """The replicas of a train step: problems.mnist over ONE data set -- or problems.confocal_microscopy_3d of ONE
+        shape --, all variables stepped by ONE network, without second derivatives."""
         g0 = self.graphs[0]
+        if all(len(g.terms) == 1 and g.terms[0].kind == _abi.PROB_CONFOCAL for g in self.graphs):
+            for g in self.graphs:
+                g._ensure_init()
+                if (g.second_derivatives or len({id(s.net) for s in g.slots}) != 1 or g.slots[0].net is not g0.slots[0].net
+                        or _confocal_shape(g._mlp_desc(g.terms[0])) != _confocal_shape(g0._mlp_desc(g0.terms[0]))):
+                    raise ValueError("Replicas.train_step: confocal replicas must be problems.confocal_microscopy_3d instances "
+                                     "of ONE shape, stepped by one LSTM network, without second derivatives")
+            return
         for g in self.graphs:
             g._ensure_init()
             nets = {id(s.net) for s in g.slots}
@@ -250,13 +333,14 @@ class Replicas(object):
         computes for that replica alone), and ONE Adam step of the optimizer applies it.  Under torch.distributed the
         gradient is also averaged over the ranks (the mean over N x world replicas).
         Forward: launches of up to eight replicas on the recording one-instance-per-XCD kernel where it applies
-        (last_form "xcd"), else each replica's own recording unroll (last_form "chip").  Backward: the replicas' panels
-        pooled two replicas per fused BPTT launch (4 panels each; the launch takes 8).
+        (last_form "xcd"), of up to 32 confocal replicas on the recording one-workgroup-per-row kernel (last_form "rows";
+        "auto" takes it for two or more replicas), else each replica's own recording unroll (last_form "chip").  Backward:
+        the replicas' panels pooled two replicas per BPTT call (the fused BPTT launch takes 8 panels: two MNIST replicas).
         A partner timeout of a recording kernel skips the (device-side, status-guarded) update, takes the Adam step back
         and raises L2OPartnerTimeout, as UnrollGraph.train_step does.
         Returns {"loss": mean over the replicas of sum_t fx_t, "fx": [N] final losses}; fx_arrays as run()."""
-        if form not in ("auto", "xcd", "chip"):
-            raise ValueError("form must be auto, xcd or chip")
+        if form not in ("auto", "xcd", "rows", "chip"):
+            raise ValueError("form must be auto, xcd, rows or chip")
         graphs = self.graphs
         g0 = graphs[0]
         eng = g0.engine
@@ -271,11 +355,19 @@ class Replicas(object):
             self._sync_weights()
             self._weights_synced = True
         step0 = int(feed[g0.step]) if g0.rnnprop else 1
-        use_xcd = form == "xcd" or (form == "auto" and self.xcd_supported())
+        use_rows = form == "rows" or (form == "auto" and len(graphs) > 1 and self.rows_supported())
+        if use_rows and not self.rows_supported():
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "Replicas.train_step(form='rows'): "
+                                      "l2o_confocal_unroll_multi_record does not apply to these optimizees / this network / engine")
+        use_xcd = not use_rows and (form == "xcd" or (form == "auto" and self.xcd_supported()))
         if use_xcd and not self.xcd_supported():
             raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "Replicas.train_step(form='xcd'): l2o_mlp_unroll_multi_record "
                                       "does not apply to this optimizee / network / device")
-        if use_xcd:
+        if use_rows:                                        # (no exchange: no status word guards the update)
+            insts, recs = self._launch_rows(feed, record=True)
+            runs = [(rec, inst["fx"]) for rec, inst in zip(recs, insts)]
+            fused = False
+        elif use_xcd:
             self.last_form = "xcd"
             runs = self._record_xcd(feed, step0)
             fused = hasattr(eng, "check_unroll_status")

@@ -12,7 +12,8 @@ def evaluate_replicas(FLAGS, optimizer, problem, net_assignments, num_unrolls):
     committed unrolls of unroll_len steps whose fx is recorded: DM/evaluate_dm.py:88-91, DM/evaluate_rnnprop.py:79-92,
     DM/util.py:78-89) -- as ONE unroll of num_unrolls * unroll_len steps per instance, all instances in launches of up to
     eight (Replicas.run: problems.mnist at minibatch 64 or 128 on the MI355X runs one instance per XCD; other minibatches
-    one instance after the other on the whole chip)."""
+    one instance after the other on the whole chip) -- or, for confocal_microscopy_3d with --confocal_fused 1, of up to 32
+    (kernel form "rows": one workgroup per row of every instance)."""
     L = FLAGS.unroll_len
     reps = Replicas(optimizer, [problem] * FLAGS.replicas, num_unrolls * L, net_assignments=net_assignments)
     records = [[] for _ in range(FLAGS.replicas)]

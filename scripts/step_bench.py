@@ -9,11 +9,14 @@
     autograd on the same GPU, timed the same way (lenet: conv2d / max_pool2d / matmul of the installed torch, batch norm
     from var_mean; confocal: torch.erf on the separable tables, one einsum per point);
   * confocal: the per-kernel split comes from the device, in a run of its own: ``--loop N`` runs N bare evaluations and
-    nothing else, for ``rocprofv3 --kernel-trace --stats -- python scripts/step_bench.py --problem confocal --loop 2000``.
+    nothing else, for ``rocprofv3 --kernel-trace --stats -- python scripts/step_bench.py --problem confocal --loop 2000``;
+  * confocal with ``--fused 1 --replicas N``: nothing but N fused unrolls as ONE launch (replicas.Replicas, form "rows":
+    rows_step_us_per_instance) against the same N replicas as N single fused launches (the yardstick:
+    single_step_us_per_instance) -- us per optimizer step per instance, the median of 10 event-timed rounds each.
 
     python scripts/step_bench.py --problem {mnist_conv,cifar_conv,lenet} [--batch 128] [--iters 200] [--unroll 20] [--unrolls 10]
     python scripts/step_bench.py --problem confocal [--batch 32] [--points 5] [--roi 28] [--iters 500] [--unroll 20] [--fused 1]
-                                 [--unrolls 10] [--loop N]
+                                 [--unrolls 10] [--loop N] [--replicas N]
 
 Prints one JSON line.  The image nets run on synthetic data (problems.synthetic_mnist / synthetic_cifar10); the arithmetic
 does not depend on it."""
@@ -188,7 +191,51 @@ def confocal_torch(theta, sim, points, roi, iters):
     return us, float(out["loss"].detach())
 
 
+def confocal_replicas(a):
+    """N fused unrolls as one rows launch, and the same N replicas as N single fused launches: us per optimizer step per
+    instance, medians of `rounds` event-timed rounds after a warm-up, the two forms alternating in one process."""
+    from open_l2o_amd.replicas import Replicas
+    roi, N, T, rounds = [a.roi] * 3, a.replicas, a.unroll, 10
+    problem, net_config, na = util.get_config("confocal_microscopy_3d", problem_options={
+        "batch_size": a.batch, "num_points": a.points, "ROI": roi, "fused": True})
+    reps = Replicas(meta.MetaOptimizer(**net_config), [problem] * N, T, na)
+    reps.reset()
+    if not reps.rows_supported():
+        raise SystemExit("step_bench: form 'rows' does not apply")
+
+    def rows():
+        reps.launch({})
+
+    def singles():
+        for g in reps.graphs:
+            g.launch({}, commit=True)
+    times = {"rows": [], "single": []}
+    for k in range(2 + rounds):
+        for name, fn in (("rows", rows), ("single", singles)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if k >= 2:
+                times[name].append(1e3 * e0.elapsed_time(e1) / (T * N))
+        if k == 0:
+            forms = (reps.last_form, reps.graphs[0].last_path)
+    assert forms == ("rows", "confocal_unroll"), forms
+    return {"workload": "confocal_microscopy_3d", "batch": a.batch, "points": a.points, "roi": roi, "replicas": N,
+            "unroll": T, "rounds": rounds, "rows_step_us_per_instance": round(float(np.median(times["rows"])), 2),
+            "single_step_us_per_instance": round(float(np.median(times["single"])), 2),
+            "rows_min_max": [round(min(times["rows"]), 2), round(max(times["rows"]), 2)],
+            "single_min_max": [round(min(times["single"]), 2), round(max(times["single"]), 2)],
+            "workgroups_per_rows_launch": N * a.batch, "device": torch.cuda.get_device_name(0)}
+
+
 def confocal_main(eng, a):
+    if a.replicas:
+        if not a.fused:
+            raise SystemExit("step_bench: --replicas needs --fused 1")
+        return confocal_replicas(a)
     roi = (a.roi, a.roi, a.roi)
     fg, loss, (theta, sim) = confocal_fg(eng, a.batch, a.points, roi)
     if a.loop:
@@ -237,6 +284,8 @@ def main():
     p.add_argument("--fused", type=int, choices=(0, 1), default=0,
                    help="confocal: 1 also times the fused unroll (fused_step_us) beside the step path (step_us)")
     p.add_argument("--loop", type=int, default=0, help="confocal: only run this many bare evaluations (for a kernel trace)")
+    p.add_argument("--replicas", type=int, default=0,
+                   help="confocal, with --fused 1: time N fused unrolls as one launch against N single launches, nothing else")
     a = p.parse_args()
     confocal = a.problem == "confocal"
     a.batch = a.batch or (32 if confocal else 128)
