@@ -143,9 +143,35 @@ __device__ __forceinline__ unsigned bias_one(int q) {
 }
 
 // one = bias_one<PK>(q) for the chunks that carry a bias row, 0 otherwise
-template <bool PK>
+// SR (packed form only): the SCALAR-RESIDUAL form -- the two residual updates per level as four plain v_sub_f32 on the
+// components instead of two v_pk_add_f32 on the pairs.  For a split that the wave issues between MFMAs (k_unroll_pair:
+// the split of h2 under chunk L2B, the split of h1 in front of chunk L2A): beside MFMAs a packed fp32 instruction costs
+// its issue slot plus 13-22 cycles, a plain one only its slot (see gates5_scalar).  The same subtractions of the same
+// operands, the same conversions, the same register quads: bit-identical.  Everything else keeps the packed form
+// (profiles/r09_split_beside_mfma_ab.txt).
+template <bool PK, bool SR = false>
 __device__ __forceinline__ void split5(const float (&v)[kNT], unsigned one, BOp<PK>& o) {
-  if constexpr (PK) {
+  static_assert(PK || !SR, "split5: the scalar-residual form belongs to the packed split");
+#ifdef L2O_ABLATE_SPLIT
+  constexpr bool kSR = false;      // (the timing ablation lives in the packed branch)
+#else
+  constexpr bool kSR = SR;
+#endif
+  if constexpr (PK && kSR) {
+    float a0 = v[0], a1 = v[1], b0 = v[2], b1 = v[3];
+    const unsigned pa0 = cvt_pk(mk2(a0, a1)), pb0 = cvt_pk(mk2(b0, b1)), ca = cvt_pk(mk2(v[4], v[4]));
+    o.m[0][0] = pa0; o.m[0][1] = pb0; o.m[0][2] = ca; o.m[0][3] = one;
+    o.m[1][0] = pa0; o.m[1][1] = pb0; o.m[1][2] = pa0; o.m[1][3] = pb0;
+    a0 -= __uint_as_float(pa0 << 16); a1 -= __uint_as_float(pa0 & 0xffff0000u);
+    b0 -= __uint_as_float(pb0 << 16); b1 -= __uint_as_float(pb0 & 0xffff0000u);
+    const float r1 = v[4] - __uint_as_float(ca << 16);
+    const unsigned pa1 = cvt_pk(mk2(a0, a1)), pb1 = cvt_pk(mk2(b0, b1)), cb = cvt_pk(mk2(v[4], r1));
+    o.m[2][0] = pa1; o.m[2][1] = pb1; o.m[2][2] = cb; o.m[2][3] = pa1;
+    a0 -= __uint_as_float(pa1 << 16); a1 -= __uint_as_float(pa1 & 0xffff0000u);
+    b0 -= __uint_as_float(pb1 << 16); b1 -= __uint_as_float(pb1 & 0xffff0000u);
+    const float r2 = r1 - __uint_as_float(cb & 0xffff0000u);
+    o.m[3][0] = pb1; o.m[3][1] = cvt_pk(mk2(a0, a1)); o.m[3][2] = cvt_pk(mk2(b0, b1)); o.m[3][3] = cvt_pk(mk2(r1, r2));
+  } else if constexpr (PK) {
 #ifdef L2O_ABLATE_SPLIT
 #pragma unroll
     for (int j = 0; j < kPack; ++j) {
@@ -461,11 +487,13 @@ __device__ __forceinline__ void gates5_scalar(const f32x4 (&acc)[kNT], float (&c
 struct NoShadow { __device__ __forceinline__ void operator()() const {} };
 // REARM: leave acc1 / acc2 re-initialised with the biases for the NEXT step (the persistent unroll kernels); tile_step
 // (a fresh pair of accumulators per call) switches it off -- the pinned loads would be 10 dead ds_read_b128 per tile
-template <int PRE, bool NEXT, bool PK, class Shadow = NoShadow, bool REARM = true, class W = NetWB<PRE, PK>>
+// SR: the split of h1 in front of chunk L2A in its scalar-residual form (split5; k_unroll_pair)
+template <int PRE, bool NEXT, bool PK, class Shadow = NoShadow, bool REARM = true, class W = NetWB<PRE, PK>, bool SR = false>
 __device__ __forceinline__ float finish(const W& w, TileState& s, BOp<PK>& b1, BOp<PK>& b2,
                                         f32x4 (&acc1)[kNT], f32x4 (&acc2)[kNT], float in0, float in1, unsigned one,
                                         int q, PhaseClock& pc, Shadow&& shadow = Shadow()) {
   constexpr int kN = chunk_mfmas(PK);
+  static_assert(!SR || (PK && !NEXT && !W::kLdsFrags), "finish: the scalar-residual split is k_unroll_pair's");
   if constexpr (PRE == L2O_PRE_FC_ELU) {   // (constexpr: chunk L1X does not exist for the DM nets)
     float fc[kNT];
 #pragma unroll
@@ -500,7 +528,7 @@ __device__ __forceinline__ float finish(const W& w, TileState& s, BOp<PK>& b1, B
   constexpr bool kPinBias = !W::kLdsFrags || L2O_FINISH_PINNED_LDSFRAGS;
   if (REARM || NEXT) preload_bias<0, W, kPinBias>(w, acc1);   // acc1 is dead: the next step's layer-1 accumulator init
   pc.mark(6);
-  split5<PK>(s.h1, one, b1);
+  split5<PK, SR>(s.h1, one, b1);
   issue<PRE, kChL2A, 0, kN, false>(w, b1, acc2);
   if constexpr (!std::is_same<typename std::decay<Shadow>::type, NoShadow>::value) {
     // the caller's work between the MFMAs: in program order the wave would issue the kN MFMAs back to back
@@ -706,7 +734,9 @@ struct LstmCore<PRE, false, PK> {
   __device__ __forceinline__ void refresh(const TileState&) {}
 };
 
-template <int PRE, bool PK, class WT>
+// SR: refresh() and the split inside finish() in the scalar-residual form (bx::split5) -- the two splits that the step
+// loop of k_unroll_pair interleaves with MFMAs; init() runs in front of the loop and keeps the packed form
+template <int PRE, bool PK, class WT, bool SR = false>
 struct LstmCoreRegs {
   static constexpr int kTotal = bx::chunk_mfmas(PK), kHalf = kTotal / 2;
   WT w;
@@ -763,13 +793,25 @@ struct LstmCoreRegs {
   template <bool NEXT, class Shadow = bx::NoShadow, bool REARM = true>
   __device__ __forceinline__ float finish(TileState& s, f32x4 (&acc1)[kNT], f32x4 (&acc2)[kNT], float in0, float in1,
                                           int q, PhaseClock& pc, Shadow&& shadow = Shadow()) {
-    return bx::finish<PRE, NEXT, PK, Shadow, REARM, WT>(w, s, b1, b2, acc1, acc2, in0, in1, one, q, pc, static_cast<Shadow&&>(shadow));
+    return bx::finish<PRE, NEXT, PK, Shadow, REARM, WT, SR>(w, s, b1, b2, acc1, acc2, in0, in1, one, q, pc, static_cast<Shadow&&>(shadow));
   }
   // after finish<false>: b1 already holds split h1(t) (finish builds it for chunk L2A); split h2(t) for chunk L2B
-  __device__ __forceinline__ void refresh(const TileState& s) { bx::split5<PK>(s.h2, one, b2); }
+  __device__ __forceinline__ void refresh(const TileState& s) { bx::split5<PK, SR>(s.h2, one, b2); }
 };
 template <int PRE, bool PK>
 struct LstmCore<PRE, true, PK> : LstmCoreRegs<PRE, PK, bx::NetWB<PRE, PK>> {};
+// The core of the two-CU unroll (k_unroll_pair): LstmCore, with the packed form's in-loop splits scalar-residual in the
+// FAST kernel (full tiles: config 2).  One wave per SIMD issues those splits between the MFMAs of chunks L2B and L2A.  The
+// gather kernel (ragged shapes) keeps the packed residuals: measured on config 4's shard of 8 the scalar form cost it
+// 0.5 % (the loop's schedule shifts with it), so its text and ISA stay what they were; so does every other kernel, which
+// splits away from the matrix pipe's busy stretches or runs several waves per SIMD (profiles/r09_split_beside_mfma_ab.txt).
+#ifndef L2O_PAIR_SPLIT_SCALAR
+#define L2O_PAIR_SPLIT_SCALAR 1   // 0: the packed residuals everywhere (A/B builds)
+#endif
+template <int PRE, bool BX, bool FAST, bool PK = bx::packed_default(PRE)>
+struct LstmCorePair : LstmCore<PRE, BX, PK> {};
+template <int PRE>
+struct LstmCorePair<PRE, true, true, true> : LstmCoreRegs<PRE, true, bx::NetWB<PRE, true>, L2O_PAIR_SPLIT_SCALAR != 0> {};
 // the 6-product form with chunk LDSCH in LDS (bx::NetWBH); stage_chunk: every thread copies its share, a barrier follows
 template <int PRE, int LDSCH>
 struct LstmCoreHyb : LstmCoreRegs<PRE, false, bx::NetWBH<PRE, LDSCH>> {

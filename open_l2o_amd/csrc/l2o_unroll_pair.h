@@ -119,6 +119,9 @@ __device__ __forceinline__ void dot4v(const float4 a, const l2o::f32x4 b, float4
 #ifndef L2O_GEMV_PK
 #define L2O_GEMV_PK 1
 #endif
+#ifndef L2O_GEMV_PK_G
+#define L2O_GEMV_PK_G L2O_GEMV_PK   // the g pass alone (the 16 FMAs behind barrier B2; profiles/r09_split_beside_mfma_ab.txt)
+#endif
 struct Acc4pk { l2o::bx::f32x2 lo, hi; };
 __device__ __forceinline__ void dot4pk(const l2o::f32x4 a, const l2o::f32x4 b, Acc4pk& acc) {
   acc.lo = __builtin_elementwise_fma(__builtin_shufflevector(a, a, 0, 1), __builtin_shufflevector(b, b, 0, 1), acc.lo);
@@ -247,7 +250,7 @@ __device__ __forceinline__ void unroll_pair_body_gather(const UnrollPairArgs& pa
 
   // ---- per-lane persistent registers -------------------------------------
   // <= 4 waves per workgroup: bf16x3 gate GEMM, weights in VGPR + AGPR
-  using Core = LstmCore<PRE, !EXACT>;
+  using Core = LstmCorePair<PRE, !EXACT, false>;
   Core core;
   core.load(a.np.wpack, lane);
   core.pin();   // fragments -> AGPRs (MFMA reads them there): the VGPRs hold W, the state and the gate math
@@ -437,7 +440,7 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
 
   // ---- per-lane persistent registers -------------------------------------
   // <= 4 waves per workgroup: bf16x3 gate GEMM, weights in VGPR + AGPR
-  using Core = LstmCore<PRE, !EXACT>;
+  using Core = LstmCorePair<PRE, !EXACT, true>;
   Core core;
   core.load(a.np.wpack, lane);
   __builtin_amdgcn_sched_barrier(0);                    // (everything above is issue only; the uses start below)

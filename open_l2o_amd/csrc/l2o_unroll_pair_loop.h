@@ -149,14 +149,15 @@
     // ---- g = W^T r for this wave's 16 coordinates ------------------------------
     // all CH residual reads are issued back to back (hipcc serialises them on one register
     // quad otherwise: CH x LDS latency on the critical path), one wait, then the FMAs
+    constexpr bool kPkG = L2O_GEMV_PK_G != 0;
     float4 gacc4 = {0.f, 0.f, 0.f, 0.f};
     Acc4pk gaccp = {{0.f, 0.f}, {0.f, 0.f}};
 #pragma unroll
     for (int m = 0; m < CH; ++m) {
-      if (kPk) dot4pk(wtq[m], rv4v[m], gaccp);
+      if (kPkG) dot4pk(wtq[m], rv4v[m], gaccp);
       else dot4v(wt[m], rv4v[m], gacc4);
     }
-    float gv = quad_q_sum(kPk ? hsum4pk(gaccp) : hsum4(gacc4));
+    float gv = quad_q_sum(kPkG ? hsum4pk(gaccp) : hsum4(gacc4));
     if (KIND == L2O_PROB_SQUARE_COS) gv *= 2.0f;            // only the ||wx-y||^2 part carries the 2
     if (KIND == L2O_PROB_LASSO) gv += pp.l1 * (xsv > 0.f ? 1.f : (xsv < 0.f ? -1.f : 0.f));
     if (kCos) gv += kTwoPi * pp.alpha * cj * trig.s;
