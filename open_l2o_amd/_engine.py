@@ -152,9 +152,41 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
-def _ptr_array(ts):
-    """void *[len(ts)] of contiguous fp32 device tensors (None: a NULL array)."""
-    return None if ts is None else (C.c_void_p * len(ts))(*[_ptr(t).value for t in ts])
+def _addr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+def _ptr_array(ts, optional=False, size=None):
+    """void *[size or len(ts)] of contiguous fp32 device tensors, a None entry NULL (ts None, or `optional` and every entry
+    None: a NULL array)."""
+    if ts is None or (optional and all(t is None for t in ts)):
+        return None
+    return (C.c_void_p * (size or len(ts)))(*[None if t is None else _ptr(t).value for t in ts])
+
+
+def _set_ptrs(s, **lists):
+    """Fill the void *[N] fields of the ctypes struct `s` from lists of device tensors (a None list: the field stays NULL)."""
+    for field, ts in lists.items():
+        if ts is not None:
+            setattr(s, field, _ptr_array(ts, size=len(getattr(s, field))))
+
+
+def _fill_hist(h, hist):
+    """struct l2o_mlp_hist / l2o_confocal_hist from dict(st=, g=, m=, v=) of per-variable lists (m / v, or entries of them,
+    None for the DM nets).  Returns h."""
+    _set_ptrs(h, st=hist["st"], g=hist["g"], m=hist.get("m"), v=hist.get("v"))
+    return h
+
+
+def _check_confocal(name, d, lists, sim, img):
+    """The argument check the confocal entry points share: every list in `lists` (the variables first) holds
+    6 num_points + 1 tensors, the variables [batch] floats; sim exactly when not in inference mode, else img [batch, V]."""
+    nv, inference = 6 * d.num_points + 1, d.img is not None
+    if any(len(ts) != nv for ts in lists) or (sim is None) != inference or (sim is not None and len(sim) != nv):
+        raise ValueError("%s: %d variables for %d points" % (name, len(lists[0]), d.num_points))
+    if any(t.numel() != d.batch for t in lists[0]) \
+            or (inference and (img is None or img.numel() != d.batch * int(np.prod(d.roi)))):
+        raise ValueError("%s: every variable holds [batch] floats, img [batch, V]" % name)
 
 
 class HipEngine(object):
@@ -331,17 +363,11 @@ class HipEngine(object):
 
     def mlp_fg(self, d: MlpDesc, indices, w1, b1, w2, b2, loss, grads):
         """grads = (gw1, gb1, gw2, gb2) device tensors or None (forward only)."""
-        c = _abi.Mlp()
-        c.n_in, c.n_hidden, c.n_out, c.batch = d.n_in, d.n_hidden, d.n_out, d.batch
-        c.activation, c.n_data = d.activation, int(d.images.shape[0])
-        c.flags = _abi.MLP_GENERIC if _abi.get_option(_abi.OPT_MLP_GENERIC) else 0
-        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
+        c = self._cmlp(d)
         g = [None] * 4 if grads is None else [_ptr(t) for t in grads]
-        n = int(self.lib.l2o_mlp_scratch_floats(C.byref(c)))
-        if self._mlp_scratch is None or self._mlp_scratch.numel() < n:
-            self._mlp_scratch = self.empty(n)
+        scr = self._cached_buffer("_mlp_scratch", int(self.lib.l2o_mlp_scratch_floats(C.byref(c))))
         _abi.check(self.lib.l2o_mlp_fg(C.byref(c), C.c_void_p(indices.data_ptr()), _ptr(w1), _ptr(b1), _ptr(w2),
-                                       _ptr(b2), _ptr(loss), *g, _ptr(self._mlp_scratch), self._stream()))
+                                       _ptr(b2), _ptr(loss), *g, _ptr(scr), self._stream()))
 
     def _cmlp(self, d: MlpDesc):
         c = _abi.Mlp()
@@ -351,17 +377,20 @@ class HipEngine(object):
         c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
         return c
 
+    def _cached_buffer(self, attr, n, dtype=torch.float32):
+        """The device buffer cached as self.<attr>, replaced by a new one of n elements when it holds fewer: fp32 scratch
+        uninitialised, a uint8 workspace ZERO-FILLED (the library never clears a workspace and relies on that)."""
+        buf = self.__dict__.get(attr)
+        if buf is None or buf.numel() < n:
+            buf = (torch.zeros if dtype == torch.uint8 else torch.empty)(n, dtype=dtype, device=self.device)
+            setattr(self, attr, buf)
+        return buf
+
     def _step_scratch(self, entry, c):
         """The cached scratch of one step-path optimizee, grown to what <stem>_scratch_floats asks for the struct `c`; None
         where the library refuses the shape (a size of 0)."""
         n = int(getattr(self.lib, entry.stem + "_scratch_floats")(C.byref(c)))
-        if not n:
-            return None
-        scr = self.__dict__.get(entry.scratch)
-        if scr is None or scr.numel() < n:
-            scr = self.empty(n)
-            setattr(self, entry.scratch, scr)
-        return scr
+        return self._cached_buffer(entry.scratch, n) if n else None
 
     def mlp_deep_fg(self, d: MlpDeepDesc, indices, ws, loss, grads):
         """Loss and gradients of the MLP optimizee with SEVERAL hidden layers on ONE minibatch (l2o_mlp_deep_fg).  ws / grads:
@@ -416,12 +445,7 @@ class HipEngine(object):
         if scr is None:
             raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_confocal_fg: batch in [1, 1024], num_points in [1, 8], "
                                       "ROI edges in [2, 32] (got %d, %d, %r)" % (d.batch, d.num_points, tuple(d.roi)))
-        nv = entry.nvars(d)
-        if len(theta) != nv or (grads is not None and len(grads) != nv) or ((sim is None) != (d.img is not None)) \
-                or (sim is not None and len(sim) != nv):
-            raise ValueError("l2o_confocal_fg: %d variables for %d points" % (len(theta), d.num_points))
-        if any(t.numel() != d.batch for t in theta) or (d.img is not None and d.img.numel() != d.batch * int(np.prod(d.roi))):
-            raise ValueError("l2o_confocal_fg: every variable holds [batch] floats, img [batch, V]")
+        _check_confocal("l2o_confocal_fg", d, (theta,) if grads is None else (theta, grads), sim, d.img)
         _abi.check(self.lib.l2o_confocal_fg(C.byref(c), _ptr_array(theta), _ptr_array(sim), _ptr(loss), _ptr_array(grads),
                                             _ptr(scr), self._stream()))
 
@@ -443,38 +467,19 @@ class HipEngine(object):
         sim is None in inference mode).  hist: None, or dict(st=, g=, m=, v=) of such lists ([T, state], [T + 1, batch],
         [T + 1, batch] x 2; m / v None for the DM nets) that receive the history the meta-gradient needs
         (l2o_confocal_unroll_record)."""
-        nv = 6 * d.num_points + 1
-        if any(len(ts) != nv for ts in (xs, sts, ms, vs, scales)) or ((sim is None) != (d.img is not None)) \
-                or (sim is not None and len(sim) != nv):
-            raise ValueError("l2o_confocal_unroll: %d variables for %d points" % (len(xs), d.num_points))
-        if any(t.numel() != d.batch for t in xs) or (d.img is not None and d.img.numel() != d.batch * int(np.prod(d.roi))):
-            raise ValueError("l2o_confocal_unroll: every variable holds [batch] floats, img [batch, V]")
+        _check_confocal("l2o_confocal_unroll", d, (xs, sts, ms, vs, scales), sim, d.img)
         cc, cm = spec.to_c(), self._cconfocal(d)
         n = int(self.lib.l2o_confocal_unroll_scratch_floats(C.byref(cm), int(T)))
         if not n:
             raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_confocal_unroll: batch in [1, 1024], num_points in [1, 8], "
                                       "ROI edges in [2, 32] (got %d, %d, %r)" % (d.batch, d.num_points, tuple(d.roi)))
-        scr = self.__dict__.get("_confocal_unroll_scratch")
-        if scr is None or scr.numel() < n:
-            scr = self._confocal_unroll_scratch = self.empty(n)
-
-        def arr(ts, optional=False):
-            if ts is None or (optional and all(t is None for t in ts)):
-                return None
-            a = (C.c_void_p * nv)()
-            for k, t in enumerate(ts):
-                a[k] = None if t is None else _ptr(t).value
-            return a
-        args = (C.byref(cc), _ptr(wpack), C.byref(cm), arr(xs), arr(sts), arr(ms, True), arr(vs, True), arr(scales, True),
-                arr(sim), int(T), int(step0), _ptr(fx))
+        scr = self._cached_buffer("_confocal_unroll_scratch", n)
+        args = (C.byref(cc), _ptr(wpack), C.byref(cm), _ptr_array(xs), _ptr_array(sts), _ptr_array(ms, True),
+                _ptr_array(vs, True), _ptr_array(scales, True), _ptr_array(sim), int(T), int(step0), _ptr(fx))
         if hist is None:
             _abi.check(self.lib.l2o_confocal_unroll(*args, _ptr(scr), self._stream()))
             return
-        h = _abi.ConfocalHist()
-        for k in range(nv):
-            h.st[k], h.g[k] = hist["st"][k].data_ptr(), hist["g"][k].data_ptr()
-            h.m[k] = None if hist.get("m") is None or hist["m"][k] is None else hist["m"][k].data_ptr()
-            h.v[k] = None if hist.get("v") is None or hist["v"][k] is None else hist["v"][k].data_ptr()
+        h = _fill_hist(_abi.ConfocalHist(), hist)
         _abi.check(self.lib.l2o_confocal_unroll_record(*args, C.byref(h), _ptr(scr), self._stream()))
 
     def confocal_unroll_multi_supported(self, spec: NetSpec, d: ConfocalDesc, n_inst):
@@ -492,16 +497,9 @@ class HipEngine(object):
         one history dict per instance as confocal_unroll's `hist` (l2o_confocal_unroll_multi_record)."""
         if not hasattr(self.lib, "l2o_confocal_unroll_multi"):
             raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "libl2o_hip.so has no l2o_confocal_unroll_multi")
-        nv = 6 * d.num_points + 1
-        inference = d.img is not None
-        V = int(np.prod(d.roi))
         for i in insts:
-            if any(len(i[k]) != nv for k in ("xs", "sts", "ms", "vs", "scales")) \
-                    or (i.get("sim") is None) != inference or (not inference and len(i["sim"]) != nv):
-                raise ValueError("l2o_confocal_unroll_multi: %d variables for %d points" % (len(i["xs"]), d.num_points))
-            if any(t is not None and t.numel() != d.batch for t in i["xs"]) \
-                    or (inference and (i.get("img") is None or i["img"].numel() != d.batch * V)):
-                raise ValueError("l2o_confocal_unroll_multi: every variable holds [batch] floats, img [batch, V]")
+            _check_confocal("l2o_confocal_unroll_multi", d, [i[k] for k in ("xs", "sts", "ms", "vs", "scales")], i.get("sim"),
+                            i.get("img"))
         if hists is not None and len(hists) != len(insts):
             raise ValueError("l2o_confocal_unroll_multi: one history per instance")
         cc, cm = spec.to_c(), self._cconfocal(d)
@@ -510,30 +508,18 @@ class HipEngine(object):
             raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_confocal_unroll_multi: batch in [1, 1024], num_points in "
                                       "[1, 8], ROI edges in [2, 32], 1 to %d instances (got %d, %d, %r, %d)"
                                       % (_abi.CONFOCAL_MAX_INSTANCES, d.batch, d.num_points, tuple(d.roi), len(insts)))
-        scr = self.__dict__.get("_confocal_multi_scratch")
-        if scr is None or scr.numel() < n:
-            scr = self._confocal_multi_scratch = self.empty(n)
-
-        def ptr(t):
-            return None if t is None else _ptr(t).value
+        scr = self._cached_buffer("_confocal_multi_scratch", n)
         arr = (_abi.ConfocalInstance * len(insts))()
-        for j, i in enumerate(insts):
-            arr[j].fx = ptr(i["fx"])
-            arr[j].img = ptr(i.get("img")) if inference else None
-            for k in range(nv):
-                arr[j].x[k], arr[j].st[k] = ptr(i["xs"][k]), ptr(i["sts"][k])
-                arr[j].m[k], arr[j].v[k], arr[j].x_scale[k] = ptr(i["ms"][k]), ptr(i["vs"][k]), ptr(i["scales"][k])
-                arr[j].sim[k] = None if inference else ptr(i["sim"][k])
+        for a, i in zip(arr, insts):
+            a.fx, a.img = _ptr(i["fx"]), _ptr(i.get("img")) if d.img is not None else None
+            _set_ptrs(a, x=i["xs"], st=i["sts"], m=i["ms"], v=i["vs"], x_scale=i["scales"], sim=i.get("sim"))
         args = (C.byref(cc), _ptr(wpack), C.byref(cm), arr, len(insts), int(T), int(step0))
         if hists is None:
             _abi.check(self.lib.l2o_confocal_unroll_multi(*args, _ptr(scr), self._stream()))
             return
         harr = (_abi.ConfocalHist * len(hists))()
-        for j, h in enumerate(hists):
-            for k in range(nv):
-                harr[j].st[k], harr[j].g[k] = h["st"][k].data_ptr(), h["g"][k].data_ptr()
-                harr[j].m[k] = None if h.get("m") is None or h["m"][k] is None else h["m"][k].data_ptr()
-                harr[j].v[k] = None if h.get("v") is None or h["v"][k] is None else h["v"][k].data_ptr()
+        for h, hist in zip(harr, hists):
+            _fill_hist(h, hist)
         _abi.check(self.lib.l2o_confocal_unroll_multi_record(*args, harr, _ptr(scr), self._stream()))
 
     def mlp_unroll_supported(self, spec: NetSpec, d: MlpDesc):
@@ -548,26 +534,15 @@ class HipEngine(object):
         m / v None for the DM nets) that receive the history the meta-gradient needs (l2o_mlp_unroll_record)."""
         # the argument objects of a repeated launch (same buffers, same options: an evaluation loop, bench.py) are built
         # ONCE -- per call the host does a dict lookup and one ctypes call instead of ~0.1 ms of struct building
-        def ptr(t):
-            return 0 if t is None else t.data_ptr()
         key = (_abi.options_word(), id(d), spec.kind, spec.preprocess, tuple(spec.layers), float(spec.scale), bool(spec.tanh_output),
                float(spec.logsign_k), float(spec.beta1), float(spec.beta2), wpack.data_ptr(), indices.data_ptr(), int(T), hist is None,
-               tuple(ptr(t) for ts in (xs, sts, ms, vs, scales) for t in ts))
+               tuple(_addr(t) for ts in (xs, sts, ms, vs, scales) for t in ts))
         memo = self.__dict__.setdefault("_mlp_unroll_memo", {})
         ent = memo.get(key) if hist is None else None
         if ent is None:
             cc, cm = spec.to_c(), self._cmlp(d)
-            n = int(self.lib.l2o_mlp_unroll_workspace_bytes(C.byref(cm)))
-            ws = self.__dict__.get("_mlp_ws")
-            if ws is None or ws.numel() < n:
-                ws = self._mlp_ws = torch.zeros(n, dtype=torch.uint8, device=self.device)
-
-            def arr(ts):
-                a = (C.c_void_p * 4)()
-                for k, t in enumerate(ts):
-                    a[k] = None if t is None else t.data_ptr()
-                return a
-            ent = dict(cc=cc, cm=cm, ws=ws, arrs=(arr(xs), arr(sts), arr(ms), arr(vs), arr(scales)),
+            ws = self._cached_buffer("_mlp_ws", int(self.lib.l2o_mlp_unroll_workspace_bytes(C.byref(cm))), torch.uint8)
+            ent = dict(cc=cc, cm=cm, ws=ws, arrs=tuple(_ptr_array(ts) for ts in (xs, sts, ms, vs, scales)),
                        keep=(d, wpack, indices, list(xs), list(sts), list(ms), list(vs), list(scales)))
             if hist is None:
                 if len(memo) >= 8:
@@ -580,11 +555,7 @@ class HipEngine(object):
         self._last_ws = ws
         ax, ast, am, av, asc = ent["arrs"]
         if hist is not None:
-            h = _abi.MlpHist()
-            for k in range(4):
-                h.st[k], h.g[k] = hist["st"][k].data_ptr(), hist["g"][k].data_ptr()
-                h.m[k] = None if hist.get("m") is None or hist["m"][k] is None else hist["m"][k].data_ptr()
-                h.v[k] = None if hist.get("v") is None or hist["v"][k] is None else hist["v"][k].data_ptr()
+            h = _fill_hist(_abi.MlpHist(), hist)
             _abi.check(self.lib.l2o_mlp_unroll_record(C.byref(cc), _ptr(wpack), C.byref(cm), C.c_void_p(indices.data_ptr()),
                                                       ax, ast, am, av, asc, int(T), int(step0), _ptr(fx), C.byref(h),
                                                       C.c_void_p(ws.data_ptr()), self._stream()))
@@ -604,14 +575,12 @@ class HipEngine(object):
         mlp_unroll (all instances share the network, the data set and T / step0).  hists: None, or one history dict per
         instance as mlp_unroll's `hist` (l2o_mlp_unroll_multi_record).  The argument block of a repeated launch (same
         buffers) is built once."""
-        def ptr(t):
-            return 0 if t is None else t.data_ptr()
         hkey = None if hists is None else tuple(
-            tuple(ptr(t) for k in ("st", "g", "m", "v") for t in (h.get(k) or (None,) * 4)) for h in hists)
+            tuple(_addr(t) for k in ("st", "g", "m", "v") for t in (h.get(k) or (None,) * 4)) for h in hists)
         key = ("multi", _abi.options_word(), id(d), spec.kind, spec.preprocess, float(spec.scale), bool(spec.tanh_output),
                float(spec.logsign_k), float(spec.beta1), float(spec.beta2), wpack.data_ptr(), int(T),
-               tuple((ptr(i["indices"]), ptr(i["fx"])) + tuple(ptr(t) for k in ("xs", "sts", "ms", "vs", "scales") for t in i[k])
-                     for i in instances), hkey)
+               tuple((_addr(i["indices"]), _addr(i["fx"]))
+                     + tuple(_addr(t) for k in ("xs", "sts", "ms", "vs", "scales") for t in i[k]) for i in instances), hkey)
         memo = self.__dict__.setdefault("_mlp_unroll_memo", {})
         ent = memo.get(key)
         if ent is None:
@@ -619,27 +588,18 @@ class HipEngine(object):
             n = int(self.lib.l2o_mlp_unroll_multi_workspace_bytes(C.byref(cm), len(instances)))
             if not n:
                 raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_mlp_unroll_multi: unsupported shape / instance count")
-            ws = self.__dict__.get("_mlp_ws")
-            if ws is None or ws.numel() < n:
-                ws = self._mlp_ws = torch.zeros(n, dtype=torch.uint8, device=self.device)
+            ws = self._cached_buffer("_mlp_ws", n, torch.uint8)
             arr = (_abi.MlpInstance * len(instances))()
-            for j, i in enumerate(instances):
-                arr[j].indices, arr[j].fx = i["indices"].data_ptr(), i["fx"].data_ptr()
-                for k in range(4):
-                    arr[j].x[k], arr[j].st[k] = i["xs"][k].data_ptr(), i["sts"][k].data_ptr()
-                    arr[j].m[k] = None if i["ms"][k] is None else i["ms"][k].data_ptr()
-                    arr[j].v[k] = None if i["vs"][k] is None else i["vs"][k].data_ptr()
-                    arr[j].x_scale[k] = None if i["scales"][k] is None else i["scales"][k].data_ptr()
+            for a, i in zip(arr, instances):
+                a.indices, a.fx = i["indices"].data_ptr(), i["fx"].data_ptr()
+                _set_ptrs(a, x=i["xs"], st=i["sts"], m=i["ms"], v=i["vs"], x_scale=i["scales"])
             harr = None
             if hists is not None:
                 if len(hists) != len(instances):
                     raise ValueError("mlp_unroll_multi: one history per instance")
                 harr = (_abi.MlpHist * len(hists))()
-                for j, h in enumerate(hists):
-                    for k in range(4):
-                        harr[j].st[k], harr[j].g[k] = h["st"][k].data_ptr(), h["g"][k].data_ptr()
-                        harr[j].m[k] = None if h.get("m") is None or h["m"][k] is None else h["m"][k].data_ptr()
-                        harr[j].v[k] = None if h.get("v") is None or h["v"][k] is None else h["v"][k].data_ptr()
+                for h, hist in zip(harr, hists):
+                    _fill_hist(h, hist)
             ent = dict(cc=cc, cm=cm, ws=ws, arr=arr, harr=harr,
                        keep=(d, wpack, [dict(i) for i in instances], None if hists is None else [dict(h) for h in hists]))
             if len(memo) >= 8:
@@ -662,20 +622,14 @@ class HipEngine(object):
     #    buffers (the T steps of a recorded unroll); per call only what changes is passed ------------------
     def prepared_mlp_fg(self, d: MlpDesc, indices, w1, b1, w2, b2, grads):
         """Returns call(loss_ptr): l2o_mlp_fg with everything but the address of the loss slot fixed."""
-        c = _abi.Mlp()
-        c.n_in, c.n_hidden, c.n_out, c.batch = d.n_in, d.n_hidden, d.n_out, d.batch
-        c.activation, c.n_data = d.activation, int(d.images.shape[0])
-        c.flags = _abi.MLP_GENERIC if _abi.get_option(_abi.OPT_MLP_GENERIC) else 0
-        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
+        c = self._cmlp(d)
         g = [None] * 4 if grads is None else [_ptr(t) for t in grads]
-        n = int(self.lib.l2o_mlp_scratch_floats(C.byref(c)))
-        if self._mlp_scratch is None or self._mlp_scratch.numel() < n:
-            self._mlp_scratch = self.empty(n)
+        scr = self._cached_buffer("_mlp_scratch", int(self.lib.l2o_mlp_scratch_floats(C.byref(c))))
         cref, idx0 = C.byref(c), C.c_void_p(indices.data_ptr())
         mid = (_ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2))
-        tail = tuple(g) + (_ptr(self._mlp_scratch), self._stream())
+        tail = tuple(g) + (_ptr(scr), self._stream())
         fn, check = self.lib.l2o_mlp_fg, _abi.check
-        keep = (c, d, indices, w1, b1, w2, b2, grads, self._mlp_scratch)
+        keep = (c, d, indices, w1, b1, w2, b2, grads, scr)
 
         def call(loss_ptr, idx_ptr=None, _keep=keep):        # idx_ptr: another minibatch (device int32 [batch])
             rc = fn(cref, idx0 if idx_ptr is None else idx_ptr, *mid, loss_ptr, *tail)

@@ -3,7 +3,7 @@ l2o_mlp_fg + l2o_cwlstm_step per step (eager, planned with prepared calls, or re
 problems.mnist, and the persistent MLP unroll's recording form."""
 from __future__ import annotations
 
-import collections  # noqa: F401
+import collections
 import os
 
 import numpy as np
@@ -18,6 +18,16 @@ from ._graph_core import PackedState, _DevGrad, _LazyHost, _term_vars, _world, r
 # of them that draw a minibatch per evaluation (all but the last)
 _MULTIVAR = tuple(sorted(STEP_OPTIMIZEES))
 _SAMPLED = tuple(k for k in _MULTIVAR if STEP_OPTIMIZEES[k].sampled)
+
+# the optimizees that also have a fused unroll -- the T steps in ONE launch: the term's problem kind, the engine's
+# single-launch method (<method>_supported answers for a (net, descriptor) pair) and the kind's own conditions on the graph
+# and the term's variable count
+FusedUnroll = collections.namedtuple("FusedUnroll", "problem method applies")
+FUSED_UNROLLS = {
+    "mlp": FusedUnroll(_abi.PROB_MLP, "mlp_unroll", lambda g, nv: nv == 4),
+    "confocal": FusedUnroll(_abi.PROB_CONFOCAL, "confocal_unroll",
+                            lambda g, nv: g.terms[0].hyper.get("fused") and not g.second_derivatives),
+}
 
 
 class StepPlanMixin(object):
@@ -88,33 +98,57 @@ class StepPlanMixin(object):
         out = eng.to_numpy(fxbuf).reshape(n, L + 1)
         return [np.float32(out[k, L]) for k in range(n)]
 
-    def _run_mlp_unroll_record(self, T, step0, panels, slots, states, ms, vs, scales, fx, record):
-        """The recording form of the fused MLP unroll: history buffers (built once per set of variable buffers, like the
-        plan of _run_steps_planned, and handed to _backward in the same format) + one l2o_mlp_unroll_record launch."""
-        eng = self.engine
-        term = self.terms[0]
-        plan = self._mlp_hist_plan(T, panels, slots, states, ms, vs)
+    def _term_order(self, term, slots):
+        """(js, sis): the variables of `term`, in the order its entry points take them (problems.mnist: w1, b1, w2, b2), as
+        indices into self.x and into `slots`."""
         index_of = {v.decl.name: j for j, v in enumerate(self.x)}
-        js = [index_of[tv.name] for tv in _term_vars(term)]               # w1, b1, w2, b2 -> variable index
+        js = [index_of[tv.name] for tv in _term_vars(term)]
         slot_of = {s.var_index: si for si, s in enumerate(slots)}
-        sis = [slot_of[j] for j in js]
+        return js, [slot_of[j] for j in js]
+
+    def _fx_ring(self, T):
+        """The ring of loss buffers fx[0..T] of this unroll length (ONE tensor: a run of pending buffers is one contiguous
+        all-reduce): FX_RING of them on a sharded graph, one otherwise."""
+        ring = self._fx_cache.get(T)
+        if ring is None:
+            n = self.FX_RING if self.sharded else 1
+            store = self.engine.zeros(n, T + 1)
+            ring = self._fx_cache[T] = {"store": store, "bufs": [store[k] for k in range(n)], "work": [None] * n, "i": 0,
+                                        "pending": []}
+        return ring
+
+    def _confocal_sim(self, term):
+        """The live *_sim constants of a confocal term (a reset re-draws them); None in inference mode."""
+        return [self._by_name[c.name].value for c in term.consts["sim"]] or None
+
+    def _run_fused_unroll(self, kind, T, step0, panels, slots, states, ms, vs, scales, fx, record=None):
+        """The fused unroll of the ONE term (kind: a key of FUSED_UNROLLS): the per-variable lists gathered in the term's
+        order and one launch of the engine's single-launch method; with `record`, its recording form: the history buffers of
+        _mlp_hist_plan (built once per set of variable buffers, like the plan of _run_steps_planned), handed to _backward
+        in the step path's format."""
+        eng, term = self.engine, self.terms[0]
+        js, sis = self._term_order(term, slots)
         net = slots[sis[0]].net
-        eng.mlp_unroll(net.spec, net.wpack(eng), self._mlp_desc(term), self._mlp_idx[0],
-                       [panels[j] for j in js], [states[si].packed for si in sis], [ms[si] for si in sis],
-                       [vs[si] for si in sis], [scales[j] for j in js], T, step0, fx, hist=plan["hist"])
-        record.update(g=plan["g"], st=plan["st"], m=plan["m"], v=plan["v"], g_final=plan["g_final"], plan=plan)
+        plan = self._mlp_hist_plan(T, panels, slots, states, ms, vs) if record is not None else None
+        head = (net.spec, net.wpack(eng), self._mlp_desc(term))
+        lists = ([panels[j] for j in js], [states[si].packed for si in sis], [ms[si] for si in sis], [vs[si] for si in sis],
+                 [scales[j] for j in js])
+        hist = None if plan is None else plan["hist"]
+        if kind == "mlp":
+            eng.mlp_unroll(*head, self._mlp_idx[0], *lists, T, step0, fx, hist=hist)
+        else:
+            eng.confocal_unroll(*head, *lists, self._confocal_sim(term), T, step0, fx, hist=hist)
+        if record is not None:
+            record.update(g=plan["g"], st=plan["st"], m=plan["m"], v=plan["v"], g_final=plan["g_final"], plan=plan)
 
     def _mlp_hist_plan(self, T, panels, slots, states, ms, vs):
-        """The history buffers of a recording MLP unroll for this set of variable buffers (built once, kept while the
-        buffers stay): plan["hist"] in the argument order of l2o_mlp_unroll_record (w1, b1, w2, b2), and its per-step
-        views in the record format _backward reads.  Replicas.train_step hands the same to l2o_mlp_unroll_multi_record."""
+        """The history buffers of a recording fused unroll for this set of variable buffers (built once, kept while the
+        buffers stay): plan["hist"] in the argument order of l2o_mlp_unroll_record (w1, b1, w2, b2) /
+        l2o_confocal_unroll_record, and its per-step views in the record format _backward reads.  Replicas.train_step hands
+        the same to the multi-instance recording kernels."""
         eng = self.engine
-        term = self.terms[0]
         nvar = len(self.x)
-        index_of = {v.decl.name: j for j, v in enumerate(self.x)}
-        js = [index_of[tv.name] for tv in _term_vars(term)]               # w1, b1, w2, b2 -> variable index
-        slot_of = {s.var_index: si for si, s in enumerate(slots)}
-        sis = [slot_of[j] for j in js]
+        js, sis = self._term_order(self.terms[0], slots)
         key = (T, tuple(p.data_ptr() for p in panels), tuple(st.packed.data_ptr() for st in states),
                tuple(0 if m is None else m.data_ptr() for m in ms))
         plan = self.__dict__.get("_mlp_record_plan")
@@ -134,68 +168,39 @@ class StepPlanMixin(object):
                 g_final=[hist_g[j][T] for j in range(nvar)])
         return plan
 
-    def _mlp_unroll_ok(self, slots, states, scales):
-        """l2o_mlp_unroll applies: ONE problems.mnist term of weight 1 whose four variables are all stepped by the
-        same (20, 20) LSTM net, on an engine / device that has the fused kernel."""
-        eng = self.engine
-        if not hasattr(eng, "mlp_unroll") or os.environ.get("L2O_DISABLE_FUSED") or self.sharded:
+    def _fused_unroll_ok(self, kind, slots, states):
+        """What the engine's <method>_supported says (0: no) about the fused unroll of `kind` for this graph: ONE term of
+        that problem of weight 1, which meets the kind's own conditions, whose variables are all stepped by the same
+        (20, 20) LSTM net from packed states, on an engine that has the kernel."""
+        eng, entry = self.engine, FUSED_UNROLLS[kind]
+        if not hasattr(eng, entry.method) or os.environ.get("L2O_DISABLE_FUSED") or self.sharded:
             return 0
-        if len(self.terms) != 1 or self.terms[0].kind != _abi.PROB_MLP or self.terms[0].weight != 1.0:
+        if len(self.terms) != 1 or self.terms[0].kind != entry.problem or self.terms[0].weight != 1.0:
             return 0
-        tv = _term_vars(self.terms[0])
-        if len(tv) != 4 or len(self.x) != 4 or len(slots) != 4:
+        nv = len(_term_vars(self.terms[0]))
+        if len(self.x) != nv or len(slots) != nv or not entry.applies(self, nv):
             return 0
         net = slots[0].net
         for s, st in zip(slots, states):
             if s.net is not net or not isinstance(net, networks.StandardDeepLSTM) or not isinstance(st, PackedState) \
                     or st.packed is None:
                 return 0
-        return int(eng.mlp_unroll_supported(net.spec, self._mlp_desc(self.terms[0])))   # 2: the kernel's FAST form
+        return int(getattr(eng, entry.method + "_supported")(net.spec, self._mlp_desc(self.terms[0])))
+
+    def _mlp_unroll_ok(self, slots, states, scales):
+        """l2o_mlp_unroll applies (_fused_unroll_ok; 2: the kernel's FAST form) to ONE problems.mnist term with four
+        variables."""
+        return self._fused_unroll_ok("mlp", slots, states)
 
     def _confocal_unroll_ok(self, slots, states):
-        """l2o_confocal_unroll applies: ONE problems.confocal_microscopy_3d(fused=True) term of weight 1 whose variables are
-        all stepped by the same (20, 20) LSTM net, on an engine that has the fused kernel, for a shape the library takes."""
-        eng = self.engine
-        if not hasattr(eng, "confocal_unroll") or os.environ.get("L2O_DISABLE_FUSED") or self.sharded \
-                or self.second_derivatives:
-            return False
-        if len(self.terms) != 1 or self.terms[0].kind != _abi.PROB_CONFOCAL or self.terms[0].weight != 1.0 \
-                or not self.terms[0].hyper.get("fused"):
-            return False
-        nv = len(_term_vars(self.terms[0]))
-        if len(self.x) != nv or len(slots) != nv:
-            return False
-        net = slots[0].net
-        for s, st in zip(slots, states):
-            if s.net is not net or not isinstance(net, networks.StandardDeepLSTM) or not isinstance(st, PackedState) \
-                    or st.packed is None:
-                return False
-        return bool(eng.confocal_unroll_supported(net.spec, self._mlp_desc(self.terms[0])))
+        """l2o_confocal_unroll applies (_fused_unroll_ok) to ONE problems.confocal_microscopy_3d(fused=True) term, for a
+        shape the library takes, without second derivatives."""
+        return bool(self._fused_unroll_ok("confocal", slots, states))
 
-    def _run_confocal_unroll(self, T, step0, panels, slots, states, ms, vs, scales, fx, record=None):
-        """The fused confocal unroll (one l2o_confocal_unroll launch); with `record`, its recording form: the history
-        buffers of _mlp_hist_plan, handed to _backward in the step path's format."""
-        eng = self.engine
-        term = self.terms[0]
-        index_of = {v.decl.name: j for j, v in enumerate(self.x)}
-        js = [index_of[tv.name] for tv in _term_vars(term)]               # the reference's variable order -> variable index
-        slot_of = {s.var_index: si for si, s in enumerate(slots)}
-        sis = [slot_of[j] for j in js]
-        net = slots[sis[0]].net
-        sim = [self._by_name[c.name].value for c in term.consts["sim"]] or None
-        plan = self._mlp_hist_plan(T, panels, slots, states, ms, vs) if record is not None else None
-        eng.confocal_unroll(net.spec, net.wpack(eng), self._mlp_desc(term), [panels[j] for j in js],
-                            [states[si].packed for si in sis], [ms[si] for si in sis], [vs[si] for si in sis],
-                            [scales[j] for j in js], sim, T, step0, fx, hist=None if plan is None else plan["hist"])
-        if record is not None:
-            record.update(g=plan["g"], st=plan["st"], m=plan["m"], v=plan["v"], g_final=plan["g_final"], plan=plan)
-
-    def mlp_instance(self, feed=None, dry=False, draw=True):
-        """What this graph contributes to a launch of several optimizee instances (replicas.Replicas ->
-        l2o_mlp_unroll_multi): its minibatch indices (drawn here, like a launch of its own would), the live x / LSTM
-        state / moment buffers of the four variables in the order w1, b1, w2, b2 and its loss buffer -- or None when
-        the fused MLP unroll does not apply to it.  dry: no draw, no buffers -- only whether it applies.  draw=False: the
-        caller has filled self._mlp_idx[0] itself (Replicas draws the minibatches of all its replicas in one call)."""
+    def _fused_instance(self, kind, feed, dry, draw=False):
+        """What this graph contributes to a launch of several optimizee instances (replicas.Replicas): the network and the
+        descriptor, the live x / LSTM state / moment buffers in the term's variable order, its loss buffer and the kind's own
+        inputs -- or None when the fused unroll of `kind` does not apply to it.  dry: only whether it applies."""
         self._ensure_init()
         T = self.len_unroll
         feed = feed or {}
@@ -203,64 +208,37 @@ class StepPlanMixin(object):
             return None
         slots = self.slots
         states = [s.state for s in slots]
-        if not self._mlp_unroll_ok(slots, states, [None] * len(self.x)):
+        if not self._fused_unroll_ok(kind, slots, states):
             return None
         term = self.terms[0]
-        net = slots[0].net
-        desc = self._mlp_desc(term)
+        net, desc = slots[0].net, self._mlp_desc(term)
         if dry:
             return dict(net=net, desc=desc)
         if self.rnnprop and self.step not in feed:
             raise ValueError("You must feed a value for placeholder 'step' (DM/util.py:59-60)")
         if draw:
             self._draw_minibatches(T)
-        index_of = {v.decl.name: j for j, v in enumerate(self.x)}
-        js = [index_of[tv.name] for tv in _term_vars(term)]               # w1, b1, w2, b2 -> variable index
-        slot_of = {s.var_index: si for si, s in enumerate(slots)}
-        sis = [slot_of[j] for j in js]
+        js, sis = self._term_order(term, slots)
         panels = [v.value.view(*self._panel_shape(v)) for v in self.x]
-        ring = self._fx_cache.get(T)
-        if ring is None:
-            store = self.engine.zeros(1, T + 1)
-            ring = self._fx_cache[T] = {"store": store, "bufs": [store[0]], "work": [None], "i": 0, "pending": []}
-        return dict(net=net, desc=desc, indices=self._mlp_idx[0], xs=[panels[j] for j in js],
-                    sts=[states[si].packed for si in sis], ms=[slots[si].m for si in sis], vs=[slots[si].v for si in sis],
-                    scales=[None] * 4, fx=ring["bufs"][0])
+        inst = dict(net=net, desc=desc, xs=[panels[j] for j in js], sts=[states[si].packed for si in sis],
+                    ms=[slots[si].m for si in sis], vs=[slots[si].v for si in sis], scales=[None] * len(js),
+                    fx=self._fx_ring(T)["bufs"][0])
+        if kind == "mlp":
+            inst["indices"] = self._mlp_idx[0]
+        else:
+            inst.update(sim=self._confocal_sim(term), img=desc.img)
+        return inst
+
+    def mlp_instance(self, feed=None, dry=False, draw=True):
+        """This graph as one instance of l2o_mlp_unroll_multi (_fused_instance): the four variables in the order w1, b1, w2,
+        b2 and its minibatch `indices`, drawn here like a launch of its own would.  dry: no draw, no buffers.  draw=False:
+        the caller has filled self._mlp_idx[0] itself (Replicas draws the minibatches of all its replicas in one call)."""
+        return self._fused_instance("mlp", feed, dry, draw)
 
     def confocal_instance(self, feed=None, dry=False):
-        """mlp_instance's counterpart for problems.confocal_microscopy_3d(fused=True) (replicas.Replicas ->
-        l2o_confocal_unroll_multi): the live x / LSTM state / moment buffers in the term's variable order, the live *_sim
-        constants (None in inference mode, where `img` is this instance's target) and the loss buffer -- or None when the
-        fused confocal unroll does not apply to this graph.  dry: no buffers -- only whether it applies."""
-        self._ensure_init()
-        T = self.len_unroll
-        feed = feed or {}
-        if any(ph in feed for ph in self.scale):
-            return None
-        slots = self.slots
-        states = [s.state for s in slots]
-        if not self._confocal_unroll_ok(slots, states):
-            return None
-        term = self.terms[0]
-        net = slots[0].net
-        desc = self._mlp_desc(term)
-        if dry:
-            return dict(net=net, desc=desc)
-        if self.rnnprop and self.step not in feed:
-            raise ValueError("You must feed a value for placeholder 'step' (DM/util.py:59-60)")
-        index_of = {v.decl.name: j for j, v in enumerate(self.x)}
-        js = [index_of[tv.name] for tv in _term_vars(term)]               # the reference's variable order -> variable index
-        slot_of = {s.var_index: si for si, s in enumerate(slots)}
-        sis = [slot_of[j] for j in js]
-        panels = [v.value.view(*self._panel_shape(v)) for v in self.x]
-        sim = [self._by_name[c.name].value for c in term.consts["sim"]] or None
-        ring = self._fx_cache.get(T)
-        if ring is None:
-            store = self.engine.zeros(1, T + 1)
-            ring = self._fx_cache[T] = {"store": store, "bufs": [store[0]], "work": [None], "i": 0, "pending": []}
-        return dict(net=net, desc=desc, xs=[panels[j] for j in js], sts=[states[si].packed for si in sis],
-                    ms=[slots[si].m for si in sis], vs=[slots[si].v for si in sis], scales=[None] * len(js), sim=sim,
-                    img=desc.img, fx=ring["bufs"][0])
+        """This graph as one instance of l2o_confocal_unroll_multi (_fused_instance): with the live *_sim constants as `sim`
+        (None in inference mode, where `img` is this instance's target)."""
+        return self._fused_instance("confocal", feed, dry)
 
     def _draw_minibatches(self, T):
         """A fresh uniform minibatch per evaluation of a neural optimizee (DM/problems.py:282-286: tf.random_uniform
@@ -334,7 +312,7 @@ class StepPlanMixin(object):
         call = getattr(eng, entry.method)
         if term.kind == _abi.PROB_CONFOCAL:
             # no minibatch; the simulation parameters are the live constants (a reset re-draws them)
-            sim = [self._by_name[c.name].value for c in term.consts["sim"]] or None
+            sim = self._confocal_sim(term)
             return lambda t, xin, out, grads: call(d, xin, sim, out, grads)
         idx = self._mlp_idx[k]
         return lambda t, xin, out, grads: call(d, idx[t], xin, out, grads)

@@ -456,13 +456,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
         # fx[0..T] of this launch.  Sharded runs all-reduce it ASYNCHRONOUSLY (the next unroll
         # does not wait for the 404-byte collective); the buffers rotate so that a collective in
         # flight is never overwritten, and every reader goes through wait_fx().
-        key = T
-        ring = self._fx_cache.get(key)
-        if ring is None:
-            n = self.FX_RING if self.sharded else 1
-            store = eng.zeros(n, T + 1)                      # (ONE tensor: a run of pending buffers is one contiguous all-reduce)
-            ring = self._fx_cache[key] = {"store": store, "bufs": [store[k] for k in range(n)], "work": [None] * n, "i": 0,
-                                          "pending": []}
+        ring = self._fx_ring(T)
         fused_path = record is None and self._fused_ok(descs)
         if restart_fused and not fused_path:
             self.rewind(restart)                            # (panels / states are views of the live tensors: still valid)
@@ -516,14 +510,14 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
             self.last_path = "mlp_unroll"
             self._draw_minibatches(T)
             record.update(step0=step0, shapes=[tuple(pn.shape) for pn in panels])
-            self._run_mlp_unroll_record(T, step0, panels, slots, states, ms, vs, scales, fx, record)
+            self._run_fused_unroll("mlp", T, step0, panels, slots, states, ms, vs, scales, fx, record=record)
             if events is not None:
                 events[1].record()
         elif record is not None and self._confocal_unroll_ok(slots, states):
             # meta-gradient on the confocal optimizee (fused=True): the T steps and their history in ONE launch
             self.last_path = "confocal_unroll"
             record.update(step0=step0, shapes=[tuple(pn.shape) for pn in panels])
-            self._run_confocal_unroll(T, step0, panels, slots, states, ms, vs, scales, fx, record=record)
+            self._run_fused_unroll("confocal", T, step0, panels, slots, states, ms, vs, scales, fx, record=record)
             if events is not None:
                 events[1].record()
         elif record is not None:                           # meta-gradient: needs the per-step history
@@ -556,22 +550,14 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
             self._draw_minibatches(T)
             if commit and not _recovering and self._wants_snapshot(False):
                 self._snapshot(slots)
-            term = self.terms[0]
-            index_of = {v.decl.name: j for j, v in enumerate(self.x)}
-            js = [index_of[tv.name] for tv in _term_vars(term)]
-            slot_of = {s.var_index: si for si, s in enumerate(slots)}
-            sis = [slot_of[j] for j in js]
-            net = slots[sis[0]].net
-            eng.mlp_unroll(net.spec, net.wpack(eng), self._mlp_desc(term), self._mlp_idx[0],
-                           [panels[j] for j in js], [states[si].packed for si in sis], [ms[si] for si in sis],
-                           [vs[si] for si in sis], [scales[j] for j in js], T, step0, fx)
+            self._run_fused_unroll("mlp", T, step0, panels, slots, states, ms, vs, scales, fx)
             if events is not None:
                 events[1].record()
         elif self._confocal_unroll_ok(slots, states):
             # the confocal optimizee (fused=True), every variable stepped by one LSTM net: one workgroup per batch row runs
             # the T steps in ONE launch (no workgroup waits for another: no status word)
             self.last_path = "confocal_unroll"
-            self._run_confocal_unroll(T, step0, panels, slots, states, ms, vs, scales, fx)
+            self._run_fused_unroll("confocal", T, step0, panels, slots, states, ms, vs, scales, fx)
             if events is not None:
                 events[1].record()
         else:

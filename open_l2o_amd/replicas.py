@@ -26,6 +26,7 @@ Every instance draws its own initial weights and its own minibatches, exactly as
 """
 from __future__ import annotations
 
+import collections
 import os
 import warnings
 
@@ -40,6 +41,26 @@ from ._graph_core import _DevGrad, _all_reduce, _world
 def _confocal_shape(d):
     """What the instances of one l2o_confocal_unroll_multi launch share (ONE descriptor)."""
     return (int(d.batch), int(d.num_points), tuple(int(r) for r in d.roi), d.img is not None)
+
+
+def _mismatch(form, inst, first):
+    """`inst` cannot ride in the launch that `first` opened (None: the form's fused unroll does not apply to its graph)."""
+    if inst is None or inst["net"] is not first["net"]:
+        return True
+    if form == "rows":
+        return _confocal_shape(inst["desc"]) != _confocal_shape(first["desc"])
+    return inst["desc"] is not first["desc"]                 # (ONE data set: one descriptor object)
+
+
+# The forms that run several instances per launch: the graph method that describes one instance, the engine's launch method
+# (<multi>_supported answers for a net, a descriptor and an instance count), the instances per launch, the graphs' last_path
+# stamp, whether every unroll draws minibatches, and whether the kernel leaves a status word to check (workgroups that wait
+# for partner workgroups can time out)
+MultiForm = collections.namedtuple("MultiForm", "instance multi per_launch last_path sampled status")
+MULTI_FORMS = {
+    "xcd": MultiForm("mlp_instance", "mlp_unroll_multi", 8, "mlp_xcd", True, True),
+    "rows": MultiForm("confocal_instance", "confocal_unroll_multi", _abi.CONFOCAL_MAX_INSTANCES, "confocal_multi", False, False),
+}
 
 
 class Replicas(object):
@@ -89,42 +110,44 @@ class Replicas(object):
                 out[ph] = val
         return out
 
-    def xcd_supported(self):
-        g = self.graphs[0]
-        eng = g.engine
-        if not hasattr(eng, "mlp_unroll_multi") or os.environ.get("L2O_DISABLE_FUSED"):
+    def _form_supported(self, form, graphs):
+        """The engine has the form's kernel, the form's fused unroll applies to every graph in `graphs`, they can share a
+        launch, and the library takes the shape for as many instances as a launch would hold."""
+        f, eng = MULTI_FORMS[form], self.graphs[0].engine
+        if not hasattr(eng, f.multi) or os.environ.get("L2O_DISABLE_FUSED"):
             return False
-        inst = g.mlp_instance(None, dry=True)
-        return inst is not None and eng.mlp_unroll_multi_supported(inst["net"].spec, inst["desc"], min(8, len(self.graphs)))
+        first = None
+        for g in graphs:
+            inst = getattr(g, f.instance)(None, dry=True)
+            first = first or inst
+            if _mismatch(form, inst, first):
+                return False
+        return bool(getattr(eng, f.multi + "_supported")(first["net"].spec, first["desc"], min(f.per_launch, len(self.graphs))))
+
+    def xcd_supported(self):
+        """Form "xcd" applies to the first replica (run / train_step hold the others against it when they launch)."""
+        return self._form_supported("xcd", self.graphs[:1])
 
     def rows_supported(self):
         """Form "rows" applies: every replica is a problems.confocal_microscopy_3d(fused=True) term of ONE shape whose
         variables are all stepped by one (20, 20) LSTM network, on an engine that has l2o_confocal_unroll_multi."""
-        eng = self.graphs[0].engine
-        if not hasattr(eng, "confocal_unroll_multi") or os.environ.get("L2O_DISABLE_FUSED"):
-            return False
-        first = None
-        for g in self.graphs:
-            inst = g.confocal_instance(None, dry=True)
-            if inst is None:
-                return False
-            if first is None:
-                first = inst
-            elif inst["net"] is not first["net"] or _confocal_shape(inst["desc"]) != _confocal_shape(first["desc"]):
-                return False
-        return bool(eng.confocal_unroll_multi_supported(first["net"].spec, first["desc"],
-                                                        min(_abi.CONFOCAL_MAX_INSTANCES, len(self.graphs))))
+        return self._form_supported("rows", self.graphs)
 
-    def _launch_rows(self, feed, record=False):
-        """ENQUEUE one committed unroll of every replica on form "rows": launches of up to CONFOCAL_MAX_INSTANCES instances,
-        in the replicas' order.  record: the recording form, every replica's history into its graph's record plan.
-        Returns (instances, records or None)."""
-        graphs = self.graphs
+    def _launch_multi(self, form, feed, record=False, who="run"):
+        """ENQUEUE one committed unroll of every replica on `form` ("xcd" / "rows"): launches of up to the form's instance
+        count, in the replicas' order.  record: the recording kernel, every replica's history into its graph's record plan
+        (built once per set of variable buffers).  who: the public method a refusal names.  Returns (instances, per-replica
+        records or None)."""
+        f, graphs, T = MULTI_FORMS[form], self.graphs, self.len_unroll
         eng = graphs[0].engine
-        T = self.len_unroll
-        insts = [g.confocal_instance(self._feed(g, feed)) for g in graphs]
-        if any(i is None for i in insts):
-            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "Replicas: l2o_confocal_unroll_multi does not apply")
+        feed = feed or {}
+        kw = {"draw": not self._draw_all()} if f.sampled else {}
+        insts = [getattr(g, f.instance)(self._feed(g, feed), **kw) for g in graphs]
+        if any(_mismatch(form, i, insts[0]) for i in insts):
+            if form == "rows":
+                raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "Replicas: l2o_confocal_unroll_multi does not apply")
+            raise ValueError("Replicas.%s: the replicas must be problems.mnist instances over ONE data set, stepped by one "
+                             "(20, 20) LSTM network" % who)
         step0 = int(feed[graphs[0].step]) if graphs[0].rnnprop else 1
         hists = recs = None
         if record:
@@ -137,15 +160,20 @@ class Replicas(object):
                                  v=plan["v"], g_final=plan["g_final"], plan=plan))
                 hists.append(plan["hist"])
         net, desc = insts[0]["net"], insts[0]["desc"]
-        wpack = net.wpack(eng)
-        n = _abi.CONFOCAL_MAX_INSTANCES
+        wpack, launch, n = net.wpack(eng), getattr(eng, f.multi), f.per_launch
         for k in range(0, len(insts), n):
-            eng.confocal_unroll_multi(net.spec, wpack, desc, insts[k:k + n], T, step0,
-                                      hists=None if hists is None else hists[k:k + n])
-        self.last_form = "rows"
+            launch(net.spec, wpack, desc, insts[k:k + n], T, step0, hists=None if hists is None else hists[k:k + n])
+        self.last_form = form
         for g in graphs:
-            g.last_path = "confocal_multi"
+            g.last_path = f.last_path
         return insts, recs
+
+    def _record_xcd(self, feed, step0):
+        """The forward of a train step on form "xcd" (_launch_multi, recording) as [(record, fx device [T + 1])] per replica;
+        step0 is what `feed` says (1 without RNNProp's `step`)."""
+        insts, recs = self._launch_multi("xcd", feed, record=True, who="train_step")
+        assert all(rec["step0"] == step0 for rec in recs)
+        return [(rec, inst["fx"]) for rec, inst in zip(recs, insts)]
 
     def _draw_all(self):
         """The minibatch indices of ALL replicas in one device draw (one torch generator call instead of one per replica;
@@ -171,23 +199,8 @@ class Replicas(object):
         synchronising the host, without a recovery snapshot and without a status check -- the caller syncs and calls
         engine.check_unroll_status() itself (bench.py's timed region).  Confocal replicas (rows_supported()) go out on
         form "rows" instead, which has no status to check.  Returns the replicas' loss buffers (device, [T + 1])."""
-        graphs = self.graphs
-        eng = graphs[0].engine
-        if self.rows_supported():
-            return [i["fx"] for i in self._launch_rows(feed or {})[0]]
-        drew = self._draw_all()
-        insts = [g.mlp_instance(self._feed(g, feed), draw=not drew) for g in graphs]
-        if any(i is None for i in insts):
-            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "Replicas.launch: l2o_mlp_unroll_multi does not apply")
-        net, desc = insts[0]["net"], insts[0]["desc"]
-        step0 = int(feed[graphs[0].step]) if graphs[0].rnnprop else 1
-        wpack = net.wpack(eng)
-        for k in range(0, len(insts), 8):
-            eng.mlp_unroll_multi(net.spec, wpack, desc, insts[k:k + 8], self.len_unroll, step0)
-        self.last_form = "xcd"
-        for g in graphs:
-            g.last_path = "mlp_xcd"
-        return [i["fx"] for i in insts]
+        form = "rows" if self.rows_supported() else "xcd"
+        return [i["fx"] for i in self._launch_multi(form, feed, who="launch")[0]]
 
     def run(self, feed=None, form="auto"):
         """One committed unroll of every replica from its current variables (== N x sess.run([fx, update])).
@@ -202,7 +215,7 @@ class Replicas(object):
             if not self.rows_supported():
                 raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "Replicas.run(form='rows'): l2o_confocal_unroll_multi does "
                                           "not apply to these optimizees / this network / engine")
-            insts, _ = self._launch_rows(feed or {})
+            insts, _ = self._launch_multi("rows", feed)
             fx_host = [eng.to_numpy(i["fx"]) for i in insts]    # host sync; nothing to check or to recover from
             self.fx_arrays = fx_host
             return np.array([f[self.len_unroll] for f in fx_host], np.float32)
@@ -216,24 +229,13 @@ class Replicas(object):
             outs = [g.execute(self._feed(g, feed), True) for g in graphs]
             self.fx_arrays = [o["fx_array"] for o in outs]
             return np.array([o["fx"] for o in outs], np.float32)
-        self.last_form = "xcd"
-        step0 = int(feed[graphs[0].step]) if graphs[0].rnnprop else 1
         recover = not os.environ.get("L2O_NO_RECOVERY")
-        insts = []
-        drew = self._draw_all()
-        for g in graphs:
-            inst = g.mlp_instance(self._feed(g, feed), draw=not drew)
-            if inst is None or (insts and (inst["desc"] is not insts[0]["desc"] or inst["net"] is not insts[0]["net"])):
-                raise ValueError("Replicas.run: the replicas must be problems.mnist instances over ONE data set, stepped by "
-                                 "one (20, 20) LSTM network")
-            if recover:
+        if recover:                                          # (the kernel runs in place and its teams can time out)
+            for g in graphs:
+                g._ensure_init()
                 g._last_launch = {"restart": None, "snapshot": False, "commit": True}
                 g._snapshot(g.slots)
-            insts.append(inst)
-        net, desc = insts[0]["net"], insts[0]["desc"]
-        wpack = net.wpack(eng)
-        for k in range(0, len(insts), 8):
-            eng.mlp_unroll_multi(net.spec, wpack, desc, insts[k:k + 8], T, step0)
+        insts, _ = self._launch_multi("xcd", feed)
         if hasattr(eng, "prefetch_unroll_status"):
             eng.prefetch_unroll_status()
         fx_host = [eng.to_numpy(i["fx"]) for i in insts]    # host sync
@@ -259,8 +261,8 @@ class Replicas(object):
                 finally:
                     g._reuse_minibatches = False
             self.last_form = "steps (recovered)"
-        for g in graphs:
-            g.last_path = "mlp_xcd"
+            for g in graphs:
+                g.last_path = "mlp_xcd"
         self.fx_arrays = fx_host
         return np.array([f[T] for f in fx_host], np.float32)
 
@@ -268,22 +270,21 @@ class Replicas(object):
     def _check_shared(self):
         """The replicas of a train step: problems.mnist over ONE data set -- or problems.confocal_microscopy_3d of ONE
         shape --, all variables stepped by ONE network, without second derivatives."""
-        g0 = self.graphs[0]
-        if all(len(g.terms) == 1 and g.terms[0].kind == _abi.PROB_CONFOCAL for g in self.graphs):
-            for g in self.graphs:
-                g._ensure_init()
-                if (g.second_derivatives or len({id(s.net) for s in g.slots}) != 1 or g.slots[0].net is not g0.slots[0].net
-                        or _confocal_shape(g._mlp_desc(g.terms[0])) != _confocal_shape(g0._mlp_desc(g0.terms[0]))):
-                    raise ValueError("Replicas.train_step: confocal replicas must be problems.confocal_microscopy_3d instances "
-                                     "of ONE shape, stepped by one LSTM network, without second derivatives")
-            return
+        confocal = all(len(g.terms) == 1 and g.terms[0].kind == _abi.PROB_CONFOCAL for g in self.graphs)
+        kind, form, what = (_abi.PROB_MLP, "xcd", "the replicas must be problems.mnist instances over ONE data set")
+        if confocal:
+            kind, form, what = (_abi.PROB_CONFOCAL, "rows",
+                                "confocal replicas must be problems.confocal_microscopy_3d instances of ONE shape")
+        first = None
         for g in self.graphs:
             g._ensure_init()
-            nets = {id(s.net) for s in g.slots}
-            if (g.second_derivatives or len(g.terms) != 1 or g.terms[0].kind != _abi.PROB_MLP or len(nets) != 1
-                    or g.slots[0].net is not g0.slots[0].net or g._mlp_desc(g.terms[0]) is not g0._mlp_desc(g0.terms[0])):
-                raise ValueError("Replicas.train_step: the replicas must be problems.mnist instances over ONE data set, stepped "
-                                 "by one LSTM network, without second derivatives")
+            inst = None
+            if not g.second_derivatives and len(g.terms) == 1 and g.terms[0].kind == kind \
+                    and len({id(s.net) for s in g.slots}) == 1:
+                inst = dict(net=g.slots[0].net, desc=g._mlp_desc(g.terms[0]))
+            first = first or inst
+            if _mismatch(form, inst, first):                 # (the rule of the form's launches, on any engine)
+                raise ValueError("Replicas.train_step: %s, stepped by one LSTM network, without second derivatives" % what)
 
     def _sync_weights(self):
         """Every rank starts from rank 0's network weights (once per Replicas): the meta-gradient is averaged over the
@@ -297,35 +298,6 @@ class Replicas(object):
             for m, d in box[0][key].items():
                 for v, a in d.items():
                     net.assign(m, v, a)
-
-    def _record_xcd(self, feed, step0):
-        """The forward of a train step on the one-instance-per-XCD recording kernel (l2o_mlp_unroll_multi_record):
-        launches of up to eight replicas; every replica's history goes to its own buffers (its graph's record plan,
-        built once per set of variable buffers).  Returns [(record, fx device [T + 1])] per replica."""
-        graphs = self.graphs
-        eng = graphs[0].engine
-        T = self.len_unroll
-        drew = self._draw_all()
-        insts, hists, out = [], [], []
-        for g in graphs:
-            inst = g.mlp_instance(self._feed(g, feed), draw=not drew)
-            if inst is None or (insts and (inst["desc"] is not insts[0]["desc"] or inst["net"] is not insts[0]["net"])):
-                raise ValueError("Replicas.train_step: the replicas must be problems.mnist instances over ONE data set, "
-                                 "stepped by one (20, 20) LSTM network")
-            slots = g.slots
-            panels = [v.value.view(*g._panel_shape(v)) for v in g.x]
-            plan = g._mlp_hist_plan(T, panels, slots, [s.state for s in slots], [s.m for s in slots], [s.v for s in slots])
-            rec = dict(step0=step0, shapes=[tuple(p.shape) for p in panels], g=plan["g"], st=plan["st"], m=plan["m"],
-                       v=plan["v"], g_final=plan["g_final"], plan=plan)
-            insts.append(inst)
-            hists.append(plan["hist"])
-            out.append((rec, inst["fx"]))
-            g.last_path = "mlp_xcd"
-        net, desc = insts[0]["net"], insts[0]["desc"]
-        wpack = net.wpack(eng)
-        for k in range(0, len(insts), 8):
-            eng.mlp_unroll_multi(net.spec, wpack, desc, insts[k:k + 8], T, step0, hists=hists[k:k + 8])
-        return out
 
     def train_step(self, feed, learning_rate, form="auto"):
         """One meta-training step on all N replicas, which share the optimizer's networks: loss L = (1/N) sum_r sum_t
@@ -364,11 +336,10 @@ class Replicas(object):
             raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "Replicas.train_step(form='xcd'): l2o_mlp_unroll_multi_record "
                                       "does not apply to this optimizee / network / device")
         if use_rows:                                        # (no exchange: no status word guards the update)
-            insts, recs = self._launch_rows(feed, record=True)
+            insts, recs = self._launch_multi("rows", feed, record=True, who="train_step")
             runs = [(rec, inst["fx"]) for rec, inst in zip(recs, insts)]
             fused = False
         elif use_xcd:
-            self.last_form = "xcd"
             runs = self._record_xcd(feed, step0)
             fused = hasattr(eng, "check_unroll_status")
         else:
