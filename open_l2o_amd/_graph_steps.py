@@ -55,13 +55,9 @@ class StepPlanMixin(object):
                 else:
                     rows.append(np.asarray(sampler(L + 1, d.batch, d.images.shape[0])).reshape(L + 1, d.batch))
             idx = eng.int_tensor(np.stack(rows))             # [n, L + 1, batch]
-        index_of = {v.decl.name: j for j, v in enumerate(self.x)}
-        js = [index_of[tv.name] for tv in _term_vars(term)]
-        panels = []
-        for v in self.x:
-            B, D = self._panel_shape(v)
-            panels.append(v.value.view(B, D))
         slots = self.slots
+        js, _ = self._term_order(term, slots)
+        panels = [v.value.view(*self._panel_shape(v)) for v in self.x]
         key = (tuple(p.data_ptr() for p in panels), tuple(s.state.packed.data_ptr() for s in slots),
                tuple(0 if s.m is None else s.m.data_ptr() for s in slots))
         plan = self.__dict__.get("_eval_plan")
@@ -141,6 +137,26 @@ class StepPlanMixin(object):
         if record is not None:
             record.update(g=plan["g"], st=plan["st"], m=plan["m"], v=plan["v"], g_final=plan["g_final"], plan=plan)
 
+    def _fused_hist_plan(self, T, panel, packed):
+        """The history buffers of the recording l2o_unroll (and the per-step views of them, and the BPTT pointer table that
+        _bptt_panels keeps in this dict): they live as long as the unroll keeps its shape."""
+        eng, rn = self.engine, bool(self.rnnprop)
+        B, D = panel.shape
+        N = B * D
+        key = (T, B, D, packed.numel(), rn)
+        fp = self.__dict__.get("_fused_plan")
+        if fp is None or fp["key"] != key:
+            hist = {"st": eng.empty(T, packed.numel()), "g": eng.empty(T, N), "g_final": eng.empty(N)}
+            if rn:
+                hist.update(m=eng.empty(T, N), v=eng.empty(T, N))
+            fp = self.__dict__["_fused_plan"] = dict(
+                key=key, hist=hist,
+                g=[[hist["g"][t].view(B, D)] for t in range(T)], st=[[hist["st"][t]] for t in range(T)],
+                m=[[hist["m"][t].view(B, D) if rn else None] for t in range(T)],
+                v=[[hist["v"][t].view(B, D) if rn else None] for t in range(T)],
+                g_final=[hist["g_final"].view(B, D)])
+        return fp
+
     def _mlp_hist_plan(self, T, panels, slots, states, ms, vs):
         """The history buffers of a recording fused unroll for this set of variable buffers (built once, kept while the
         buffers stay): plan["hist"] in the argument order of l2o_mlp_unroll_record (w1, b1, w2, b2) /
@@ -214,8 +230,7 @@ class StepPlanMixin(object):
         net, desc = slots[0].net, self._mlp_desc(term)
         if dry:
             return dict(net=net, desc=desc)
-        if self.rnnprop and self.step not in feed:
-            raise ValueError("You must feed a value for placeholder 'step' (DM/util.py:59-60)")
+        self._step0(feed)                                    # (a missing `step` raises)
         if draw:
             self._draw_minibatches(T)
         js, sis = self._term_order(term, slots)
@@ -441,7 +456,6 @@ class StepPlanMixin(object):
                 states[si].packed.copy_(hs[T])
                 if hm is not None:
                     ms[si].copy_(hm[T].view(ms[si].shape)); vs[si].copy_(hv[T].view(vs[si].shape))
-
 
     # -- the recorded unroll of a neural optimizee as a PLAN: buffers and ctypes arguments built once ------
     def _plan_ok(self, slots, states, nvar):

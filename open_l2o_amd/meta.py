@@ -42,6 +42,19 @@ from ._graph_steps import StepPlanMixin, _SAMPLED, _MULTIVAR
 
 MetaLoss = collections.namedtuple("MetaLoss", "loss, update, reset, fx, x")     # DM/meta.py:158
 MetaStep = collections.namedtuple("MetaStep", "step, update, reset, fx, x")     # DM/meta.py:159
+# one UnrollGraph.launch: what it works on (_launch_buffers) and what its caller asked for; fold: `restart` goes into the
+# fused kernel; fast: the prepared-call key of _replay_prepared
+_LaunchBuffers = collections.namedtuple("_LaunchBuffers", "scales step0 xs states ms vs descs panels")
+_LaunchOpts = collections.namedtuple("_LaunchOpts", "commit recovering restart fold fast use_graph")
+
+
+def _copy_all(dst, src):
+    """dst[k] <- src[k]: ONE multi-tensor launch where torch has it."""
+    if hasattr(torch, "_foreach_copy_") and len(dst) > 1:
+        torch._foreach_copy_(dst, src)
+    else:
+        for d_, s_ in zip(dst, src):
+            d_.copy_(s_)
 
 
 # ---------------------------------------------------------------------------
@@ -62,21 +75,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
         loss = make_loss()                                            # _get_variables, :293
         self.terms = list(loss.terms)
         decls = list(loss.variables)
-        batched_kinds = (_abi.PROB_QUADRATIC, _abi.PROB_LASSO, _abi.PROB_RASTRIGIN, _abi.PROB_SQUARE_COS)
-        self.sharded = self.world > 1 and all(t.kind in batched_kinds for t in self.terms)
-        if self.world > 1 and any(t.kind == _abi.PROB_CONFOCAL for t in self.terms):
-            raise NotImplementedError("problems.confocal_microscopy_3d is not implemented for a sharded graph (world size "
-                                      "%d): its batch rows are not split over ranks" % self.world)
-        B_global = decls[0].shape[0] if self.sharded else None
-        if self.sharded:
-            if any(d.shape[0] != B_global for d in decls if not getattr(d, "shared", False)):
-                raise ValueError("cannot shard: variables disagree on the batch dimension")
-            if B_global % self.world:
-                raise ValueError("batch_size %d is not divisible by world size %d" % (B_global, self.world))
-            per = B_global // self.world
-            self.shard = (self.rank * per, (self.rank + 1) * per)
-        else:
-            self.shard = None
+        self.sharded, self.shard = self._shard_of(decls)
         by_name = {}
         self.x, self.constants = [], []
         for d in decls:
@@ -118,6 +117,22 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
         self._fx_cache = {}
         self.last_path = None
         self.second_derivatives = False
+
+    def _shard_of(self, decls):
+        """(sharded, this rank's contiguous slice of the batch or None): the batched analytic problems under torch.distributed."""
+        batched_kinds = (_abi.PROB_QUADRATIC, _abi.PROB_LASSO, _abi.PROB_RASTRIGIN, _abi.PROB_SQUARE_COS)
+        if self.world > 1 and any(t.kind == _abi.PROB_CONFOCAL for t in self.terms):
+            raise NotImplementedError("problems.confocal_microscopy_3d is not implemented for a sharded graph (world size "
+                                      "%d): its batch rows are not split over ranks" % self.world)
+        if not (self.world > 1 and all(t.kind in batched_kinds for t in self.terms)):
+            return False, None
+        B_global = decls[0].shape[0]
+        if any(d.shape[0] != B_global for d in decls if not getattr(d, "shared", False)):
+            raise ValueError("cannot shard: variables disagree on the batch dimension")
+        if B_global % self.world:
+            raise ValueError("batch_size %d is not divisible by world size %d" % (B_global, self.world))
+        per = B_global // self.world
+        return True, (self.rank * per, (self.rank + 1) * per)
 
     # -- geometry helpers ----------------------------------------------------
     def _panel_shape(self, var):
@@ -189,12 +204,16 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
     def execute(self, feed, commit):
         """Run one unroll from the current variables.  Returns dict(loss, fx, x) on the host."""
         fx, xs = self.launch(feed, commit)
-        eng = self.engine
-        T = self.len_unroll
         fx_host, fx, xs = self._sync_or_recover(fx, xs, feed, commit)
-        x_out = _LazyHost(eng, xs, [self._local_shape(var) for var in self.x])   # copied to the host only if fetched
+        return self._result(fx_host, xs)
+
+    def _result(self, fx_host, xs):
+        """What execute / train_step return; fx_host None: a deferred step, whose losses nobody has read back."""
+        x_out = _LazyHost(self.engine, xs, [self._local_shape(var) for var in self.x])   # copied to the host only if fetched
+        if fx_host is None:
+            return {"loss": None, "fx": None, "fx_array": None, "x": x_out}
         # (host NumPy on the T + 1 losses already copied back: loss = tf.reduce_sum(fx_array), DM/meta.py:376)
-        return {"loss": np.float32(fx_host.sum(dtype=np.float32)), "fx": np.float32(fx_host[T]),
+        return {"loss": np.float32(fx_host.sum(dtype=np.float32)), "fx": np.float32(fx_host[self.len_unroll]),
                 "x": x_out, "fx_array": fx_host}
 
     # -- recovery from a partner timeout (round 5; VERDICT r04 item 6) -----------------------------------------
@@ -206,22 +225,34 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
     # in-place launch of an exchanging kernel snapshots first (one multi-tensor copy).  L2O_NO_RECOVERY=1: raise instead.
     def _snapshot(self, slots):
         """Copy x, packed LSTM states and moments aside ahead of an IN-PLACE launch that may time out."""
-        live = [v.value for v in self.x]
-        for s in slots:
-            if isinstance(s.state, PackedState) and s.state.packed is not None:
-                live.append(s.state.packed)
-            if s.m is not None:
-                live += [s.m, s.v]
+        live = [v.value for v in self.x] + self._state_tensors(slots)
         snap = self.__dict__.get("_snap")
         if snap is None or len(snap["bak"]) != len(live) or any(b.shape != t.shape for b, t in zip(snap["bak"], live)):
             snap = self._snap = {"bak": [torch.empty_like(t) for t in live]}
-        if hasattr(torch, "_foreach_copy_") and len(live) > 1:
-            torch._foreach_copy_(snap["bak"], live)
-        else:
-            for b, t in zip(snap["bak"], live):
-                b.copy_(t)
+        _copy_all(snap["bak"], live)
         snap["live"] = live
         self._last_launch["snapshot"] = True
+
+    def _arm_snapshot(self):
+        """The launch memo and the snapshot of a committed in-place launch that goes out past launch() (Replicas.run)."""
+        self._ensure_init()
+        self._last_launch = {"restart": None, "snapshot": False, "commit": True}
+        self._snapshot(self.slots)
+
+    def _restore_snapshot(self):
+        """The inputs of the in-place launch come back."""
+        for t, b in zip(self._snap["live"], self._snap["bak"]):
+            t.copy_(b)
+
+    def _rerun(self, feed, commit, restart, off):
+        """The recovery re-run of the last unroll: launch() again with the library options `off` at 0 -- the exchange-free
+        kernels --, on the SAME minibatches (the MLP optimizee: not a fresh draw), the launch memo left as it is."""
+        self._reuse_minibatches = True
+        try:
+            with _abi.option_scope({opt: 0 for opt in off}):
+                return self.launch(feed, commit, restart=restart, _recovering=True)
+        finally:
+            self._reuse_minibatches = False
 
     def _wants_snapshot(self, restart_fused):
         """An in-place committed launch of a kernel that can time out: unknown before the first launch of a shape (then:
@@ -295,19 +326,12 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
             import warnings
             warnings.warn("open_l2o_amd: %s -- re-running this unroll on the exchange-free kernels" % (err,), RuntimeWarning)
             self.recoveries = self.__dict__.get("recoveries", 0) + 1
-            if info.get("restart") is None and info.get("snapshot"):    # the in-place launch: its inputs come back
-                snap = self._snap
-                for t, b in zip(snap["live"], snap["bak"]):
-                    t.copy_(b)
-            self._reuse_minibatches = True               # (the MLP optimizee: the SAME minibatches, not a fresh draw)
-            try:
-                with _abi.option_scope({_abi.OPT_PAIR: 0, _abi.OPT_MLP_UNROLL: 0}):
-                    fx, xs = self.launch(feed, commit, restart=info.get("restart"), _recovering=True)
-                    self.wait_fx()
-                    fx_host = eng.to_numpy(fx)
-                    self._check_unroll_status()          # (an exchange-free kernel raises nothing)
-            finally:
-                self._reuse_minibatches = False
+            if info.get("restart") is None and info.get("snapshot"):
+                self._restore_snapshot()
+            fx, xs = self._rerun(feed, commit, info.get("restart"), (_abi.OPT_PAIR, _abi.OPT_MLP_UNROLL))
+            self.wait_fx()
+            fx_host = eng.to_numpy(fx)
+            self._check_unroll_status()                  # (an exchange-free kernel raises nothing)
         return fx_host, fx, xs
 
     def deterministic(self):
@@ -354,242 +378,223 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
         ``events`` = (start, end) torch.cuda.Event pair recorded around the unroll kernels.
         ``use_graph`` (with commit=True, no fed x-scale): the launch sequence of the step-granular
         path is captured once into a HIP graph per ``step0`` and replayed afterwards, which
-        removes the per-launch host cost of its 2..6 x T small kernels."""
+        removes the per-launch host cost of its 2..6 x T small kernels.
+        ``record`` (a dict): a meta-gradient launch, which also leaves the per-step history there (_backward reads it)."""
         self._ensure_init()
-        eng = self.engine
-        T = self.len_unroll
-        feed = feed or {}
+        T, feed = self.len_unroll, feed or {}
         if not _recovering:
             self._last_launch = {"restart": restart if (restart is not None and commit and record is None) else None,
                                  "snapshot": False, "commit": bool(commit)}
-        # ---- fast path: the SAME fused launch as before (same buffers / problem tensors / options) replays a
-        # prepared call -- one ctypes call instead of ~0.2 ms of argument building, which is a whole config-2 unroll.
-        # Both the committed launch of Session.run([fx, update]) (the product path: evaluate_*.py, util.run_eval_epoch)
-        # and the restart= form (an evaluation loop over a ring of problem instances) take it; RNNProp's fed `step`
-        # is a call-time argument.  The key is the identity of every object the call points into, and the cache entry
-        # keeps ALL of them alive, so an id cannot be recycled behind the key (ADVICE r03).
-        fast_key = None
-        if (commit and record is None and events is None and len(self.x) == 1 and len(self.slots) == 1
+        out, fast = self._replay_prepared(feed, commit, events, record, restart, _recovering)
+        if out is not None:
+            return out
+        # restart = list of device tensors x0: run this unroll from x0 and the zero LSTM state / moments on the SAME
+        # problem instance (rewind(x0) + launch); the fused kernel folds it in (no copy / memset pass) -- decided for good
+        # once the path is known --, every other path rewinds first
+        fold = restart is not None and commit and record is None and len(self.x) == 1 and hasattr(self.engine, "mlp_unroll")
+        if restart is not None and not fold:
+            self.rewind(restart)
+        b = self._launch_buffers(feed, commit)
+        # fx[0..T] of this launch.  Sharded runs all-reduce it ASYNCHRONOUSLY (the next unroll
+        # does not wait for the 404-byte collective); the buffers rotate so that a collective in
+        # flight is never overwritten, and every reader goes through wait_fx().
+        ring = self._fx_ring(T)
+        path = self.last_path = self._choose_path(record, T, b)
+        if fold and path != "fused":
+            self.rewind(restart)                            # (panels / states are views of the live tensors: still valid)
+            fold = False
+        rotate = path == "fused" and record is None        # every other launch uses buffer 0: a captured sequence owns it
+        i = ring["i"] if rotate else 0
+        ring["i"] = (i + 1) % len(ring["bufs"]) if rotate else 0
+        self._claim_fx(ring, i)
+        fx = ring["bufs"][i]
+        if events is not None:
+            events[0].record()
+        if record is not None:
+            record.update(step0=b.step0, shapes=[tuple(pn.shape) for pn in b.panels])
+            if self.second_derivatives:
+                record["x"] = []                          # the Hessian needs the iterates: step-granular recording
+                record["descs"] = b.descs
+        getattr(self, "_path_" + path)(b, T, fx, record, _LaunchOpts(commit, _recovering, restart, fold, fast, use_graph))
+        if events is not None:
+            events[1].record()
+        if self.sharded:
+            self._queue_fx(ring, i)
+        if commit:
+            for s, st in zip(self.slots, b.states):
+                s.state = st
+        return fx, b.xs
+
+    # ---- the prepared call: the SAME fused launch as before (same buffers / problem tensors / options) replays a call
+    # whose arguments were built once -- one ctypes call instead of ~0.2 ms of argument building, which is a whole config-2
+    # unroll.  Both the committed launch of Session.run([fx, update]) (the product path: evaluate_*.py,
+    # util.run_eval_epoch) and the restart= form (an evaluation loop over a ring of problem instances) take it; RNNProp's
+    # fed `step` is a call-time argument.  The key is the identity of every object the call points into, and the cache
+    # entry keeps ALL of them alive, so an id cannot be recycled behind the key (ADVICE r03).
+    def _replay_prepared(self, feed, commit, events, record, restart, recovering):
+        """Returns (what launch returns when a prepared call ran, else None; (key, pinned objects) under which the general
+        path may register this launch -- _register_prepared --, None when it is no candidate)."""
+        eng, T = self.engine, self.len_unroll
+        if not (commit and record is None and events is None and len(self.x) == 1 and len(self.slots) == 1
                 and hasattr(eng, "prepared_unroll") and all(ph not in feed for ph in self.scale)
                 and isinstance(self.slots[0].state, PackedState) and self.slots[0].state.packed is not None
                 and (not self.rnnprop or self.step in feed)):
-            s0 = self.slots[0]
-            fast_objs = (None if restart is None else restart[0], self.x[0].value, s0.state.packed, s0.m, s0.v,
-                         getattr(s0.net, "_wpack", None)) + tuple(v.value for v in self.constants)
-            fast_key = (T, restart is not None, _abi.options_word()) + tuple(id(o) for o in fast_objs)
-            ent = self.__dict__.setdefault("_fast_unrolls", {}).get(fast_key)
-            if ent is not None:
-                if commit and restart is None and not _recovering and self._wants_snapshot(False):
-                    self._snapshot(self.slots)
-                ring = self._fx_cache[T]
-                i = ring["i"]
-                ring["i"] = (i + 1) % len(ring["bufs"])
-                self._claim_fx(ring, i)
-                fx = ring["bufs"][i]
-                if ent["call"](fx, int(feed[self.step]) if self.rnnprop else 1):
-                    self.last_path = "fused"
-                    if self.sharded:
-                        self._queue_fx(ring, i)
-                    return fx, [self.x[0].value]
-                self._fast_unrolls.pop(fast_key, None)      # stale (the engine's workspace / layout changed): general path
-        # restart = list of device tensors x0: run this unroll from x0 and the zero LSTM state / moments on the SAME
-        # problem instance (rewind(x0) + launch); the fused kernels fold it in (no copy / memset pass), every other
-        # path rewinds first
-        restart_fused = False
-        if restart is not None:
-            if commit and record is None and len(self.x) == 1 and hasattr(eng, "mlp_unroll"):
-                restart_fused = True                        # (decided for good below, once the path is known)
-            else:
-                self.rewind(restart)
-        # placeholders
+            return None, None
+        s0 = self.slots[0]
+        objs = (None if restart is None else restart[0], self.x[0].value, s0.state.packed, s0.m, s0.v,
+                getattr(s0.net, "_wpack", None)) + tuple(v.value for v in self.constants)
+        key = (T, restart is not None, _abi.options_word()) + tuple(id(o) for o in objs)
+        ent = self.__dict__.setdefault("_fast_unrolls", {}).get(key)
+        if ent is not None:
+            if restart is None and not recovering and self._wants_snapshot(False):
+                self._snapshot(self.slots)
+            ring = self._fx_cache[T]
+            i = ring["i"]
+            ring["i"] = (i + 1) % len(ring["bufs"])
+            self._claim_fx(ring, i)
+            fx = ring["bufs"][i]
+            if ent["call"](fx, int(feed[self.step]) if self.rnnprop else 1):
+                self.last_path = "fused"
+                if self.sharded:
+                    self._queue_fx(ring, i)
+                return (fx, [self.x[0].value]), None
+            self._fast_unrolls.pop(key, None)               # stale (the engine's workspace / layout changed): general path
+        return None, (key, objs)
+
+    def _register_prepared(self, fast, b, T, fx_part, x0v, fold):
+        """After a plain fused launch: its prepared call under the key _replay_prepared built -- 16 at most, the oldest
+        evicted first (a bounded set of pinned buffers)."""
+        s, d = self.slots[0], b.descs[0]
+        fu = self._fast_unrolls
+        if len(fu) >= 16:
+            fu.pop(next(iter(fu)))
+        call = self.engine.prepared_unroll(s.net.spec, s.net.wpack(self.engine), d, b.panels[0], b.states[0].packed, b.ms[0],
+                                           b.vs[0], T, fx_part, x0v, fold)
+        if call is not None and getattr(s.net, "_wpack", None) is fast[1][5]:
+            fu[fast[0]] = {"call": call, "keep": fast[1]}
+
+    def _launch_buffers(self, feed, commit):
+        """What one launch works on (_LaunchBuffers): the fed x-scales on the device, RNNProp's fed step, the iterates, LSTM
+        states and moments -- the live tensors when `update` is fetched (commit), copies otherwise --, the problem
+        descriptors and the [B, D] panels of the iterates.  Sets _mlp_scales."""
+        eng = self.engine
         # (persistent device buffers, re-uploaded only when a NEW array is fed: util.run_epoch feeds the same
         #  random scaling to every unroll of an epoch, DM/util.py:40-54; stable addresses keep plans valid)
         scales = []
         sbufs = self.__dict__.setdefault("_scale_bufs", {})
         for ph, var in zip(self.scale, self.x):
+            ent = None
             if ph in feed:
                 src = feed[ph]
                 ent = sbufs.get(var.decl.name)
                 if ent is None or ent[0] is not src:
-                    arr = var._local(src)
-                    B, D = self._panel_shape(var)
-                    new = eng.tensor(arr.reshape(B, D))
+                    new = eng.tensor(var._local(src).reshape(self._panel_shape(var)))
                     if ent is not None and ent[1].shape == new.shape:
                         ent[1].copy_(new)
                         new = ent[1]
                     ent = sbufs[var.decl.name] = (src, new)
-                scales.append(ent[1])
-            else:
-                scales.append(None)
-        step0 = 1
-        if self.rnnprop:
-            if self.step not in feed:
-                raise ValueError("You must feed a value for placeholder 'step' (DM/util.py:59-60)")
-            step0 = int(feed[self.step])
-
-        # buffers: run in place on the live tensors when `update` is fetched, on copies otherwise
+            scales.append(None if ent is None else ent[1])
+        step0 = self._step0(feed)
         xs = [v.value if commit else v.value.clone() for v in self.x]
-        slots = self.slots
         states, ms, vs = [], [], []
-        for s in slots:
-            if isinstance(s.state, PackedState):
-                states.append(s.state if commit else s.state.clone())
-            else:
-                states.append(s.state)
+        for s in self.slots:
+            states.append(s.state.clone() if isinstance(s.state, PackedState) and not commit else s.state)
             ms.append(s.m if (commit or s.m is None) else s.m.clone())
             vs.append(s.v if (commit or s.v is None) else s.v.clone())
+        # (a step-path optimizee has no descriptor: _run_steps evaluates it at x * scale, DM/meta_dm_train.py:384)
+        multivar = [self.term_of[v.decl.name].kind in _MULTIVAR for v in self.x]
+        descs = [None if mv else self._desc(v, sc) for v, sc, mv in zip(self.x, scales, multivar)]
+        panels = [xv.view(*self._panel_shape(var)) for xv, var in zip(xs, self.x)]
+        self._mlp_scales = [sc if mv else None for sc, mv in zip(scales, multivar)]
+        return _LaunchBuffers(scales, step0, xs, states, ms, vs, descs, panels)
 
-        descs = []
-        for v, sc in zip(self.x, scales):
-            if self.term_of[v.decl.name].kind in _MULTIVAR:
-                descs.append(None)                          # (its x-scale is applied around l2o_mlp_fg, see _run_steps)
-            else:
-                descs.append(self._desc(v, sc))
-        panels = []
-        for xv, var in zip(xs, self.x):
-            B, D = self._panel_shape(var)
-            panels.append(xv.view(B, D))
-        # the MLP / conv optimizees are evaluated at x * scale and their gradient is scale * grad (DM/meta_dm_train.py:384)
-        self._mlp_scales = [sc if self.term_of[v.decl.name].kind in _MULTIVAR else None
-                            for v, sc in zip(self.x, scales)]
+    def _step0(self, feed):
+        """RNNProp's fed `step`: the running step count of the bias corrections; 1 for the other nets."""
+        if self.rnnprop and self.step not in feed:
+            raise ValueError("You must feed a value for placeholder 'step' (DM/util.py:59-60)")
+        return int(feed[self.step]) if self.rnnprop else 1
 
-        # fx[0..T] of this launch.  Sharded runs all-reduce it ASYNCHRONOUSLY (the next unroll
-        # does not wait for the 404-byte collective); the buffers rotate so that a collective in
-        # flight is never overwritten, and every reader goes through wait_fx().
-        ring = self._fx_ring(T)
-        fused_path = record is None and self._fused_ok(descs)
-        if restart_fused and not fused_path:
-            self.rewind(restart)                            # (panels / states are views of the live tensors: still valid)
-            restart_fused = False
-        if not fused_path:
-            ring["i"] = 0                                  # a captured launch sequence owns buffer 0
-        i = ring["i"]
-        ring["i"] = (i + 1) % len(ring["bufs"]) if fused_path else 0
-        self._claim_fx(ring, i)
-        fx = ring["bufs"][i]
+    def _choose_path(self, record, T, b):
+        """The kernel form of this launch, the first that applies: "fused" (l2o_unroll: ONE analytic problem under ONE LSTM
+        net), "mlp_unroll" / "confocal_unroll" (that optimizee's fused unroll), else "steps".  A recording launch asks for the
+        recording kernels: no fused one under second derivatives (the Hessian needs the iterates) or for T = 0, and the MLP
+        one only in its FAST form (its generic loops are no faster than the steps: minibatch 128, 1.12 vs 0.89 ms)."""
+        slots, env = self.slots, os.environ
+        if record is None:
+            if self._fused_ok(b.descs):
+                return "fused"
+            if self._mlp_unroll_ok(slots, b.states, b.scales):
+                return "mlp_unroll"
+        elif not self.second_derivatives:
+            if T > 0 and self._fused_ok(b.descs, record=True) and isinstance(b.states[0], PackedState) \
+                    and b.states[0].packed is not None:
+                return "fused"
+            if not env.get("L2O_NO_MLP_UNROLL_RECORD") and \
+                    self._mlp_unroll_ok(slots, b.states, b.scales) >= (1 if env.get("L2O_MLP_UNROLL_RECORD_GENERIC") else 2):
+                return "mlp_unroll"
+        return "confocal_unroll" if self._confocal_unroll_ok(slots, b.states) else "steps"
 
-        if events is not None:
-            events[0].record()
-        if record is not None and self.second_derivatives:
-            record["x"] = []                              # the Hessian needs the iterates: step-granular recording
-            record["descs"] = descs
-        if record is not None and T > 0 and not self.second_derivatives and self._fused_ok(descs, record=True) \
-                and isinstance(states[0], PackedState) and states[0].packed is not None:
-            # meta-gradient on a fused-size problem: ONE launch that also records the history
-            # (state before, gradient at, moments after every step; gradient at x_T)
-            self.last_path = "fused"
-            s, d = slots[0], descs[0]
-            B, D = panels[0].shape
-            N = B * D
-            # the history buffers (and the per-step views of them, and the BPTT pointer table that
-            # _bptt_panels keeps in this dict) live as long as the unroll keeps its shape
-            key = (T, B, D, states[0].packed.numel(), bool(self.rnnprop))
-            fp = self.__dict__.get("_fused_plan")
-            if fp is None or fp["key"] != key:
-                hist = {"st": eng.empty(T, states[0].packed.numel()), "g": eng.empty(T, N), "g_final": eng.empty(N)}
-                if self.rnnprop:
-                    hist.update(m=eng.empty(T, N), v=eng.empty(T, N))
-                fp = self.__dict__["_fused_plan"] = dict(
-                    key=key, hist=hist,
-                    g=[[hist["g"][t].view(B, D)] for t in range(T)], st=[[hist["st"][t]] for t in range(T)],
-                    m=[[hist["m"][t].view(B, D) if self.rnnprop else None] for t in range(T)],
-                    v=[[hist["v"][t].view(B, D) if self.rnnprop else None] for t in range(T)],
-                    g_final=[hist["g_final"].view(B, D)])
-            hist = fp["hist"]
-            fx_part = self._scratch("fx_part", (T + 1) * d.B_local)
-            eng.unroll(s.net.spec, s.net.wpack(eng), d, panels[0], states[0].packed, ms[0], vs[0], T, step0,
-                       fx_part, hist=hist, fx=fx)
-            record.update(step0=step0, shapes=[tuple(pn.shape) for pn in panels], g=fp["g"], st=fp["st"],
-                          m=fp["m"], v=fp["v"], g_final=fp["g_final"], plan=fp)
-        elif (record is not None and not self.second_derivatives and not os.environ.get("L2O_NO_MLP_UNROLL_RECORD")
-              and self._mlp_unroll_ok(slots, states, scales) >= (1 if os.environ.get("L2O_MLP_UNROLL_RECORD_GENERIC") else 2)):
-            # meta-gradient on the neural optimizee: the T steps AND their history in ONE persistent launch
-            # (l2o_mlp_unroll_record) instead of 3 T + 2 step-granular launches -- where the kernel's FAST form applies
-            # (the reference's shape; training step 0.86 -> 0.68 ms at T = 20): its generic loops are no faster than
-            # the step-granular path (minibatch 128: 1.12 vs 0.89 ms)
-            self.last_path = "mlp_unroll"
-            self._draw_minibatches(T)
-            record.update(step0=step0, shapes=[tuple(pn.shape) for pn in panels])
-            self._run_fused_unroll("mlp", T, step0, panels, slots, states, ms, vs, scales, fx, record=record)
-            if events is not None:
-                events[1].record()
-        elif record is not None and self._confocal_unroll_ok(slots, states):
-            # meta-gradient on the confocal optimizee (fused=True): the T steps and their history in ONE launch
-            self.last_path = "confocal_unroll"
-            record.update(step0=step0, shapes=[tuple(pn.shape) for pn in panels])
-            self._run_fused_unroll("confocal", T, step0, panels, slots, states, ms, vs, scales, fx, record=record)
-            if events is not None:
-                events[1].record()
-        elif record is not None:                           # meta-gradient: needs the per-step history
-            self.last_path = "steps"
-            self._draw_minibatches(T)
-            record.update(step0=step0, shapes=[tuple(pn.shape) for pn in panels])
-            self._run_steps(T, step0, descs, panels, slots, states, ms, vs, fx, record=record)
-        elif fused_path:
-            self.last_path = "fused"
-            s, d = slots[0], descs[0]
-            fx_part = self._scratch("fx_part", (T + 1) * d.B_local)
-            x0v = restart[0].view(panels[0].shape) if restart_fused else None
-            if commit and not _recovering and self._wants_snapshot(restart_fused):
-                self._snapshot(slots)
-            eng.unroll(s.net.spec, s.net.wpack(eng), d, panels[0], states[0].packed, ms[0], vs[0], T, step0,
-                       fx_part, fx=fx, x0=x0v, zero_state=restart_fused)   # (the batch-mean reduction rides in the epilogue)
-            if fast_key is not None and (restart is None or restart_fused) and d.x_scale is None:
-                fu = self._fast_unrolls
-                if len(fu) >= 16:
-                    fu.pop(next(iter(fu)))                  # (oldest first: a bounded set of pinned buffers)
-                call = eng.prepared_unroll(s.net.spec, s.net.wpack(eng), d, panels[0], states[0].packed, ms[0], vs[0],
-                                           T, fx_part, x0v, restart_fused)
-                if call is not None and getattr(s.net, "_wpack", None) is fast_objs[5]:
-                    fu[fast_key] = {"call": call, "keep": fast_objs}
-            if events is not None:
-                events[1].record()
-        elif self._mlp_unroll_ok(slots, states, scales):
-            # the neural optimizee, all four variables stepped by one LSTM net: T steps in ONE persistent launch
-            self.last_path = "mlp_unroll"
-            self._draw_minibatches(T)
-            if commit and not _recovering and self._wants_snapshot(False):
-                self._snapshot(slots)
-            self._run_fused_unroll("mlp", T, step0, panels, slots, states, ms, vs, scales, fx)
-            if events is not None:
-                events[1].record()
-        elif self._confocal_unroll_ok(slots, states):
-            # the confocal optimizee (fused=True), every variable stepped by one LSTM net: one workgroup per batch row runs
-            # the T steps in ONE launch (no workgroup waits for another: no status word)
-            self.last_path = "confocal_unroll"
-            self._run_fused_unroll("confocal", T, step0, panels, slots, states, ms, vs, scales, fx)
-            if events is not None:
-                events[1].record()
+    def _path_fused(self, b, T, fx, record, o):
+        """ONE launch of l2o_unroll (the batch-mean reduction rides in its epilogue); with `record` its recording form, which
+        also writes the history: state before, gradient at, moments after every step; gradient at x_T."""
+        eng, s, d, panel = self.engine, self.slots[0], b.descs[0], b.panels[0]
+        fx_part = self._scratch("fx_part", (T + 1) * d.B_local)
+        if record is not None:      # a training step is not re-run and starts where the last one ended: no snapshot, no x0, no replay
+            fp = self._fused_hist_plan(T, panel, b.states[0].packed)
+            eng.unroll(s.net.spec, s.net.wpack(eng), d, panel, b.states[0].packed, b.ms[0], b.vs[0], T, b.step0, fx_part,
+                       hist=fp["hist"], fx=fx)
+            record.update(g=fp["g"], st=fp["st"], m=fp["m"], v=fp["v"], g_final=fp["g_final"], plan=fp)
+            return
+        x0v = o.restart[0].view(panel.shape) if o.fold else None
+        if o.commit and not o.recovering and self._wants_snapshot(o.fold):
+            self._snapshot(self.slots)
+        eng.unroll(s.net.spec, s.net.wpack(eng), d, panel, b.states[0].packed, b.ms[0], b.vs[0], T, b.step0, fx_part, fx=fx,
+                   x0=x0v, zero_state=o.fold)
+        if o.fast is not None and (o.restart is None or o.fold) and d.x_scale is None:
+            self._register_prepared(o.fast, b, T, fx_part, x0v, o.fold)
+
+    def _path_mlp_unroll(self, b, T, fx, record, o):
+        """The neural optimizee, all four variables stepped by one LSTM net: the T steps -- with `record`, and their history
+        (l2o_mlp_unroll_record instead of 3 T + 2 step-granular launches) -- in ONE persistent launch."""
+        self._draw_minibatches(T)
+        if record is None and o.commit and not o.recovering and self._wants_snapshot(False):
+            self._snapshot(self.slots)                      # (only an evaluation unroll is re-run after a partner timeout)
+        self._run_fused_unroll("mlp", T, b.step0, b.panels, self.slots, b.states, b.ms, b.vs, b.scales, fx, record=record)
+
+    def _path_confocal_unroll(self, b, T, fx, record, o):
+        """The confocal optimizee (fused=True), every variable stepped by one LSTM net: one workgroup per batch row runs the
+        T steps in ONE launch.  No workgroup waits for another (no status word: no snapshot), nothing is drawn."""
+        self._run_fused_unroll("confocal", T, b.step0, b.panels, self.slots, b.states, b.ms, b.vs, b.scales, fx, record=record)
+
+    def _path_steps(self, b, T, fx, record, o):
+        """The step-granular kernels; with `record` they keep the per-step history."""
+        self._draw_minibatches(T)                          # host RNG -> persistent device index buffers
+        args = (T, b.step0, b.descs, b.panels, self.slots, b.states, b.ms, b.vs, fx)
+        if record is None:                                 # (a recording sequence is never captured: bench.py's loop is plain)
+            self._run_steps_graphed(o.use_graph and o.commit and all(sc is None for sc in b.scales), *args)
         else:
-            self.last_path = "steps"
-            self._draw_minibatches(T)                      # host RNG -> persistent device index buffers
-            graphable = (use_graph and commit and all(sc is None for sc in scales) and
-                         all(isinstance(st, PackedState) for st in states) and hasattr(torch.cuda, "CUDAGraph")
-                         and eng.device.type == "cuda")
-            if not graphable:
-                self._run_steps(T, step0, descs, panels, slots, states, ms, vs, fx)
-            else:
-                cache = self.__dict__.setdefault("_hip_graphs", {})
-                entry = cache.get(step0)
-                if entry is None:                          # 1st call: eager (allocates every scratch buffer)
-                    self._run_steps(T, step0, descs, panels, slots, states, ms, vs, fx)
-                    cache[step0] = "warm"
-                else:
-                    if entry == "warm":                    # 2nd call: capture (records, does not execute)
-                        g = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(g):
-                            self._run_steps(T, step0, descs, panels, slots, states, ms, vs, fx)
-                        cache[step0] = entry = g
-                    entry.replay()
-            if events is not None:
-                events[1].record()
+            self._run_steps(*args, record=record)
 
-        if self.sharded:
-            self._queue_fx(ring, i)
-        if commit:
-            for s, st in zip(slots, states):
-                s.state = st
-        return fx, xs
+    def _run_steps_graphed(self, wanted, T, step0, descs, panels, slots, states, ms, vs, fx):
+        """_run_steps, as a HIP graph per step0 where the caller wants one and it can be captured: eager the first time,
+        captured the second, replayed from then on (reset drops the graphs)."""
+        graphable = (wanted and all(isinstance(st, PackedState) for st in states) and hasattr(torch.cuda, "CUDAGraph")
+                     and self.engine.device.type == "cuda")
+        if not graphable:
+            self._run_steps(T, step0, descs, panels, slots, states, ms, vs, fx)
+        else:
+            cache = self.__dict__.setdefault("_hip_graphs", {})
+            entry = cache.get(step0)
+            if entry is None:                          # 1st call: eager (allocates every scratch buffer)
+                self._run_steps(T, step0, descs, panels, slots, states, ms, vs, fx)
+                cache[step0] = "warm"
+            else:
+                if entry == "warm":                    # 2nd call: capture (records, does not execute)
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        self._run_steps(T, step0, descs, panels, slots, states, ms, vs, fx)
+                    cache[step0] = entry = g
+                entry.replay()
 
     # -- the loss all-reduce of a sharded job: DEFERRED and COALESCED (round 6) --------------------------------------------------
     # Nothing reads an unroll's losses before the host asks for them (Session.run: wait_fx + a copy; bench.py: at the end of the
@@ -652,8 +657,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
         loss entries of the result are None; honoured when every network's meta-step runs on the device."""
         record = {}
         fx, xs = self.launch(feed, commit, record=record)
-        eng = self.engine
-        T = self.len_unroll
+        eng, T = self.engine, self.len_unroll
         grads = self._backward(T, record)                   # (launched before the host reads anything back)
         self.wait_fx()
         fused = self.last_path in ("fused", "mlp_unroll") and hasattr(eng, "check_unroll_status")   # kernels with a status word
@@ -678,8 +682,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
             if fused:
                 import weakref
                 eng._deferred_graph = weakref.ref(self)     # (whose sticky status it is, should an evaluation see it first)
-            return {"loss": None, "fx": None, "fx_array": None,
-                    "x": _LazyHost(eng, xs, [self._local_shape(var) for var in self.x])}
+            return self._result(None, xs)
         if fused and hasattr(eng, "prefetch_unroll_status"):
             eng.prefetch_unroll_status()                    # (rides on the sync below)
         fx_host = eng.to_numpy(fx)                          # host sync
@@ -687,11 +690,9 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
             self._guarded_pending = pend + (1 if early else 0)
             self._check_unroll_status()                     # raise BEFORE a host-side Adam update / report the skipped ones
         self._guarded_pending = 0
-        x_out = _LazyHost(eng, xs, [self._local_shape(var) for var in self.x])   # copied to the host only if fetched
         if not early:
             self._adam_apply(grads, learning_rate)
-        return {"loss": np.float32(fx_host.sum(dtype=np.float32)), "fx": np.float32(fx_host[T]),
-                "x": x_out, "fx_array": fx_host}
+        return self._result(fx_host, xs)
 
     def _check_unroll_status(self):
         """engine.check_unroll_status() after a host sync; when it raises, guarded meta-steps enqueued since the last
@@ -731,12 +732,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
     def rewind(self, x0):
         """Device-side restart of the SAME problem instance: x <- x0 (list of device tensors),
         LSTM state / moments <- 0, without re-sampling the problem data (bench.py)."""
-        dst, src = self.rewind_lists(x0)
-        if hasattr(torch, "_foreach_copy_") and len(dst) > 1:
-            torch._foreach_copy_(dst, src)                  # ONE launch for x, LSTM state and moments
-        else:
-            for d_, s_ in zip(dst, src):
-                d_.copy_(s_)
+        _copy_all(*self.rewind_lists(x0))                   # ONE launch for x, LSTM state and moments
 
     def rewind_lists(self, x0):
         """(destinations, sources) of rewind(x0): a caller that rewinds several graphs at once (bench.py's replicas) passes
@@ -744,19 +740,23 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
         self._ensure_init()
         dst, src = [v.value for v in self.x], list(x0)
         zeros = self.__dict__.setdefault("_rewind_zeros", {})
-        for s in self.slots:
-            ts = []
+        for t in self._state_tensors(self.slots):
+            z = zeros.get(tuple(t.shape))
+            if z is None or z.device != t.device:
+                z = zeros[tuple(t.shape)] = torch.zeros_like(t)
+            dst.append(t)
+            src.append(z)
+        return dst, src
+
+    def _state_tensors(self, slots):
+        """The packed LSTM states and RNNProp moments behind `slots`, slot by slot."""
+        ts = []
+        for s in slots:
             if isinstance(s.state, PackedState) and s.state.packed is not None:
                 ts.append(s.state.packed)
             if s.m is not None:
                 ts += [s.m, s.v]
-            for t in ts:
-                z = zeros.get(tuple(t.shape))
-                if z is None or z.device != t.device:
-                    z = zeros[tuple(t.shape)] = torch.zeros_like(t)
-                dst.append(t)
-                src.append(z)
-        return dst, src
+        return ts
 
     def _local_shape(self, var):
         if self.sharded:
@@ -769,7 +769,6 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
             buf = self.engine.zeros(n)
             setattr(self, "_scr_" + name, buf)
         return buf[:n]
-
 
 
 # ---------------------------------------------------------------------------
@@ -823,11 +822,7 @@ class MtUnroll(object):
         for ph in self.inputs + self.labels:
             if ph not in feed:
                 raise ValueError("You must feed a value for placeholder %r" % (ph.name,))
-        step0 = 1
-        if g.rnnprop:
-            if g.step not in feed:
-                raise ValueError("You must feed a value for placeholder 'step' (DM/util.py:59-60)")
-            step0 = int(feed[g.step])
+        step0 = g._step0(feed)
         b1, b2 = float(np.float32(g.beta1)), float(np.float32(g.beta2))
         states = [st if commit else st.clone() for st in self.state]
         ms = [m if (commit or m is None) else m.clone() for m in self.m]

@@ -232,9 +232,7 @@ class Replicas(object):
         recover = not os.environ.get("L2O_NO_RECOVERY")
         if recover:                                          # (the kernel runs in place and its teams can time out)
             for g in graphs:
-                g._ensure_init()
-                g._last_launch = {"restart": None, "snapshot": False, "commit": True}
-                g._snapshot(g.slots)
+                g._arm_snapshot()
         insts, _ = self._launch_multi("xcd", feed)
         if hasattr(eng, "prefetch_unroll_status"):
             eng.prefetch_unroll_status()
@@ -250,16 +248,9 @@ class Replicas(object):
             self.recoveries += 1
             fx_host = []
             for g in graphs:
-                snap = g._snap
-                for t, b in zip(snap["live"], snap["bak"]):
-                    t.copy_(b)
-                g._reuse_minibatches = True
-                try:
-                    with _abi.option_scope({_abi.OPT_MLP_UNROLL: 0}):
-                        fx, _ = g.launch(self._feed(g, feed), True, _recovering=True)
-                        fx_host.append(eng.to_numpy(fx))
-                finally:
-                    g._reuse_minibatches = False
+                g._restore_snapshot()
+                fx, _ = g._rerun(self._feed(g, feed), True, None, (_abi.OPT_MLP_UNROLL,))
+                fx_host.append(eng.to_numpy(fx))
             self.last_form = "steps (recovered)"
             for g in graphs:
                 g.last_path = "mlp_xcd"
