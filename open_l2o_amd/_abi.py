@@ -44,6 +44,8 @@ CONFOCAL_UNROLL_SYMBOLS = ("l2o_confocal_unroll", "l2o_confocal_unroll_record", 
 # ... and include/l2o_confocal_multi_abi.h (several confocal instances per fused launch); bound when the library has them
 CONFOCAL_MULTI_SYMBOLS = ("l2o_confocal_unroll_multi", "l2o_confocal_unroll_multi_record",
                           "l2o_confocal_unroll_multi_supported", "l2o_confocal_unroll_multi_scratch_floats")
+# ... and include/l2o_mlp_hvp_abi.h (the Hessian-vector product of the MLP optimizee: second_derivatives=True on problems.mnist)
+MLP_HVP_SYMBOLS = ("l2o_mlp_hvp", "l2o_mlp_hvp_scratch_floats")
 
 
 # option ids of include/l2o_abi.h ("options": per call, caller-owned -- the LIBRARY keeps no option state since ABI v9).
@@ -304,7 +306,8 @@ def source_build_id():
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     names = ["l2o_kernels.hip", "l2o_kernels_ilp.hip", "Makefile", "../../include/l2o_abi.h",
-             "../../include/l2o_confocal_unroll_abi.h", "../../include/l2o_confocal_multi_abi.h"] + [
+             "../../include/l2o_confocal_unroll_abi.h", "../../include/l2o_confocal_multi_abi.h",
+             "../../include/l2o_mlp_hvp_abi.h"] + [
         os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.h"))]
     h = hashlib.sha256()
     try:
@@ -413,6 +416,10 @@ def lib():
         floats, fg = getattr(L, stem + "_scratch_floats"), getattr(L, stem + "_fg")
         floats.restype, floats.argtypes = C.c_size_t, [C.POINTER(struct)]
         fg.restype, fg.argtypes = C.c_int, [C.POINTER(struct)] + [vp] * 6
+    L.l2o_mlp_hvp_scratch_floats.restype = C.c_size_t
+    L.l2o_mlp_hvp_scratch_floats.argtypes = [C.POINTER(MlpDeep)]
+    L.l2o_mlp_hvp.restype = C.c_int
+    L.l2o_mlp_hvp.argtypes = [C.POINTER(MlpDeep)] + [vp] * 6
     L.l2o_mlp_unroll_multi_supported.restype = C.c_int
     L.l2o_mlp_unroll_multi_supported.argtypes = [C.POINTER(NetCfg), C.POINTER(Mlp), i32, vp]
     L.l2o_mlp_unroll_multi_workspace_bytes.restype = C.c_size_t

@@ -395,17 +395,39 @@ class HipEngine(object):
     def mlp_deep_fg(self, d: MlpDeepDesc, indices, ws, loss, grads):
         """Loss and gradients of the MLP optimizee with SEVERAL hidden layers on ONE minibatch (l2o_mlp_deep_fg).  ws / grads:
         lists [w0, b0, w1, b1, ..., wL, bL] of device tensors (grads may be None: forward only)."""
-        c = _abi.MlpDeep()
-        c.n_in, c.n_out, c.batch, c.activation = d.n_in, d.n_out, d.batch, d.activation
-        c.n_data, c.n_hidden_layers = int(d.images.shape[0]), len(d.hidden)
-        for k, h in enumerate(d.hidden):
-            c.hidden[k] = int(h)
-        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
+        c = self._cmlp_deep(d, d.hidden)
         scr = self._step_scratch(STEP_OPTIMIZEES[_abi.PROB_MLP], c)
         if scr is None:
             raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_mlp_deep_fg: unsupported MLP shape %r" % (d.hidden,))
         _abi.check(self.lib.l2o_mlp_deep_fg(C.byref(c), C.c_void_p(indices.data_ptr()), _ptr_array(ws), _ptr(loss),
                                             _ptr_array(grads), _ptr(scr), self._stream()))
+
+    @staticmethod
+    def _cmlp_deep(d, hidden):
+        """struct l2o_mlp_deep of an MLP descriptor with the hidden layers `hidden` (more than three: the count alone, which
+        the library refuses)."""
+        c = _abi.MlpDeep()
+        c.n_in, c.n_out, c.batch, c.activation = d.n_in, d.n_out, d.batch, d.activation
+        c.n_data, c.n_hidden_layers = int(d.images.shape[0]), len(hidden)
+        for k, h in enumerate(hidden[:len(c.hidden)]):
+            c.hidden[k] = int(h)
+        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
+        return c
+
+    def mlp_hvp(self, d, indices, ws, us, outs):
+        """outs = H(ws; minibatch `indices`) us: the Hessian-vector product of the MLP optimizee's loss (l2o_mlp_hvp), H the
+        Hessian of what mlp_fg / mlp_deep_fg differentiate.  d: an MlpDesc (one hidden layer) or an MlpDeepDesc; ws / us /
+        outs: lists [w0, b0, w1, b1, ..., wL, bL] of device tensors."""
+        hidden = (d.n_hidden,) if isinstance(d, MlpDesc) else tuple(d.hidden)
+        c = self._cmlp_deep(d, hidden)
+        n = int(self.lib.l2o_mlp_hvp_scratch_floats(C.byref(c)))
+        if not n:
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_mlp_hvp: unsupported MLP shape %r" % (hidden,))
+        if not len(ws) == len(us) == len(outs) == 2 * len(hidden) + 2:
+            raise ValueError("l2o_mlp_hvp: %d / %d / %d arrays for hidden layers %r" % (len(ws), len(us), len(outs), hidden))
+        scr = self._cached_buffer("_mlp_hvp_scratch", n)
+        _abi.check(self.lib.l2o_mlp_hvp(C.byref(c), C.c_void_p(indices.data_ptr()), _ptr_array(ws), _ptr_array(us),
+                                        _ptr_array(outs), _ptr(scr), self._stream()))
 
     def _image_net_fg(self, method, d, indices, ws, loss, grads):
         """Loss and gradients of an image-net optimizee on ONE minibatch: <stem>_fg of the table entry of the public method

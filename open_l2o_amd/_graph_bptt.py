@@ -57,6 +57,28 @@ class BpttMixin(object):
             w = float(pn.get("weight", 1.0))
             eng.lincomb(pn["lam"], pn["gs"][t].reshape(N), 1.0, pn["lam"], 1.0, hv, w)       # lam <- g_t + lam + w H u
 
+        def mlp_hess_update(grp, t):
+            """second_derivatives on an MLP term: its Hessian couples ALL the term's variables, so after every panel's step
+            at time t ONE Hessian-vector product (l2o_mlp_hvp) on the step's minibatch rows serves them all:
+            lam_j <- g_j(t) + lam_j + weight s_j * [H(x_t * s; rows_t) (s * u(t))]_j with u(t) the dg of all the panels.
+            g_t was recorded with the x-scale s and the term's weight folded in (_run_steps), hence both factors."""
+            ht = grp[0]["mlp"]
+            by_pos = sorted(grp, key=lambda pn: pn["mlp_pos"])
+            if "ws" not in ht:
+                ht["ws"] = [None if sc is None else eng.empty(pn["D"]) for pn, sc in zip(by_pos, ht["scales"])]
+                ht["us"] = [None if sc is None else eng.empty(pn["D"]) for pn, sc in zip(by_pos, ht["scales"])]
+                ht["outs"] = [eng.empty(pn["D"]) for pn in by_pos]
+            ws, us = [], []
+            for pn, sc, wb, ub in zip(by_pos, ht["scales"], ht["ws"], ht["us"]):
+                x = pn["xs"][t].reshape(-1)
+                ws.append(x if sc is None else torch.mul(x, sc.reshape(-1), out=wb))
+                us.append(pn["dg"] if sc is None else torch.mul(pn["dg"], sc.reshape(-1), out=ub))
+            eng.mlp_hvp(ht["desc"], ht["idx"][t], ws, us, ht["outs"])
+            for pn, sc, hv in zip(by_pos, ht["scales"], ht["outs"]):
+                if sc is not None:
+                    hv.mul_(sc.reshape(-1))
+                eng.lincomb(pn["lam"], pn["gs"][t].reshape(-1), 1.0, pn["lam"], 1.0, hv, float(ht["weight"]))
+
         def rnnprop_input_adjoint(pn, t, N, Bt, k):
             """second_derivatives for RNNProp (DM/meta_rnnprop_train.py:380-388 without the stop_gradient): the network
             inputs m~ = m^/(sqrt(v^) + 1e-8), g~ = g/(sqrt(v^) + 1e-8) depend on g_t directly AND through the moment
@@ -158,7 +180,21 @@ class BpttMixin(object):
                  and hasattr(eng, "bwd_unroll")
                  and (multi or (getattr(eng, "bwd_unroll_any_d", False) and not os.environ.get("L2O_BWD_ALIGNED_ONLY")))
                  and _abi.get_option(_abi.OPT_BWD_KERNEL) == 0)                                   # A/B switches of the tests
-        groups = [panels] if (multi or fused) else [[pn] for pn in panels]
+        if multi or fused:
+            groups = [panels]
+        else:
+            # panel by panel, each through all T steps on its own -- except, under second derivatives, the panels of one MLP
+            # term: they go through the steps TOGETHER (time is the outer loop), because the term's Hessian couples them
+            groups, of_term = [], {}
+            for pn in panels:
+                ht = pn.get("mlp")
+                if ht is None:
+                    groups.append([pn])
+                elif id(ht) in of_term:
+                    of_term[id(ht)].append(pn)
+                else:
+                    of_term[id(ht)] = [pn]
+                    groups.append(of_term[id(ht)])
         if not fused:
             need_dxs()
         for grp in groups:
@@ -189,6 +225,22 @@ class BpttMixin(object):
                 for o, n in zip(offs[:-1], Ns):
                     A[:, o:o + n, KA - 1] = 1.0
                 carry_in, carry_out = eng.zeros(4, R, H), eng.zeros(4, R, H)
+            coupled = second and grp[0].get("mlp") is not None
+            if coupled:                                    # every panel its own dense [4][N][H] carries
+                for pn, n in zip(grp, Ns):
+                    pn["carry"] = [eng.zeros(4, n, H), eng.zeros(4, n, H)]
+
+            def panel_io(pn, t, Ap, Bp, cin, cout):
+                """l2o_bwd_io of one panel's step t: Ap / Bp its N rows of A[t] / Bm[t]."""
+                io = dict(g=pn["gs"][t], dx_next=pn["lam"] if second else pn["dxs"][t],
+                          dg=None if fc else pn.get("dg"),     # (RNNProp: formed from du below, not by the kernel)
+                          st_prev=pn["sts"][t], carry_in=cin, carry_out=cout, m=pn["ms"][t], v=pn["vs"][t],
+                          a_stride=KA, b_stride=KB,
+                          act1=Ap[:, 0:K1], act2=Ap[:, K1:K1 + 2 * H], h2=Ap[:, K1 + 2 * H:K1 + 3 * H],
+                          dz1=Bp[:, 0:4 * H], dz2=Bp[:, 4 * H:8 * H], dd=Bp[:, 8 * H:8 * H + 1])
+                if fc:
+                    io.update(feats=Ap[:, K1 + 3 * H:K1 + 3 * H + 2], du=Bp[:, 8 * H + 1:8 * H + 1 + H])
+                return io
             for t in (() if fused else reversed(range(T))):
                 k = step0 + t
                 At, Bt = A[t], Bm[t]
@@ -196,16 +248,18 @@ class BpttMixin(object):
                     segs = [dict(g=pn["gs"][t], m=pn["ms"][t], v=pn["vs"][t], st_prev=pn["sts"][t], dx_next=pn["dxs"][t],
                                  B=pn["B"], D=pn["D"]) for pn in grp]
                     eng.bwd_multi(spec, wdev, segs, carry_in, carry_out, At, Bt, b1 ** k, b2 ** k)
+                elif coupled:
+                    for pn, o, N in zip(grp, offs[:-1], Ns):
+                        Ap, Bp = At[o:o + N], Bt[o:o + N]
+                        eng.bwd_step(spec, wdev, panel_io(pn, t, Ap, Bp, pn["carry"][0], pn["carry"][1]), b1 ** k, b2 ** k,
+                                     pn["B"], pn["D"])
+                        pn["carry"].reverse()
+                        if fc:
+                            rnnprop_input_adjoint(pn, t, N, Bp, k)
+                    mlp_hess_update(grp, t)
                 else:
                     pn, N = grp[0], Ns[0]
-                    io = dict(g=pn["gs"][t], dx_next=pn["lam"] if second else pn["dxs"][t],
-                              dg=None if fc else pn.get("dg"),     # (RNNProp: formed from du below, not by the kernel)
-                              st_prev=pn["sts"][t], carry_in=carry_in[:, :N],
-                              carry_out=carry_out[:, :N], m=pn["ms"][t], v=pn["vs"][t], a_stride=KA, b_stride=KB,
-                              act1=At[:N, 0:K1], act2=At[:N, K1:K1 + 2 * H], h2=At[:N, K1 + 2 * H:K1 + 3 * H],
-                              dz1=Bt[:N, 0:4 * H], dz2=Bt[:N, 4 * H:8 * H], dd=Bt[:N, 8 * H:8 * H + 1])
-                    if fc:
-                        io.update(feats=At[:N, K1 + 3 * H:K1 + 3 * H + 2], du=Bt[:N, 8 * H + 1:8 * H + 1 + H])
+                    io = panel_io(pn, t, At[:N], Bt[:N], carry_in[:, :N], carry_out[:, :N])
                     if R != N:                             # the generic kernel wants dense [4][N][H] carries
                         io["carry_in"], io["carry_out"] = carry_in[:, :N].contiguous(), eng.empty(4, N, H)
                     eng.bwd_step(spec, wdev, io, b1 ** k, b2 ** k, pn["B"], pn["D"])
@@ -238,6 +292,7 @@ class BpttMixin(object):
     def _bptt_panel_sets(self, rec):
         """The BPTT panels of one recorded unroll, by network: {net key: (net, [panel dicts as _bptt_panels takes])}."""
         by_net = {}                                        # variables that share a network go through ONE launch per step
+        mlp_terms = {}                                     # second derivatives: what the panels of one MLP term share
         for si, s in enumerate(self.slots):
             net = s.net
             if not isinstance(net, networks.StandardDeepLSTM):
@@ -251,10 +306,17 @@ class BpttMixin(object):
                       ms=[m[si] for m in rec["m"]], vs=[v[si] for v in rec["v"]], dxs=None,
                       g_final=rec["g_final"][j].reshape(N))
             if self.second_derivatives:                    # dL/dx_t picks up H(x_t) . dL/dg_t (DM/meta.py:328-329)
-                if rec["descs"][j] is None:
-                    raise NotImplementedError("second_derivatives=True is implemented for the analytic optimizees")
-                pn.update(second=True, desc=rec["descs"][j], xs=[x[j] for x in rec["x"]],
-                          weight=self.term_of[self.x[j].decl.name].weight)
+                term = self.term_of[self.x[j].decl.name]
+                pn.update(second=True, desc=rec["descs"][j], xs=[x[j] for x in rec["x"]], weight=term.weight)
+                if rec["descs"][j] is None:                # an MLP term (_check_second_derivatives let nothing else through)
+                    ht = mlp_terms.get(id(term))
+                    if ht is None:
+                        k = next(i for i, tm in enumerate(self.terms) if tm is term)
+                        names = [tv.name for tv in _term_vars(term)]           # the term's variable order: l2o_mlp_hvp's
+                        by_name = {v.decl.name: i for i, v in enumerate(self.x)}
+                        ht = mlp_terms[id(term)] = dict(desc=self._mlp_desc(term), idx=rec["mlp_idx"][k], weight=term.weight,
+                                                        names=names, scales=[rec["mlp_scales"][by_name[nm]] for nm in names])
+                    pn.update(mlp=ht, mlp_pos=ht["names"].index(self.x[j].decl.name))
             by_net.setdefault(s.key, (net, []))[1].append(pn)
         return by_net
 

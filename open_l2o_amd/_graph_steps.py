@@ -338,7 +338,8 @@ class StepPlanMixin(object):
         eng = self.engine
         nvar = len(self.x)
         index_of = {v.decl.name: j for j, v in enumerate(self.x)}
-        if record is not None and self._plan_ok(slots, states, nvar):
+        # (the planned recording keeps no iterates: not under second derivatives, whose Hessian needs them)
+        if record is not None and not self.second_derivatives and self._plan_ok(slots, states, nvar):
             return self._run_steps_planned(T, step0, panels, slots, states, ms, vs, fx, record, index_of)
         grads = [self._scratch("g%d" % j, panels[j].numel()).view(panels[j].shape) for j in range(nvar)]
         tmp = self._scratch("fx1", 1)
@@ -393,6 +394,12 @@ class StepPlanMixin(object):
         chain = None
         if record is not None:
             record.update(g=[], st=[], m=[], v=[])
+            if self.second_derivatives and any(term.kind == _abi.PROB_MLP for term in self.terms):
+                # what the Hessian of an MLP term needs beside the iterates (record["x"]): the x-scales in force and a COPY
+                # of this unroll's minibatch rows -- the persistent index buffer is redrawn by the next launch
+                record["mlp_scales"] = list(getattr(self, "_mlp_scales", None) or [None] * nvar)
+                record["mlp_idx"] = {k: self._mlp_idx[k].clone() for k, term in enumerate(self.terms)
+                                     if term.kind == _abi.PROB_MLP}
             # History without copies: the gradients are written straight into their [T + 1] history
             # buffers, and the LSTM state / RNNProp moments are CHAINED through [T + 1] buffers --
             # step t reads slice t and writes slice t + 1 (l2o_step_seg.st_out / m_out / v_out).

@@ -870,6 +870,7 @@ __global__ __launch_bounds__(CH <= 4 ? 256 : 512) void k_unroll(UnrollArgs a) {
 #include "l2o_mlp_unroll.h"
 #include "l2o_mlp_xcd.h"
 #include "l2o_mlp_deep.h"
+#include "l2o_mlp_hvp.h"
 #include "l2o_mnist_conv.h"
 #include "l2o_cifar_conv.h"
 #include "l2o_lenet.h"
@@ -2087,6 +2088,44 @@ int l2o_mlp_deep_fg(const l2o_mlp_deep* m, const int32_t* indices, const float* 
   hipLaunchKernelGGL(k_mlp_deep_sample, dim3(a.batch), dim3(kMdThreads), 0, s, a);
   const long nthreads = g ? ncoord : 1;
   hipLaunchKernelGGL(k_mlp_deep_grad, dim3((unsigned)((nthreads + kMdThreads - 1) / kMdThreads)), dim3(kMdThreads), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return L2O_OK;
+}
+
+// ---- second derivatives of problems.mnist: the Hessian-vector product (csrc/l2o_mlp_hvp.h, include/l2o_mlp_hvp_abi.h) ------
+size_t l2o_mlp_hvp_scratch_floats(const l2o_mlp_deep* m) {
+  if (!mlp_deep_ok(m)) return 0;
+  return (size_t)m->batch * kMdMaxWidth * (4 * m->n_hidden_layers + 2);
+}
+int l2o_mlp_hvp(const l2o_mlp_deep* m, const int32_t* indices, const float* const* w, const float* const* u, float* const* out,
+                float* scratch, void* stream) {
+  if (!mlp_deep_ok(m))
+    return fail(L2O_ERR_UNSUPPORTED, "l2o_mlp_hvp: 1-3 hidden layers of <= 32 units, n_in <= 1024, n_out <= 16, batch <= 4096");
+  if (m->activation != 0 && m->activation != 1) return fail(L2O_ERR_UNSUPPORTED, "l2o_mlp_hvp: activation 0 (sigmoid) or 1 (relu)");
+  if (!indices || !w || !u || !out || !scratch || !m->images || !m->labels) return fail(L2O_ERR_ARG, "l2o_mlp_hvp: NULL argument");
+  MlpHvpArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.n_in = m->n_in; a.n_out = m->n_out; a.batch = m->batch; a.act = m->activation; a.nh = m->n_hidden_layers;
+  for (int l = 0; l < a.nh; ++l) a.width[l] = m->hidden[l];
+  a.width[a.nh] = m->n_out;
+  a.images = m->images; a.labels = m->labels; a.idx = indices;
+  long ncoord = 0;
+  for (int l = 0; l <= a.nh; ++l) {
+    for (int q = 2 * l; q < 2 * l + 2; ++q)
+      if (!w[q] || !u[q] || !out[q]) return fail(L2O_ERR_ARG, "l2o_mlp_hvp: NULL buffer of layer %d", l);
+    a.w[l] = w[2 * l]; a.b[l] = w[2 * l + 1];
+    a.vw[l] = u[2 * l]; a.vb[l] = u[2 * l + 1];
+    a.ow[l] = out[2 * l]; a.ob[l] = out[2 * l + 1];
+    ncoord += (long)(l == 0 ? a.n_in : a.width[l - 1]) * a.width[l] + a.width[l];
+  }
+  const size_t per = (size_t)a.batch * kMdMaxWidth;
+  a.acts = scratch;
+  a.racts = a.acts + (size_t)a.nh * per;
+  a.deltas = a.racts + (size_t)a.nh * per;
+  a.rdeltas = a.deltas + (size_t)(a.nh + 1) * per;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_mlp_hvp_sample, dim3(a.batch), dim3(kMdThreads), 0, s, a);
+  hipLaunchKernelGGL(k_mlp_hvp_reduce, dim3((unsigned)((ncoord + kMdThreads - 1) / kMdThreads)), dim3(kMdThreads), 0, s, a);
   HIP_TRY(hipGetLastError());
   return L2O_OK;
 }

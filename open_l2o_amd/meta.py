@@ -961,12 +961,36 @@ class MetaOptimizer(object):
         # DM/meta.py:328-329: without the flag the optimizee gradients are constants of the meta-gradient
         # (tf.stop_gradient); with it dL/dx_t also receives H(x_t) . dL/dg_t (l2o_problem_hvp)
         graph.second_derivatives = bool(second_derivatives)
-        if graph.second_derivatives and any(t.kind in _MULTIVAR and t.kind != _abi.PROB_MLP for t in graph.terms):
-            raise NotImplementedError("second_derivatives=True is implemented for the analytic optimizees "
-                                      "(problems.mnist_conv / problems.cifar10 / problems.LeNet / "
-                                      "problems.confocal_microscopy_3d have no Hessian-vector product)")
+        if graph.second_derivatives:
+            self._check_second_derivatives(graph)
         self._graph = graph
         return graph
+
+    @staticmethod
+    def _check_second_derivatives(graph):
+        """What second_derivatives=True is implemented for, refused here -- at graph build, with the reason -- and not in
+        the middle of the first train step: the analytic optimizees (l2o_problem_hvp) under any net the BPTT takes, and
+        problems.mnist (l2o_mlp_hvp) when ALL its variables are stepped by ONE (20, 20) LSTM net."""
+        if any(t.kind in _MULTIVAR and t.kind != _abi.PROB_MLP for t in graph.terms):
+            raise NotImplementedError("second_derivatives=True is implemented for the analytic optimizees and problems.mnist "
+                                      "(problems.mnist_conv / problems.cifar10 / problems.LeNet / "
+                                      "problems.confocal_microscopy_3d have no Hessian-vector product)")
+        slot_of = {s.var_index: s for s in graph.slots}
+        index_of = {v.decl.name: j for j, v in enumerate(graph.x)}
+        for term in graph.terms:
+            if term.kind != _abi.PROB_MLP:
+                continue
+            slots = [slot_of[index_of[tv.name]] for tv in _term_vars(term)]
+            net = slots[0].net
+            if any(s.net is not net for s in slots):
+                raise NotImplementedError("second_derivatives=True on problems.mnist: its Hessian couples all its variables, "
+                                          "so ONE network has to step them all (got the nets %r)"
+                                          % (sorted({s.key for s in slots}),))
+            if not isinstance(net, (networks.CoordinateWiseDeepLSTM, networks.RNNprop)) or \
+                    tuple(int(h) for h in net.spec.layers) != (20, 20):
+                raise NotImplementedError("second_derivatives=True on problems.mnist is implemented for a (20, 20) "
+                                          "CoordinateWiseDeepLSTM or RNNprop network (got %s with layers=%r)"
+                                          % (type(net).__name__, tuple(getattr(getattr(net, "spec", None), "layers", ()))))
 
     @staticmethod
     def _handles(graph):

@@ -12,11 +12,17 @@
     nothing else, for ``rocprofv3 --kernel-trace --stats -- python scripts/step_bench.py --problem confocal --loop 2000``;
   * confocal with ``--fused 1 --replicas N``: nothing but N fused unrolls as ONE launch (replicas.Replicas, form "rows":
     rows_step_us_per_instance) against the same N replicas as N single fused launches (the yardstick:
-    single_step_us_per_instance) -- us per optimizer step per instance, the median of 10 event-timed rounds each.
+    single_step_us_per_instance) -- us per optimizer step per instance, the median of 10 event-timed rounds each;
+  * mnist with ``--hvp 1``: us per l2o_mlp_hvp (784-20-10, the Hessian-vector product of second_derivatives=True) against
+    l2o_mlp_deep_fg of the same shape and against the same H u through float32 torch double backward on the same GPU, three
+    event-timed runs each; and one meta_minimize train step at --unroll steps with and without second_derivatives, and with
+    the flag but the Hessian-vector products left out (what of the extra time is the T products, what the un-fused
+    recording and BPTT).
 
     python scripts/step_bench.py --problem {mnist_conv,cifar_conv,lenet} [--batch 128] [--iters 200] [--unroll 20] [--unrolls 10]
     python scripts/step_bench.py --problem confocal [--batch 32] [--points 5] [--roi 28] [--iters 500] [--unroll 20] [--fused 1]
                                  [--unrolls 10] [--loop N] [--replicas N]
+    python scripts/step_bench.py --problem mnist --hvp 1 [--batch 128] [--iters 200] [--unroll 20] [--unrolls 10]
 
 Prints one JSON line.  The image nets run on synthetic data (problems.synthetic_mnist / synthetic_cifar10); the arithmetic
 does not depend on it."""
@@ -272,9 +278,92 @@ def confocal_main(eng, a):
             "device": torch.cuda.get_device_name(0)}
 
 
+# -- the MLP optimizee's Hessian-vector product ------------------------------------------------------------------------------
+def mnist_hvp_torch(x, y, w, u, iters):
+    """H u of the 784-20-10 sigmoid MLP's mean cross-entropy through float32 torch double backward on the GPU."""
+    dev = torch.device("cuda")
+    x, y = torch.tensor(x, device=dev), torch.tensor(y, device=dev, dtype=torch.int64)
+    vs = [torch.tensor(a, device=dev).requires_grad_(True) for a in w]
+    us = [torch.tensor(a, device=dev) for a in u]
+    out = {}
+
+    def hvp():
+        loss = F.cross_entropy(torch.sigmoid(x @ vs[0] + vs[1]) @ vs[2] + vs[3], y)
+        g = torch.autograd.grad(loss, vs, create_graph=True)
+        out["hu"] = torch.autograd.grad(sum((a * b).sum() for a, b in zip(g, us)), vs)
+    times = [_timed(hvp, iters) for _ in range(3)]
+    return times, [t.detach().cpu().numpy() for t in out["hu"]]
+
+
+def time_train_step(data, batch, T, second, steps, warmup=3, no_hvp=False):
+    """us per sess.run([fx, update, step]) of meta_minimize on problems.mnist (the default net), a device synchronise at
+    both ends; no_hvp: with the flag, but engine.mlp_hvp replaced by a fill (the recording and the BPTT without the products)."""
+    import time
+    problem, net_config, na = util.get_config("mnist", problem_options={"data": data, "batch_size": batch})
+    optimizer = meta.MetaOptimizer(**net_config)
+    ms = optimizer.meta_minimize(problem, T, net_assignments=na, learning_rate=1e-4, second_derivatives=second)
+    eng = optimizer.graph.engine
+    if no_hvp:
+        eng.mlp_hvp = lambda d, idx, ws, us, outs: [o.zero_() for o in outs]
+    times = []
+    try:
+        with Session() as sess:
+            sess.run(ms.reset)
+            for k in range(warmup + steps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                sess.run([ms.fx, ms.update, ms.step])
+                torch.cuda.synchronize()
+                if k >= warmup:
+                    times.append(1e6 * (time.perf_counter() - t0))
+    finally:
+        if no_hvp:
+            del eng.mlp_hvp
+    return times, optimizer.graph.last_path
+
+
+def mnist_hvp_main(eng, a):
+    hidden, n_out = (20,), 10
+    data = problems.synthetic_mnist(4096, seed=0, label_noise=0.1)
+    images = np.ascontiguousarray(data["images"], np.float32).reshape(len(data["labels"]), -1)
+    d = _engine.MlpDeepDesc(n_in=images.shape[1], hidden=hidden, n_out=n_out, batch=a.batch, activation=0,
+                            images=eng.tensor(images), labels=eng.int_tensor(data["labels"]))
+    rng = np.random.default_rng(0)
+    rows = rng.integers(0, len(images), a.batch)
+    shapes = [(images.shape[1], hidden[0]), (hidden[0],), (hidden[0], n_out), (n_out,)]
+    w = [rng.normal(0, 0.3, sh).astype(np.float32) for sh in shapes]
+    u = [rng.normal(0, 1.0, sh).astype(np.float32) for sh in shapes]
+    idx, ws, us = eng.int_tensor(rows), [eng.tensor(x) for x in w], [eng.tensor(x) for x in u]
+    outs, grads, loss = [eng.zeros(*sh) for sh in shapes], [eng.zeros(*sh) for sh in shapes], eng.zeros(1)
+    hvp = functools.partial(eng.mlp_hvp, d, idx, ws, us, outs)
+    fg = functools.partial(eng.mlp_deep_fg, d, idx, ws, loss, grads)
+    hvp_us, fg_us = [], []
+    for _ in range(3):                                       # the two alternate
+        hvp_us.append(_timed(hvp, a.iters))
+        fg_us.append(_timed(fg, a.iters))
+    torch_us, torch_hu = mnist_hvp_torch(images[rows], np.asarray(data["labels"])[rows], w, u, a.iters)
+    err = max(float(np.abs(eng.to_numpy(o) - t).max() / np.abs(t).max()) for o, t in zip(outs, torch_hu))
+    steps = {}
+    for name, kw in (("first_order", dict(second=False)), ("second", dict(second=True)),
+                     ("second_without_hvp", dict(second=True, no_hvp=True))):
+        times, path = time_train_step(data, a.batch, a.unroll, steps=a.unrolls, **kw)
+        steps[name] = {"train_step_us": round(float(np.median(times)), 1),
+                       "min_max": [round(min(times), 1), round(max(times), 1)], "path": path}
+    extra = steps["second"]["train_step_us"] - steps["first_order"]["train_step_us"]
+    in_hvp = steps["second"]["train_step_us"] - steps["second_without_hvp"]["train_step_us"]
+    r = lambda xs: [round(x, 2) for x in xs]
+    return {"workload": "mnist_hvp", "shape": [images.shape[1], hidden[0], n_out], "batch": a.batch, "iters": a.iters,
+            "mlp_hvp_us": r(hvp_us), "mlp_deep_fg_us": r(fg_us), "torch_double_backward_us": r(torch_us),
+            "hvp_over_fg": round(float(np.median(hvp_us) / np.median(fg_us)), 2), "max_rel_diff_vs_torch_f32": err,
+            "unroll": a.unroll, "train_steps": steps, "extra_us": round(extra, 1), "extra_in_hvp_calls_us": round(in_hvp, 1),
+            "hvp_share_of_extra": round(in_hvp / extra, 3) if extra > 0 else None, "device": torch.cuda.get_device_name(0)}
+
+
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--problem", required=True, choices=list(IMAGE_NETS) + ["confocal"])
+    p.add_argument("--problem", required=True, choices=list(IMAGE_NETS) + ["confocal", "mnist"])
+    p.add_argument("--hvp", type=int, choices=(0, 1), default=0,
+                   help="mnist: time l2o_mlp_hvp against l2o_mlp_deep_fg and torch double backward, and the train step")
     p.add_argument("--batch", type=int, help="default: 128; confocal: 32")
     p.add_argument("--iters", type=int, help="default: 200; confocal: 500")
     p.add_argument("--unroll", type=int, default=20)
@@ -290,10 +379,13 @@ def main():
     confocal = a.problem == "confocal"
     a.batch = a.batch or (32 if confocal else 128)
     a.iters = a.iters or (500 if confocal else 200)
+    if a.problem == "mnist" and not a.hvp:
+        raise SystemExit("step_bench: --problem mnist measures the Hessian-vector product: give --hvp 1")
     eng = _engine.HipEngine()
     _engine.set_default_engine(eng)
     meta.set_random_seed(0)
-    print(json.dumps((confocal_main if confocal else image_net_main)(eng, a)))
+    run = confocal_main if confocal else (mnist_hvp_main if a.problem == "mnist" else image_net_main)
+    print(json.dumps(run(eng, a)))
 
 
 if __name__ == "__main__":
