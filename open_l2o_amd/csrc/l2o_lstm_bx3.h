@@ -711,6 +711,7 @@ struct LstmCore<PRE, false, PK> {
   NetW<PRE> w;
   __device__ __forceinline__ void load(const float* __restrict__ wpack, int lane) { load_netw<PRE>(w, wpack, lane); }
   static constexpr int kBiasFloats = 4;
+  static constexpr int kStageFrags = 0;          // (no bf16 fragment image: see LstmCoreRegs)
   __device__ __forceinline__ void stage_bias(float*, const float* __restrict__, int, int, int) {}
   __device__ __forceinline__ void pin() {}
   __device__ __forceinline__ void preload(f32x4 (&)[kNT], f32x4 (&)[kNT]) {}
@@ -743,10 +744,46 @@ struct LstmCoreRegs {
   bx::BOp<PK> b1, b2;      // split h1(t-1), h2(t-1): the recurrent chunks' B operands
   unsigned one;
   __device__ __forceinline__ void load(const float* __restrict__ wpack, int lane) { bx::load_netw<PRE, true, PK, WT::kLdsChunk>(w, wpack, lane); }
+  // The same load in two parts, for a caller that brings the fragment image into LDS ONCE per workgroup (the FAST prologue
+  // of k_unroll_pair, as k_cwlstm_step does): the image is kStageFrags pieces of 1 KiB (64 lanes x 16 bytes), contiguous in
+  // wpack from frag_off(PRE, PK, 0, 0, 0) on, in the order of w.a.  load_small() = everything but the fragments;
+  // read_stage() = this lane's 16 bytes of every piece (ds_read_b128 at compile-time offsets) -- the caller has drained
+  // its copies and met a barrier before it, and calls pin() behind it.
+  static constexpr int kStageFrags = WT::kLdsChunk < 0 ? WT::NCH * kNT * bx::frags(PK) : 0;
+  static constexpr int kStageOff = bx::frag_off(PRE, PK, 0, 0, 0);
+  __device__ __forceinline__ void load_small(const float* __restrict__ wpack, int lane) { bx::load_netw<PRE, false, PK>(w, wpack, lane); }
+  __device__ __forceinline__ void read_stage(const float4* stage, int lane) {
+#pragma unroll
+    for (int ch = 0; ch < WT::NCH; ++ch)
+#pragma unroll
+      for (int t = 0; t < kNT; ++t)
+#pragma unroll
+        for (int j = 0; j < bx::frags(PK); ++j)
+          w.a[ch][t][j] = __builtin_bit_cast(bx::u32x4, stage[((ch * kNT + t) * bx::frags(PK) + j) * 64 + lane]);
+  }
   // the bias table -> LDS (all threads; the caller puts a barrier between this and the first issue_*), then the lane's view
   static constexpr int kBiasFloats = bx::kBiasWords;
   __device__ __forceinline__ void stage_bias(float* lds, const float* __restrict__ wpack, int tid, int nthreads, int q) {
     bx::stage_bias(lds, wpack, PRE, tid, nthreads);
+    bx::set_bias(w, lds, q);
+  }
+  // stage_bias in two parts for a caller that issues its loads early and uses them late: fetch_bias = this thread's share
+  // of the table into registers (clamped addresses, no mask), put_bias = the LDS writes and the lane's view
+  template <int NTHREADS>
+  __device__ __forceinline__ void fetch_bias(float (&v)[(bx::kBiasWords + NTHREADS - 1) / NTHREADS], const float* __restrict__ wpack, int tid) {
+#pragma unroll
+    for (int k = 0; k < (bx::kBiasWords + NTHREADS - 1) / NTHREADS; ++k) {
+      const int i = tid + k * NTHREADS;
+      v[k] = wpack[bx::bias_off(PRE) + (i < bx::kBiasWords ? i : bx::kBiasWords - 1)];
+    }
+  }
+  template <int NTHREADS>
+  __device__ __forceinline__ void put_bias(float* lds, const float (&v)[(bx::kBiasWords + NTHREADS - 1) / NTHREADS], int tid, int q) {
+#pragma unroll
+    for (int k = 0; k < (bx::kBiasWords + NTHREADS - 1) / NTHREADS; ++k) {
+      const int i = tid + k * NTHREADS;
+      if (i < bx::kBiasWords) lds[i] = v[k];
+    }
     bx::set_bias(w, lds, q);
   }
   // Pin the 180-240 fragment registers to the accumulation half of the register file.  MFMA reads its A operand

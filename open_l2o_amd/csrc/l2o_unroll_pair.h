@@ -319,7 +319,9 @@ __device__ __forceinline__ void unroll_pair_body_gather(const UnrollPairArgs& pa
   const bool same_xcd = same_xcd_s != 0;
   L2O_LAUNCH_MARK(3);
 
+#define L2O_PAIR_FX_PTR 0
 #include "l2o_unroll_pair_loop.h"
+#undef L2O_PAIR_FX_PTR
 }
 
 // FAST: the prologue for full tiles (the launcher guarantees M = D = SQ; the kernel itself checks the matrix's alignment and
@@ -353,6 +355,27 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
   // of a row / column then sit on the lanes (c, 0..3) and two permlane swaps add them INTO the lanes that feed
   // the gradient to the network -- no ds_bpermute (an LDS round trip) between the g pass and the gate math.
   const int gq = q, gr = c;
+
+  // ---- prologue, part zero: the bf16 gate fragments, ONCE per workgroup (round 13).  Every wave needs all of the 60 KB
+  // image in its AGPRs; loaded per wave (core.load) a CU pulled it NWH times through its L1, 60 dwordx4 loads per wave in
+  // the prologue's burst.  Here each wave copies its 1 / NWH of the image into LDS (LDS-DMA: no destination registers, 1 KiB
+  // per instruction, lane-linear = the layout the lanes read back), FIRST, so that the copies fly under everything else
+  // the prologue issues; behind the one drain and a barrier every wave reads its 60 x 16 bytes per lane from LDS, under the
+  // poll of the partner's handshake granule.  One wave per workgroup (CH = 2) has nobody to share with and keeps its loads.
+  using Core = LstmCorePair<PRE, !EXACT, true>;
+  constexpr bool kStage = Core::kStageFrags > 0 && NWH >= 2;
+  __shared__ float4 frag_stage[kStage ? Core::kStageFrags * 64 : 1];
+  static_assert(sizeof(frag_stage) + sizeof(float) * (NC + SQ + Core::kBiasFloats + 4) <= 64 * 1024, "static LDS");
+  if constexpr (kStage) {
+    const int wvs = __builtin_amdgcn_readfirstlane(wv);   // (the LDS destination is wave-uniform base + lane x 16)
+    const float* src = a.np.wpack + Core::kStageOff + lane * 4;
+#pragma unroll
+    for (int f = 0; f < (Core::kStageFrags + NWH - 1) / NWH; ++f) {
+      const int fr = NWH * f + wvs;
+      if (Core::kStageFrags % NWH == 0 || fr < Core::kStageFrags)
+        __builtin_amdgcn_global_load_lds((gbl_void*)(src + fr * bx::kFragWords), (lds_void*)(frag_stage + fr * 64), 16, 0, 0);
+    }
+  }
 
   // ---- the matrix lives in registers: no LDS bandwidth in the two GEMV passes -------------
   //  wr[p][m] : row (2 wv + p) 16 + gr, own columns 16 m + 4 gq + {0..3}     (partial r = W xs)
@@ -425,7 +448,9 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
   const int tpp = (D + kTile - 1) / kTile;
   const bool tile_real = tile_in_prob < tpp;            // the padded tile of an odd tile count is idle
   // (the state tile is read whatever it holds -- the kernel stores it at the end, so the memory is there -- and dropped
-  //  below when the launch starts from the zero state: no branch around five loads)
+  //  below when the launch starts from the zero state: no branch around five loads.  Round 13 measured the uniform branch:
+  //  the loads it saves are not what the burst waits for, and the loop behind it scheduled 2 % slower --
+  //  profiles/r13_launch_fixed_cost.txt)
   float* st_tile = a.st + ((size_t)b * tpp + (tile_real ? tile_in_prob : 0)) * kStateFloatsPerTile;
   float4 st_ld[5];
   fetch_tile_state(st_ld, st_tile, lane);
@@ -440,9 +465,18 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
 
   // ---- per-lane persistent registers -------------------------------------
   // <= 4 waves per workgroup: bf16x3 gate GEMM, weights in VGPR + AGPR
-  using Core = LstmCorePair<PRE, !EXACT, true>;
   Core core;
-  core.load(a.np.wpack, lane);
+  float bias_ld[kStage ? (Core::kBiasFloats + 64 * NWH - 1) / (64 * NWH) : 1];
+  if constexpr (kStage) {
+    core.load_small(a.np.wpack, lane);
+    // (the bias table rides in this burst too: hipcc drains the vector memory queue at the first use of a loaded value
+    //  while a copy into LDS is in flight -- the salt below -- so a load issued behind that point is a round trip of its own)
+    core.template fetch_bias<64 * NWH>(bias_ld, a.np.wpack, tid);
+    // (and the one kernel argument that is first used behind the stage reads is fetched here: a scalar load shares its
+    //  counter with the LDS reads and returns out of order, so its use waits for every ds_read issued in front of it)
+    asm volatile("" ::"s"(a.zero_state));
+  } else
+    core.load(a.np.wpack, lane);
   __builtin_amdgcn_sched_barrier(0);                    // (everything above is issue only; the uses start below)
   L2O_LAUNCH_MARK(1);
 
@@ -452,6 +486,13 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
   // does not touch before step 1.  Only a confirmed same-XCD pair uses the L2-resident plain stores.
   // The granule is PUBLISHED here, the moment the salt is known, and POLLED in front of the loop, behind the drain:
   // the partner's round trip runs under this wave's own loads.
+  if constexpr (kStage) {
+    // the completion point of this wave's fragment copies (they count in its vmcnt) -- and the prologue's one drain: with a
+    // copy into LDS in flight hipcc waits for vmcnt(0), not for a count, at the first use of a loaded value, which is the
+    // salt right below.  Said here in so many words; the granule's store is issued BEHIND it and nothing waits for that.
+    L2O_LAUNCH_MARK_LANDED(2);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
   const unsigned seq_w = __builtin_amdgcn_readfirstlane(seq_v), fault_w = __builtin_amdgcn_readfirstlane(fault_v);
   const unsigned salt = pa.use_salt ? ((seq_w + 1u) & 0x7fffu) << 16 : 0u;
   unsigned long long* mine = pa.xbuf + ((size_t)bl * 2 + half) * 2 * SQ;
@@ -467,8 +508,19 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
   __builtin_amdgcn_sched_barrier(0);
   __shared__ __attribute__((aligned(16))) float bias_s[Core::kBiasFloats];   // the gate biases = accumulator inits
   // (64 * NWH = the workgroup size the launcher uses: a compile-time stride, one masked load per thread instead of a loop)
-  core.stage_bias(bias_s, a.np.wpack, tid, 64 * NWH, q);     // (the handshake's __syncthreads() below orders it)
-  core.pin();   // fragments -> AGPRs (MFMA reads them there): the VGPRs hold W, the state and the gate math
+  if constexpr (kStage) core.template put_bias<64 * NWH>(bias_s, bias_ld, tid, q);
+  else core.stage_bias(bias_s, a.np.wpack, tid, 64 * NWH, q);     // (the handshake's __syncthreads() below orders it)
+  if constexpr (kStage) {
+    // every wave has drained its copies in front of the salt; behind this barrier it knows that the others have too, and
+    // only then is the stage read -- nothing else orders a ds_read behind a copy in flight.  A bare s_barrier (the asm
+    // statements fence the compiler): __syncthreads() would wait for the granule's store on top.
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    core.read_stage(frag_stage, lane);
+    __builtin_amdgcn_sched_barrier(0);                  // (the reads are issued HERE; they land under the poll below)
+  } else
+    core.pin();   // fragments -> AGPRs (MFMA reads them there): the VGPRs hold W, the state and the gate math
   constexpr bool kPk = L2O_GEMV_PK != 0;                    // packed GEMV FMAs: one wave per SIMD (see dot4pk)
   l2o::f32x4 wrq[2][NWH], wtq[CH];                          // (the same values as register quads for the packed FMAs)
 #pragma unroll
@@ -498,7 +550,7 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
     dead = true;
     if (tid == 0) atomicExch(&pa.ws->status, 1u);
   }
-  L2O_LAUNCH_MARK_LANDED(2);
+  if constexpr (!kStage) L2O_LAUNCH_MARK_LANDED(2);
   // ---- handshake, second half: the partner's granule (published at ITS salt, a prologue ago)
   __shared__ __attribute__((aligned(16))) int same_xcd_s4[4];
   int& same_xcd_s = same_xcd_s4[0];
@@ -517,9 +569,12 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
   }
   __syncthreads();
   const bool same_xcd = same_xcd_s != 0;
+  if constexpr (kStage) core.pin();                     // (the staged fragments, landed by now)
   L2O_LAUNCH_MARK(3);
 
+#define L2O_PAIR_FX_PTR 1
 #include "l2o_unroll_pair_loop.h"
+#undef L2O_PAIR_FX_PTR
 }
 
 template <int PRE, int KIND, int CH, bool HIST, bool EXACT = false, bool FAST = false>
@@ -540,36 +595,68 @@ __global__ __launch_bounds__(256) void k_combine_halves(const float* __restrict_
                                                         unsigned long long* __restrict__ xbuf, long xwords, PairWs* ws,
                                                         int b0, int B_local) {
   // nb problems of this launch = problems [b0, b0 + nb) of the shard (fx_part rows have B_local entries).  256 threads:
-  // wave 0 forms the sums (one problem per lane, the partials of a problem as 16-byte loads, all in flight), every
-  // wave zeroes a share of the granules (4.8 -> 3.x us: the kernel sits between two unrolls of a bench step)
+  // waves 1..3 zero the granules, wave 0 forms the sums.  The kernel sits between two unrolls of a bench step, so what
+  // counts is its chain of dependent memory round trips (round 13): the sequence word is fetched at entry, not in front
+  // of its store; a lane has the partials of BOTH its problems (nb <= 128: lane and lane + 64) in flight before its first
+  // add -- clamped addresses and selects, no loop whose loads wait for its counter; the granules go out 16 bytes per
+  // store, from waves that have no load pending (stores and loads share the wave's memory counter: in one wave the second
+  // round of stores waited for the loads).  The adds and their order are what they were: per problem ((p0 + p1) + p2) +
+  // ..., per lane 0 + f(lane) + f(lane + 64), then wave_sum64.
   const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  if (tid < 64) {
-    float acc = 0.0f;
-    for (int b = lane; b < nb; b += 64) {
+  if (tid >= 64) {
+    // block t zeroes pairs [t per2, (t + 1) per2) of the xwords / 2 whole pairs of granules (the area is 16-byte aligned:
+    // it follows the 192-byte header); the last granule of an odd count is wave 0's, below
+    const long npairs = xwords >> 1;
+    const long per2 = (npairs + gridDim.x - 1) / gridDim.x;
+    const long lo = (long)t * per2, hi = lo + per2 < npairs ? lo + per2 : npairs;
+    ulonglong2* xpair = reinterpret_cast<ulonglong2*>(xbuf);
+    for (long e = lo + (tid - 64); e < hi; e += 192) xpair[e] = make_ulonglong2(0ull, 0ull);
+    return;
+  }
+  const bool bump = t == 0 && tid == 0;
+  unsigned seq0 = 0;
+  if (bump) seq0 = ws->seq;
+  float acc = 0.0f;
+  if (nb <= 128 && (nparts == 2 || nparts == 4 || nparts == 8)) {
+    const int bA = lane, bB = lane + 64;
+    const bool hA = bA < nb, hB = bB < nb;
+    const float* pA = fx_half + ((size_t)t * nb + (hA ? bA : 0)) * nparts;
+    const float* pB = fx_half + ((size_t)t * nb + (hB ? bB : 0)) * nparts;
+    float fA, fB;
+    if (nparts == 8) {
+      const float4 a0 = *reinterpret_cast<const float4*>(pA), a1 = *reinterpret_cast<const float4*>(pA + 4);
+      const float4 c0 = *reinterpret_cast<const float4*>(pB), c1 = *reinterpret_cast<const float4*>(pB + 4);
+      fA = ((a0.x + a0.y) + a0.z) + a0.w;
+      fA = (((fA + a1.x) + a1.y) + a1.z) + a1.w;
+      fB = ((c0.x + c0.y) + c0.z) + c0.w;
+      fB = (((fB + c1.x) + c1.y) + c1.z) + c1.w;
+    } else if (nparts == 4) {
+      const float4 a0 = *reinterpret_cast<const float4*>(pA), c0 = *reinterpret_cast<const float4*>(pB);
+      fA = ((a0.x + a0.y) + a0.z) + a0.w;
+      fB = ((c0.x + c0.y) + c0.z) + c0.w;
+    } else {
+      const float2 a0 = *reinterpret_cast<const float2*>(pA), c0 = *reinterpret_cast<const float2*>(pB);
+      fA = a0.x + a0.y;
+      fB = c0.x + c0.y;
+    }
+    if (hA) { fx_part[(size_t)t * B_local + b0 + bA] = fA; acc += fA; }
+    if (hB) { fx_part[(size_t)t * B_local + b0 + bB] = fB; acc += fB; }
+  } else {
+    for (int b = lane; b < nb; b += 64) {                  // (any other shape: the loop of rounds 7-12)
       const float* p = fx_half + ((size_t)t * nb + b) * nparts;
-      float f;
-      if ((nparts & 3) == 0) {                           // (2 * NWH = 4 or 8 partials: whole float4s, 16-byte aligned)
-        const float4 p0 = *reinterpret_cast<const float4*>(p);
-        f = ((p0.x + p0.y) + p0.z) + p0.w;               // (the order of the scalar loop below)
-        for (int k = 4; k < nparts; k += 4) {
-          const float4 pk = *reinterpret_cast<const float4*>(p + k);
-          f = (((f + pk.x) + pk.y) + pk.z) + pk.w;
-        }
-      } else {
-        f = p[0];
-        for (int k = 1; k < nparts; ++k) f += p[k];
-      }
+      float f = p[0];
+      for (int k = 1; k < nparts; ++k) f += p[k];
       fx_part[(size_t)t * B_local + b0 + b] = f;
       acc += f;
     }
-    if (fx) {                                             // (single-launch batches only: nb == B_local)
-      acc = l2o::wave_sum64(acc);
-      if (lane == 0) fx[t] = acc * inv_bg;
-    }
   }
-  const long per = (xwords + gridDim.x - 1) / gridDim.x;
-  const long lo = (long)t * per, hi = lo + per < xwords ? lo + per : xwords;
-  for (long e = lo + tid; e < hi; e += 256) xbuf[e] = 0ull;
-  if (t == 0 && tid == 0) ws->seq = ws->seq + 1u;
+  if (fx) {                                               // (single-launch batches only: nb == B_local)
+    acc = l2o::wave_sum64(acc);
+    if (lane == 0) fx[t] = acc * inv_bg;
+  }
+  if (bump) {
+    if (xwords & 1) xbuf[xwords - 1] = 0ull;
+    ws->seq = seq0 + 1u;
+  }
 }
 #endif

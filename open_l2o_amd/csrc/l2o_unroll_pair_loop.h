@@ -25,6 +25,14 @@
 #ifdef L2O_ABLATE_EXCHANGE
   poll_salt = salt | 0x80000000u;
 #endif
+#if L2O_PAIR_FX_PTR
+  // the loss partial of (step t, this wave) lives at [(t nb + bl) 2 NWH + half NWH + wv]: a pointer that advances by one
+  // step's row (round 12's open item "Cfx", round 13) instead of two scalar multiplies, adds and a shift per step.  The
+  // including body chooses: the gather kernel keeps the address computed from t -- its loop's text, and so its ISA, is
+  // what it was.
+  float* fxp = pa.fx_half + (size_t)bl * (2 * NWH) + half * NWH + wv;
+  const size_t fx_stride = (size_t)pa.nb * (2 * NWH);
+#endif
   L2O_LAUNCH_MARK(4);
   const long long loop_t0 = __builtin_readcyclecounter();
   // The plain kernel ends with the loss at x_T, i.e. with the first half of a step.  That half stands once more BEHIND its

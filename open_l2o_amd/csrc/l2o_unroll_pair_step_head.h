@@ -136,5 +136,10 @@
       __builtin_amdgcn_sched_group_barrier(0x002, 24, 0);
       // (every lane stores: wave_sum64 leaves the same bits on all 64 lanes, so the one address gets one value and the
       //  store needs no exec-masked region -- 3 857 -> 3 813 cycles per step on config 2)
+#if L2O_PAIR_FX_PTR                                                 // (the FAST body: an advancing pointer, one add per step)
+      *fxp = fw;
+      fxp += fx_stride;
+#else
       pa.fx_half[((size_t)t * pa.nb + bl) * (2 * NWH) + half * NWH + wv] = fw;
+#endif
     }
