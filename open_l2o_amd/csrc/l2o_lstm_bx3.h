@@ -314,7 +314,10 @@ __device__ __forceinline__ f32x4 mfma_bf(u32x4 a, u32x4 b, f32x4 c) {
 // PIN = false: no pinning asm -- that empty asm is a USE of the loaded registers, so the compiler waits for the five reads
 // right there (s_waitcnt lgkmcnt(4..0) directly behind them: one exposed LDS round trip per call).  A caller that issues
 // the reads in front of a point that drains the LDS queue anyway (the step's barrier) fences them with
-// __builtin_amdgcn_sched_barrier(0) instead and pays nothing (round 4, k_unroll_pair).
+// __builtin_amdgcn_sched_barrier(0) instead (round 4, k_unroll_pair).  Cheaper than the pinned form, not free: the drain in
+// front of the barrier then waits for these reads too, and with every wave of the CU issuing them at the same moment that
+// measured 100-130 cycles per step (round 14: the kernels that have the registers keep the quads there instead, see
+// LstmCoreRegs::hold_bias).
 template <int LAYER, class W, bool PIN = true>
 __device__ __forceinline__ void preload_bias(const W& w, f32x4 (&acc)[kNT]) {
 #pragma unroll
@@ -816,6 +819,21 @@ struct LstmCoreRegs {
     bx::preload_bias<0, WT, false>(w, acc1);
     bx::preload_bias<1, WT, false>(w, acc2);
   }
+  // The REGISTER form of the accumulator inits (k_unroll_pair where kPairBiasRegs says so): the lane's ten bias quads, read
+  // from the staged table ONCE -- hold_bias(), behind the barrier that follows stage_bias / put_bias -- and kept for the
+  // whole launch.  arm() starts a step's accumulators from them: a copy in the source only, since an MFMA's C operand need
+  // not be its D register -- the first MFMA of each accumulation chain reads the bias quad as C and writes the accumulator.
+  // No LDS read per step.  40 registers: a kernel that takes this form has to have them (scripts/so_regs.py); one that
+  // never calls hold_bias() does not carry them.
+  f32x4 bias1r[kNT], bias2r[kNT];
+  __device__ __forceinline__ void hold_bias() {
+    bx::preload_bias<0>(w, bias1r);
+    bx::preload_bias<1>(w, bias2r);
+  }
+  __device__ __forceinline__ void arm(f32x4 (&acc1)[kNT], f32x4 (&acc2)[kNT]) const {
+#pragma unroll
+    for (int t = 0; t < kNT; ++t) { acc1[t] = bias1r[t]; acc2[t] = bias2r[t]; }
+  }
   template <int LO, int HI>
   __device__ __forceinline__ void issue_l1_prev(const TileState&, f32x4 (&acc1)[kNT]) {
     bx::issue<PRE, bx::kChL1H, LO, HI, true>(w, b1, acc1);
@@ -824,9 +842,9 @@ struct LstmCoreRegs {
   __device__ __forceinline__ void issue_l2_prev(const TileState&, f32x4 (&acc2)[kNT]) {
     bx::issue<PRE, bx::kChL2B, LO, HI, true>(w, b2, acc2);
   }
-  // REARM = false: the caller re-arms the accumulators itself (preload()) at a point where the bias reads' latency is
-  // free -- finish<.., true> issues them right behind the gate blocks and the pinning asm WAITS for them there, i.e.
-  // in front of the split of h1 and in front of the output Linear / the x update (round 4, k_unroll_pair)
+  // REARM = false: the caller re-arms the accumulators itself -- arm() from the registers, or preload_unpinned() in front
+  // of its barrier -- finish<.., true> issues the reads right behind the gate blocks and the pinning asm WAITS for them
+  // there, i.e. in front of the split of h1 and in front of the output Linear / the x update (round 4, k_unroll_pair)
   template <bool NEXT, class Shadow = bx::NoShadow, bool REARM = true>
   __device__ __forceinline__ float finish(TileState& s, f32x4 (&acc1)[kNT], f32x4 (&acc2)[kNT], float in0, float in1,
                                           int q, PhaseClock& pc, Shadow&& shadow = Shadow()) {
@@ -849,6 +867,16 @@ template <int PRE, bool BX, bool FAST, bool PK = bx::packed_default(PRE)>
 struct LstmCorePair : LstmCore<PRE, BX, PK> {};
 template <int PRE>
 struct LstmCorePair<PRE, true, true, true> : LstmCoreRegs<PRE, true, bx::NetWB<PRE, true>, L2O_PAIR_SPLIT_SCALAR != 0> {};
+// Which instantiations of k_unroll_pair keep the gate biases in registers (LstmCoreRegs::hold_bias / arm) instead of
+// re-reading the LDS table every step (preload_unpinned): the plain kernels with the bf16x3 core, FAST and gather, wherever
+// the 40 registers fit without a spill (scripts/so_regs.py).  They do not in two gather instantiations -- LogAndSign on
+// rastrigin / square_cos at CH = 8: 512 registers and two spills -- which keep the LDS reads, text and ISA.  So do the
+// recording kernels (CH = 8 spills; not split by CH), and the exact-gates kernels have another core
+// (profiles/r14_bias_registers.txt).
+template <int PRE, int KIND, int CH, bool HIST, bool EXACT, bool FAST>
+constexpr bool kPairBiasRegs =
+    !HIST && !EXACT &&
+    (FAST || !(PRE == L2O_PRE_LOGSIGN && (KIND == L2O_PROB_RASTRIGIN || KIND == L2O_PROB_SQUARE_COS) && CH == 8));
 // the 6-product form with chunk LDSCH in LDS (bx::NetWBH); stage_chunk: every thread copies its share, a barrier follows
 template <int PRE, int LDSCH>
 struct LstmCoreHyb : LstmCoreRegs<PRE, false, bx::NetWBH<PRE, LDSCH>> {

@@ -319,6 +319,7 @@ __device__ __forceinline__ void unroll_pair_body_gather(const UnrollPairArgs& pa
   const bool same_xcd = same_xcd_s != 0;
   L2O_LAUNCH_MARK(3);
 
+  constexpr bool kBiasRegs = kPairBiasRegs<PRE, KIND, CH, HIST, EXACT, false>;
 #define L2O_PAIR_FX_PTR 0
 #include "l2o_unroll_pair_loop.h"
 #undef L2O_PAIR_FX_PTR
@@ -572,6 +573,7 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
   if constexpr (kStage) core.pin();                     // (the staged fragments, landed by now)
   L2O_LAUNCH_MARK(3);
 
+  constexpr bool kBiasRegs = kPairBiasRegs<PRE, KIND, CH, HIST, EXACT, true>;
 #define L2O_PAIR_FX_PTR 1
 #include "l2o_unroll_pair_loop.h"
 #undef L2O_PAIR_FX_PTR

@@ -4,7 +4,13 @@
 // does not move the schedule of the other (profiles/r08_launch_fixed_cost.txt, section 8).  No include guard: included twice.
   f32x4 acc1[kNT], acc2[kNT];
   core.init(s, q);
-  core.preload(acc1, acc2);                                 // accumulator inits of the first step (the biases)
+  // accumulator inits of the first step (the biases).  Register form (kBiasRegs, set by the including body): the ten quads
+  // are read from the staged table here, once, and the first step is armed from the same registers as every later one
+  if constexpr (kBiasRegs) {
+    core.hold_bias();
+    core.arm(acc1, acc2);
+  } else
+    core.preload(acc1, acc2);
   // (both recurrent chunks -- L1H: h1(t-1) -> layer 1, L2B: h2(t-1) -> layer 2 -- are issued inside the step loop,
   //  in the window where the wave waits for its partner's partial residuals)
   PhaseClock pc;

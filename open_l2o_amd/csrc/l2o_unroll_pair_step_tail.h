@@ -53,8 +53,13 @@
     __builtin_amdgcn_sched_barrier(0);
     xs[wv * kTile + c] = live ? xv * sc : 0.0f;           // (all four q lanes, the same value: see above)
     __builtin_amdgcn_sched_barrier(0);
-    // the next step's accumulator inits (the gate biases: 10 ds_read_b128) go out HERE: their latency overlaps the wait
-    // for barrier B1, which drains this wave's LDS queue anyway
-    core.preload_unpinned(acc1, acc2);
+    // the next step's accumulator inits (the gate biases).  Register form (kPairBiasRegs): no instruction at all -- the first
+    // MFMA of each chain takes its bias quad as C.  LDS form (the recording kernels, two gather instantiations): 10
+    // ds_read_b128 go out HERE, in front of barrier B1.  Their latency is NOT free, as this comment said from round 4 to round
+    // 13: the s_waitcnt lgkmcnt(0) in front of the barrier waits for all ten and not only for the xs write above, the four
+    // waves of a CU arrive together and their 40 reads queue in front of it -- 130 cycles per step on the phase clock of
+    // config 2, 100 in the step loop's counter (profiles/r14_bias_registers.txt)
+    if constexpr (kBiasRegs) core.arm(acc1, acc2);
+    else core.preload_unpinned(acc1, acc2);
     __builtin_amdgcn_sched_barrier(0);
     pc.mark(9);
