@@ -15,22 +15,21 @@ launch that continues from the first one's x / LSTM state / moments:
  * a matrix that is not 16-byte aligned takes the gather inside the FAST kernel and gives the same bytes;
  * the injected partner timeout (workspace fault word) still raises the sticky status in both kernels.
 """
-import hashlib
-import os
+import dataclasses
 
 import numpy as np
 import pytest
-import torch
 
 import oracle as O
+import unroll_harness as H
 from helpers import device_problem, lib_option, make_params, make_problem, max_abs, rel_err, spec_of
 from open_l2o_amd import _abi
-from open_l2o_amd._engine import ProblemDesc
+from unroll_harness import eng  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 T = 3
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pair_launch_paths_parent.npz")
+GOLDEN = H.GOLDEN_DIR + "/pair_launch_paths_parent.npz"
 
 # id -> (net, kind, B, D, M, shared matrix, recording launch, x_scale, problem seed)
 # (the seeds are part of tests/golden/pair_launch_paths_parent.npz: a case keeps its seed for good)
@@ -52,20 +51,14 @@ STEP_CASES = sorted(c for c in CASES if not CASES[c][7])
 RAGGED = ("quadratic_d24", "quadratic_d100", "lasso_m48_d64")
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from open_l2o_amd._engine import HipEngine
-    return HipEngine()
-
-
 class _Setup:
     def __init__(self, eng, case, misalign=False):
         name, kind, B, D, M, shared, record, scaled, seed = CASES[case]
         self.eng, self.B, self.D, self.record = eng, B, D, record
         self.cfg = {"dm": O.DM_IDENTITY, "rnnprop": O.RNNPROP}[name]
-        self.rnnprop = name == "rnnprop"
         self.spec = spec_of(self.cfg)
-        self.wpack = eng.pack_weights(self.spec, make_params(self.cfg, seed=5, trained_like=True))
+        self.params = make_params(self.cfg, seed=5, trained_like=True)
+        self.wpack = eng.pack_weights(self.spec, self.params)
         _, x0, arrays = make_problem(kind, B, D, seed=seed, M=M)
         if shared:
             arrays = dict(arrays, W=np.ascontiguousarray(arrays["W"][0]), w_shared=True)
@@ -76,48 +69,32 @@ class _Setup:
             buf = eng.zeros(W.numel() + 4)
             buf[1:1 + W.numel()].copy_(W.reshape(-1))
             self._keep = buf
-            self.pd = ProblemDesc(kind=self.pd.kind, B_local=B, B_global=B, D=D, M=self.pd.M, l1=self.pd.l1,
-                                  alpha=self.pd.alpha, W=buf[1:1 + W.numel()], y=self.pd.y, C=self.pd.C, x_scale=None,
-                                  w_shared=self.pd.w_shared)
+            self.pd = dataclasses.replace(self.pd, W=buf[1:1 + W.numel()], x_scale=None)
             assert self.pd.W.data_ptr() % 16 == 4
-        self.x0 = eng.tensor(x0.reshape(B, D))
+        self.x0 = x0.reshape(B, D)
+
+    def fresh(self):
+        """The launch from x0 and the zero state, on buffers of its own."""
+        return H.prepare(self.eng, self.cfg, self.params, self.pd, T, x0=self.x0, record=self.record, wpack=self.wpack)
 
     def fused(self):
         """Two launches on the two-CU kernel: fresh (x0, zero state), then continuing.  -> [dict of host arrays] x 2"""
-        e, B, D = self.eng, self.B, self.D
-        x, st = e.zeros(B, D), e.state_alloc(B, D)
-        m, v = (e.zeros(B, D), e.zeros(B, D)) if self.rnnprop else (None, None)
+        first = self.fresh()
         outs = []
-        for launch in range(2):
-            fx_part, fx = e.zeros((T + 1) * B), e.zeros(T + 1)
-            hist = None
-            if self.record:
-                N = B * D
-                hist = {"st": e.zeros(T, st.numel()), "g": e.zeros(T, N), "g_final": e.zeros(N),
-                        "m": e.zeros(T, N), "v": e.zeros(T, N)}
-            if launch == 0:
-                e.unroll(self.spec, self.wpack, self.pd, x, st, m, v, T, 1, fx_part, hist=hist, fx=fx, x0=self.x0,
-                         zero_state=True)
-            else:
-                e.unroll(self.spec, self.wpack, self.pd, x, st, m, v, T, 1 + T, fx_part, hist=hist, fx=fx)
-            assert e.last_unroll_form()[0] == "k_unroll_pair"
+        for launch in (first, first.then(1 + T)):
+            r = launch.run()
+            assert r.form == "k_unroll_pair"
+            D = self.D
             full = self.pd.M == D and D in (32, 64, 128)       # (an unaligned matrix gathers INSIDE the FAST kernel)
-            assert e.last_unroll_variant() == dict(CH=(D + 31) // 32 * 2 if D <= 64 else 8, HIST=int(self.record), EXACT=0,
-                                                   FAST=int(full and _abi.get_option(_abi.OPT_PAIR_FAST_LOAD) == 1), KR=0, NV=0)
-            out = {"fx": fx, "fx_part": fx_part, "x": x, "st": st}
-            if m is not None:
-                out.update(m=m, v=v)
-            if hist is not None:
-                out.update({"hist_" + k: t for k, t in hist.items()})
-            torch.cuda.synchronize()
-            assert int(e._last_ws[0:4].view(torch.int32).item()) == 0          # (no partner timeout)
-            outs.append({k: t.cpu().numpy().copy() for k, t in out.items()})
+            assert r.variant == dict(CH=(D + 31) // 32 * 2 if D <= 64 else 8, HIST=int(self.record), EXACT=0,
+                                     FAST=int(full and _abi.get_option(_abi.OPT_PAIR_FAST_LOAD) == 1), KR=0, NV=0)
+            outs.append(r.host)
         return outs
 
     def steps(self):
         """The same 2 T steps on the step-granular kernels.  -> (fx[0..2T], x after T steps, x after 2 T steps)"""
         e, B, D = self.eng, self.B, self.D
-        xd, std, md, vd = self.x0.clone(), e.state_alloc(B, D), e.zeros(B, D), e.zeros(B, D)
+        xd, std, md, vd = e.tensor(self.x0), e.state_alloc(B, D), e.zeros(B, D), e.zeros(B, D)
         f, g = e.zeros(B), e.zeros(B, D)
         fx = e.zeros(2 * T + 1)
         b95 = float(np.float32(0.95))
@@ -144,19 +121,13 @@ def _fast_outputs(eng, case):
     return _FAST[case]
 
 
-def _assert_same(a, b, what):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert a[k].tobytes() == b[k].tobytes(), "%s: %s differs" % (what, k)
-
-
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_fast_load_equals_predicated_gather(eng, case):
     fast = _fast_outputs(eng, case)
     with lib_option(_abi.OPT_PAIR_FAST_LOAD, 0):
         slow = _Setup(eng, case).fused()
     for i, what in enumerate(("fresh launch", "continuing launch")):
-        _assert_same(fast[i], slow[i], "%s, %s" % (case, what))
+        H.assert_same_bytes(fast[i], slow[i], "%s, %s" % (case, what))
     assert np.all(np.isfinite(fast[1]["fx"])) and (fast[0]["fx"] != fast[1]["fx"]).any()
 
 
@@ -172,10 +143,6 @@ def test_fused_equals_step_granular_path(eng, case):
         assert e_x < 1e-5 * max(1.0, float(np.abs(want_x).max()))
 
 
-def _digest(a):
-    return np.frombuffer(hashlib.sha256(a.tobytes()).digest(), dtype=np.uint8)
-
-
 @pytest.mark.parametrize("case", RAGGED)
 def test_ragged_shapes_equal_the_parent_commit(eng, case):
     """Ragged shapes take the predicated gather whatever the option says; x and fx of both launches equal the arrays the
@@ -188,7 +155,8 @@ def test_ragged_shapes_equal_the_parent_commit(eng, case):
             for k in ("x", "fx"):
                 want = gold["%s/%d/%s" % (case, i, k)]
                 assert out[k].tobytes() == want.tobytes(), (case, i, k, fast_load)
-            assert _digest(out["st"]).tobytes() == gold["%s/%d/st_sha256" % (case, i)].tobytes(), (case, i, fast_load)
+            digest = np.frombuffer(bytes.fromhex(H.sha(out["st"])), dtype=np.uint8)
+            assert digest.tobytes() == gold["%s/%d/st_sha256" % (case, i)].tobytes(), (case, i, fast_load)
 
 
 def test_unaligned_matrix_takes_the_gather(eng):
@@ -196,7 +164,7 @@ def test_unaligned_matrix_takes_the_gather(eng):
     fast = _fast_outputs(eng, case)
     off = _Setup(eng, case, misalign=True).fused()
     for i in range(2):
-        _assert_same(fast[i], off[i], "matrix 4 bytes off, launch %d" % i)
+        H.assert_same_bytes(fast[i], off[i], "matrix 4 bytes off, launch %d" % i)
 
 
 @pytest.mark.parametrize("case", ["quadratic_d128_b3", "quadratic_d24"])
@@ -208,15 +176,11 @@ def test_injected_timeout_still_raises_status(eng, case):
     s.fused()                                                    # (allocates / lays out the workspace for this shape)
     ws = eng._workspace
     eng.inject_unroll_fault()
-    e, B, D = eng, s.B, s.D
-    x, st = e.zeros(B, D), e.state_alloc(B, D)
-    fx_part, fx = e.zeros((T + 1) * B), e.zeros(T + 1)
-    e.unroll(s.spec, s.wpack, s.pd, x, st, None, None, T, 1, fx_part, fx=fx, x0=s.x0, zero_state=True)
-    torch.cuda.synchronize()
-    assert int(ws[0:4].view(torch.int32).item()) == 1
+    s.fresh().run(check=False)                                   # (synchronises: the launch came back)
+    assert H.ws_word(ws, H.WS_STATUS) == 1
     with pytest.raises(_abi.L2OPartnerTimeout):
         eng.check_unroll_status()                                # (clears the workspace, the fault word with it)
-    assert int(ws[0:4].view(torch.int32).item()) == 0 and int(ws[8:12].view(torch.int32).item()) == 0
+    assert H.ws_word(ws, H.WS_STATUS) == 0 and H.ws_word(ws, H.WS_FAULT) == 0
     again = s.fused()
     for i in range(2):
-        _assert_same(again[i], ref[i], "%s after the timeout, launch %d" % (case, i))
+        H.assert_same_bytes(again[i], ref[i], "%s after the timeout, launch %d" % (case, i))

@@ -7,23 +7,18 @@ freshly zeroed one bit for bit (granules, ws->seq and the loss partials re-arm b
 exactly one per launch; fx equals l2o_reduce_fx over fx_part bit for bit; the recording and the multi-launch (chunked)
 forms; a launch that took the timeout path returns and the next one on the same workspace is clean."""
 import pytest
-import torch
 
 import oracle as O
+import unroll_harness as H
 from helpers import device_problem, lib_option, make_params, make_problem, spec_of
 from open_l2o_amd import _abi
+from unroll_harness import eng  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from open_l2o_amd._engine import HipEngine
-    return HipEngine()
-
-
 def _seq(eng):
-    return int(eng._last_ws[4:8].view(torch.int32).item()) & 0xffffffff
+    return H.ws_word(eng._last_ws, H.WS_SEQ)
 
 
 class _Case:
@@ -31,48 +26,24 @@ class _Case:
     zero state: every launch of it computes the same thing, whatever ran on the workspace before."""
 
     def __init__(self, eng, name, kind, B, D, T, seed, record=False):
-        cfg = {"dm": O.DM_IDENTITY, "rnnprop": O.RNNPROP}[name]
-        self.eng, self.B, self.D, self.T, self.rnnprop = eng, B, D, T, name == "rnnprop"
-        self.spec = spec_of(cfg)
-        self.wpack = eng.pack_weights(self.spec, make_params(cfg, seed=5, trained_like=True))
-        _, x0, arrays = make_problem(kind, B, D, seed=seed)
+        self.cfg = {"dm": O.DM_IDENTITY, "rnnprop": O.RNNPROP}[name]
+        self.eng, self.T, self.record = eng, T, record
+        self.params = make_params(self.cfg, seed=5, trained_like=True)
+        self.wpack = eng.pack_weights(spec_of(self.cfg), self.params)
+        _, self.x0, arrays = make_problem(kind, B, D, seed=seed)
         self.pd = device_problem(eng, arrays, B, D)
-        self.x0 = eng.tensor(x0.reshape(B, D))
-        self.record = record
 
-    def run(self):
-        e, B, D, T = self.eng, self.B, self.D, self.T
-        x, st = e.zeros(B, D), e.state_alloc(B, D)
-        m, v = (e.zeros(B, D), e.zeros(B, D)) if self.rnnprop else (None, None)
-        fx_part, fx = e.zeros((T + 1) * B), e.zeros(T + 1)
-        hist = None
-        if self.record:
-            N = B * D
-            hist = {"st": e.zeros(T, st.numel()), "g": e.zeros(T, N), "g_final": e.zeros(N)}
-            if self.rnnprop:
-                hist.update(m=e.zeros(T, N), v=e.zeros(T, N))
-        e.unroll(self.spec, self.wpack, self.pd, x, st, m, v, T, 1, fx_part, hist=hist, fx=fx, x0=self.x0,
-                 zero_state=True)
-        out = {"fx": fx, "fx_part": fx_part, "x": x, "st": st}
-        if m is not None:
-            out.update(m=m, v=v)
-        if hist is not None:
-            out.update({"hist_" + k: t for k, t in hist.items()})
-        torch.cuda.synchronize()
-        return {k: t.cpu().numpy() for k, t in out.items()}
+    def run(self, check=True):
+        """One launch on buffers of its own -> {name: host array}"""
+        return H.prepare(self.eng, self.cfg, self.params, self.pd, self.T, x0=self.x0, record=self.record,
+                         wpack=self.wpack).run(check).host
 
 
 def _fresh(eng):
     """Zero the engine's workspace (what l2o_unroll_workspace_init leaves; none yet: the next launch allocates a zeroed one)."""
     if eng._workspace is not None:
         eng._workspace.zero_()
-        torch.cuda.synchronize()
-
-
-def _assert_same(a, b, what):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert a[k].tobytes() == b[k].tobytes(), "%s: %s differs" % (what, k)
+        eng.synchronize()
 
 
 def _assert_fx_is_reduce_fx(eng, out, B, T):
@@ -97,7 +68,7 @@ def test_back_to_back_launches_equal_fresh_workspace(eng, name, kind, B, D):
         s0 = _seq(eng)
         out = cases[i & 1].run()
         assert _seq(eng) == (s0 + 1) & 0xffffffff, "ws->seq must advance by exactly one per launch"
-        _assert_same(out, ref[i & 1], "launch %d" % i)
+        H.assert_same_bytes(out, ref[i & 1], "launch %d" % i)
         _assert_fx_is_reduce_fx(eng, out, B, T)
     assert (ref[0]["fx"] != ref[1]["fx"]).any()                  # (the two instances differ: alternating them means something)
 
@@ -112,7 +83,7 @@ def test_recording_launches_equal_fresh_workspace(eng):
         s0 = _seq(eng)
         out = c.run()
         assert _seq(eng) == (s0 + 1) & 0xffffffff
-        _assert_same(out, ref, "recording launch %d" % i)
+        H.assert_same_bytes(out, ref, "recording launch %d" % i)
         _assert_fx_is_reduce_fx(eng, out, B, T)
 
 
@@ -130,7 +101,7 @@ def test_chunked_launches(eng):
             s0 = _seq(eng)
             out = c.run()
             assert _seq(eng) == (s0 + launches) & 0xffffffff
-            _assert_same(out, ref, "chunked launch %d" % i)
+            H.assert_same_bytes(out, ref, "chunked launch %d" % i)
             _assert_fx_is_reduce_fx(eng, out, B, T)
 
 
@@ -144,12 +115,12 @@ def test_timeout_path_returns_and_next_launch_is_clean(eng):
     ref = c.run()
     ws = eng._workspace
     s0 = _seq(eng)
-    ws[8:12].view(torch.int32).fill_(1)
-    c.run()                                                      # (run() synchronises: the launch came back)
-    assert int(ws[0:4].view(torch.int32).item()) == 1            # the sticky status word
+    H.set_ws_word(ws, H.WS_FAULT, 1)
+    c.run(check=False)                                           # (run() synchronises: the launch came back)
+    assert H.ws_word(ws, H.WS_STATUS) == 1                       # the sticky status word
     assert _seq(eng) == (s0 + 1) & 0xffffffff                    # (the dead launch's epilogue still ran)
-    ws[0:4].view(torch.int32).fill_(0)
-    ws[8:12].view(torch.int32).fill_(0)
+    H.set_ws_word(ws, H.WS_STATUS, 0)
+    H.set_ws_word(ws, H.WS_FAULT, 0)
     out = c.run()
-    assert int(ws[0:4].view(torch.int32).item()) == 0
-    _assert_same(out, ref, "launch after the timeout")
+    assert H.ws_word(ws, H.WS_STATUS) == 0
+    H.assert_same_bytes(out, ref, "launch after the timeout")

@@ -15,7 +15,8 @@ import pytest
 import torch
 
 import oracle as O
-from helpers import device_problem, lib_option, make_params, make_problem, rel_err, spec_of
+import unroll_harness as H
+from helpers import device_problem, lib_option, make_params, make_problem, rel_err
 from open_l2o_amd import _abi
 
 pytestmark = pytest.mark.gpu
@@ -31,24 +32,23 @@ def test_pair_exchange_soak(name, kind, D, B):
 
 def _soak(eng, name, kind, D, B):
     cfg = {"dm": O.DM_IDENTITY, "rnnprop": O.RNNPROP}[name]
-    spec = spec_of(cfg)
     params = make_params(cfg, seed=11, trained_like=True)
     T = 6
     prob, x0, arrays = make_problem(kind, B, D, seed=12)
-    wpack = eng.pack_weights(spec, params)
-    pd = device_problem(eng, arrays, B, D)
-    x0d = eng.tensor(x0.reshape(B, D))
-    x, st = x0d.clone(), eng.state_alloc(B, D)
-    m, v = eng.zeros(B, D), eng.zeros(B, D)
+    zeros = np.zeros((B, D), np.float32)
+    # ONE set of buffers for every launch (both nets are handed m / v), re-armed on the device before each call
+    one = H.prepare(eng, cfg, params, device_problem(eng, arrays, B, D), T, x=x0, m=zeros, v=zeros)
+    x, st, m, v = one.x, one.st, one.m, one.v
+    x0d = x.clone()
     fx_part = eng.zeros((T + 1) * B)
 
-    def launch(step0):
+    def launch():
         x.copy_(x0d); st.zero_(); m.zero_(); v.zero_()
-        eng.unroll(spec, wpack, pd, x, st, m, v, T, step0, fx_part)
+        one.call(fx_part)                                    # (no allocation, no host sync: the loop below is the test)
 
     # references: agent-scope stores (bit reference) and the oracle (tolerance)
     with lib_option(_abi.OPT_PAIR_PLAIN_STORES, 0):
-        launch(1)
+        launch()
         ref = [t.clone() for t in (fx_part, x, st, m, v)]
     res = O.unroll(prob, cfg, params, x0, O.net_initial_state(cfg, B * D), T)
     fx_ref = eng.to_numpy(ref[0]).reshape(T + 1, B).sum(1) / B
@@ -68,15 +68,15 @@ def _soak(eng, name, kind, D, B):
                 torch.mm(big, big, out=sink)                 # ~1.5 ms on every CU
                 for _ in range(4):
                     torch.mm(small, big, out=sink_s)         # short kernels on a few CUs
-        launch(1)
+        launch()
         for o, r in zip(outs, ref):
             mism += (o != r).sum()
         if i % 2500 == 2499:
             assert int(mism.item()) == 0, "a launch <= %d differs from the agent-scope reference" % i
             eng.check_unroll_status()
-    torch.cuda.synchronize()
+    eng.synchronize()
     assert int(mism.item()) == 0
     eng.check_unroll_status()
-    hdr = eng._last_ws[:8].cpu().numpy().view(np.uint32)
-    assert hdr[0] == 0 and hdr[1] >= N_LAUNCHES              # status clean, launch sequence advanced by the kernels
+    ws = eng._last_ws                                        # status clean, launch sequence advanced by the kernels
+    assert H.ws_word(ws, H.WS_STATUS) == 0 and H.ws_word(ws, H.WS_SEQ) >= N_LAUNCHES
     print("pair soak %s/%s: %d launches under a concurrent stream, 0 mismatching words, no timeout" % (name, kind, N_LAUNCHES))

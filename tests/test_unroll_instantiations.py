@@ -82,8 +82,10 @@ import numpy as np
 import pytest
 
 import oracle as O
+import unroll_harness as H
 from helpers import ORACLE_CFGS, as_float64, device_problem, make_params, make_problem, random_state, spec_of
 from open_l2o_amd import _abi
+from unroll_harness import eng  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -294,7 +296,7 @@ def inputs(recipe):
     return Inputs(cfg, params, prob, arrays, x0, state0, m0, v0, xs, B, D, recipe)
 
 
-def trajectory(inp, dtype):
+def trajectory(inp, dtype, T=T):
     """O.unroll (same operations, same order) with the per-step values kept: g[t] the gradient fed to the network, st[t]
     the state BEFORE step t, m[t] / v[t] the moments AFTER step t, g_final the gradient at x_T."""
     cfg, rn = inp.cfg, inp.cfg.kind == "rnnprop"
@@ -365,7 +367,7 @@ Reference = collections.namedtuple("Reference", "inp f64 f32 env ulp")
 ULP_DRAWS = 8
 
 
-def ulp_spread(inp):
+def ulp_spread(inp, T=T):
     """The float32 oracle's errors (as ``measure`` gives them, each against the float64 run of the same start) from
     ULP_DRAWS starts that differ from x0 by one ulp, up or down per coordinate -> the worst per quantity.  A kernel is one
     more float32 rounding of this computation; where a rounding-sized change of the start moves the oracle's own error
@@ -376,7 +378,7 @@ def ulp_spread(inp):
         up = rng.integers(0, 2, inp.x0.shape) > 0
         x0 = np.where(up, np.nextafter(inp.x0, np.float32(np.inf)), np.nextafter(inp.x0, np.float32(-np.inf)))
         p = inp._replace(x0=x0.astype(np.float32))
-        for k, e in measure(trajectory(p, np.float32), trajectory(p, np.float64)).items():
+        for k, e in measure(trajectory(p, np.float32, T), trajectory(p, np.float64, T)).items():
             worst[k] = max(worst.get(k, 0.0), e)
     return worst
 
@@ -411,12 +413,6 @@ def violations(err, env):
 
 # ---- the GPU side -------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def eng():
-    from open_l2o_amd._engine import HipEngine
-    return HipEngine()
-
-
-@pytest.fixture(scope="module")
 def tally():
     """template -> worst error per quantity and worst kernel / float32-oracle ratio; printed when the module is done."""
     t = {}
@@ -430,43 +426,34 @@ def tally():
 _WPACK = {}
 
 
-def launch(eng, cell, extra_options=None):
-    """One launch of the cell -> (outputs as host arrays, template name, variant dict, raw bytes of x / fx_part / state)."""
-    import torch
+def prepare(eng, cell, extra_options=None, T=T):
+    """The cell's launch (unroll_harness.Launch); the weights of a net are packed once per engine."""
     inp = inputs(recipe_of(cell))
-    B, D, N = inp.B, inp.D, inp.B * inp.D
-    spec = spec_of(inp.cfg)
-    if cell.net not in _WPACK:
-        _WPACK[cell.net] = eng.pack_weights(spec, inp.params)
-    wpack = _WPACK[cell.net]
-    rn = inp.cfg.kind == "rnnprop"
+    B, D = inp.B, inp.D
+    if (eng, cell.net) not in _WPACK:
+        _WPACK[eng, cell.net] = eng.pack_weights(spec_of(inp.cfg), inp.params)
     pd = device_problem(eng, inp.arrays, B, D, B_global=2 * B, x_scale=None if inp.xs is None else inp.xs.reshape(B, D))
-    x = eng.tensor(inp.x0.reshape(B, D))
-    st = eng.state_pack(*[eng.tensor(a) for hc in inp.state0 for a in hc], B, D)
-    m, v = (eng.tensor(inp.m0.reshape(B, D)), eng.tensor(inp.v0.reshape(B, D))) if rn else (None, None)
-    fx_part, fx = eng.zeros((T + 1) * B), eng.zeros(T + 1)
-    hist = None
-    if cell.variant["HIST"]:
-        hist = {"st": eng.zeros(T, st.numel()), "g": eng.zeros(T, N), "g_final": eng.zeros(N)}
-        if rn:
-            hist.update(m=eng.zeros(T, N), v=eng.zeros(T, N))
-    with _abi.option_scope(_merge(cell.options, extra_options or {})):
-        eng.unroll(spec, wpack, pd, x, st, m, v, T, STEP0, fx_part, hist=hist)
-        form, variant = eng.last_unroll_form()[0], eng.last_unroll_variant()
-    eng.reduce_fx(fx_part, T + 1, B, 2 * B, fx)
-    torch.cuda.synchronize()
-    eng.check_unroll_status()                                     # (raises on a partner timeout)
-    out = dict(fx=eng.to_numpy(fx), x=eng.to_numpy(x), st=[eng.to_numpy(a) for a in eng.state_unpack(st, B, D)])
-    if rn:
-        out.update(m=eng.to_numpy(m), v=eng.to_numpy(v))
-    if hist is not None:
-        out.update(hist_g=[eng.to_numpy(hist["g"][t]) for t in range(T)], g_final=eng.to_numpy(hist["g_final"]),
-                   hist_st=[[eng.to_numpy(a) for a in eng.state_unpack(hist["st"][t], B, D)] for t in range(T)])
-        if rn:
-            out.update(hist_m=[eng.to_numpy(hist["m"][t]) for t in range(T)],
-                       hist_v=[eng.to_numpy(hist["v"][t]) for t in range(T)])
-    raw = b"".join(eng.to_numpy(a).tobytes() for a in (x, fx_part, st))
-    return out, form, variant, raw
+    return H.prepare(eng, inp.cfg, inp.params, pd, T, x=inp.x0, state=inp.state0, m=inp.m0, v=inp.v0, step0=STEP0,
+                     options=_merge(cell.options, extra_options or {}), record=cell.variant["HIST"],
+                     wpack=_WPACK[eng, cell.net])
+
+
+def launch(eng, cell, extra_options=None, T=T):
+    """One launch of the cell -> (outputs as host arrays, template name, variant dict, raw bytes of x / fx_part / state)."""
+    r = prepare(eng, cell, extra_options, T).run()
+    B, D = r.dev["x"].shape
+
+    def unpacked(st):
+        return [eng.to_numpy(a) for a in eng.state_unpack(st, B, D)]
+
+    out = dict(fx=r.host["fx"], x=r.host["x"], st=unpacked(r.dev["st"]))
+    out.update({k: r.host[k] for k in ("m", "v") if k in r.host})
+    if "hist_g" in r.host:
+        out.update(hist_g=list(r.host["hist_g"]), g_final=r.host["hist_g_final"],
+                   hist_st=[unpacked(r.dev["hist_st"][t]) for t in range(T)])
+        out.update({k: list(r.host[k]) for k in ("hist_m", "hist_v") if k in r.host})
+    raw = b"".join(r.host[k].tobytes() for k in ("x", "fx_part", "st"))
+    return out, r.form, r.variant, raw
 
 
 def check_cell(eng, cell, tally=None, extra_options=None):
