@@ -12,6 +12,8 @@
 // floats so that the per-lane operand reads (ds_read_b32: lanes (m, k) -> row k, column 16 tile + m) are
 // bank-conflict free.  Both operands stream from HBM exactly once: 4 (KA + KB) bytes per row.
 #pragma once
+#include "l2o_lstm_bx3.h"
+#include "l2o_params.h"
 
 #ifndef L2O_ATB_ROWS
 #define L2O_ATB_ROWS 32

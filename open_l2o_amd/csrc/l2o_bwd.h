@@ -11,6 +11,8 @@
 //     dw_lin = h2^T dd   db_lin = sum dd      (RNNProp) dW_fc = feats^T du   db_fc = sum du
 // and the carries (dh1, dc1, dh2, dc2) that flow to the previous step.
 #pragma once
+#include "l2o_lstm_bx3.h"
+#include "l2o_params.h"
 
 struct BwdParams {
   int B, D, tpp;

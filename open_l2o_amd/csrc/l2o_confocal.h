@@ -28,6 +28,7 @@
 // erf differences in the tails are taken as erfc differences, so a point far outside the volume keeps full relative
 // accuracy in its (tiny) image instead of the rounding noise of 1 - 1.
 #pragma once
+#include "l2o_params.h"
 
 namespace l2o {
 

@@ -1,5 +1,5 @@
 // l2o_confocal_unroll.h -- the fused persistent unroll for problems.confocal_microscopy_3d: T optimizer steps on one batch
-// row in ONE launch (l2o_confocal_unroll / l2o_confocal_unroll_record).  Included by l2o_kernels.hip after l2o_confocal.h;
+// row in ONE launch (l2o_confocal_unroll / l2o_confocal_unroll_record).  Builds on l2o_confocal.h (the voxel model);
 // written for gfx950 only.
 //
 // The rows of the confocal optimizee are independent problems (no batch norm, no minibatch; the loss is a plain mean over
@@ -32,6 +32,8 @@
 // workgroup i serves row i % batch of instance i / batch and reads its pointers from the instance's table in device memory
 // (CfPtrs) instead of the kernel arguments.  Everything after the prologue is the same code, so the bits are the same.
 #pragma once
+#include "l2o_confocal.h"
+#include "l2o_lstm_bx3.h"
 #include "../../include/l2o_confocal_multi_abi.h"
 
 namespace l2o {

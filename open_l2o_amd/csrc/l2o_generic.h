@@ -10,6 +10,7 @@
 // ((hidden_1, cell_1), (hidden_2, cell_2), ...) tuples stored back to back.
 // Included by l2o_kernels.hip.
 #pragma once
+#include "l2o_params.h"
 
 constexpr int kGenMaxH = 64;
 constexpr int kGenMaxL = 3;

@@ -1,7 +1,7 @@
 // l2o_ilp_kernels.h -- the kernels that are compiled in a SECOND translation unit (l2o_kernels_ilp.hip) under hipcc's
-// max-ILP scheduling strategy (-mllvm -amdgpu-sched-strategy=max-ilp, a per-TU switch).  Included by l2o_kernels.hip right
-// behind the headers that define them: in the main TU as `extern template` declarations (no code there; the launchers bind
-// to the host stubs of the other object), in the ILP TU as explicit instantiations.
+// max-ILP scheduling strategy (-mllvm -amdgpu-sched-strategy=max-ilp, a per-TU switch).  Included by both: in the main TU as
+// `extern template` declarations (no code there; the launchers bind to the host stubs of the other object), in the ILP TU
+// (which defines L2O_TU_ILP) as explicit instantiations.
 //
 // Why (round 6, profiles/r06_frag_pipeline_ab.txt): where ONE wave per SIMD walks a dependent chain -- the plain two-CU
 // unroll, the optimizer phase of the streaming unroll -- the strategy is worth 1.2-2.1 % (config 2 9.10 -> 9.21 G, config 3
@@ -9,6 +9,8 @@
 // k_unroll_lds it costs 9.5 %, the RECORDING two-CU unroll gets 2 % slower, k_mlp_xcd does not move.  So only the plain
 // (HIST = false, EXACT = false) two-CU unrolls and the plain eight-wave streaming unrolls live here.
 #pragma once
+#include "l2o_unroll_pair.h"
+#include "l2o_unroll_cu8.h"
 
 #ifdef L2O_TU_ILP
 #define L2O_ILP_INST template

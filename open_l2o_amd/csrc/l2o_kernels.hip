@@ -18,6 +18,31 @@
 
 #include "l2o_common.h"
 #include "l2o_lstm_bx3.h"
+#include "l2o_params.h"
+#include "l2o_step.h"
+#include "l2o_problem_fg.h"
+#include "l2o_unroll.h"
+#include "l2o_unroll_pair.h"
+#include "l2o_unroll_lds.h"
+#include "l2o_unroll_cu.h"
+#include "l2o_unroll_cu8.h"
+#include "l2o_ilp_kernels.h"   // the plain two-CU / eight-wave unrolls: code in l2o_kernels_ilp.hip, `extern template` here
+#include "l2o_mlp.h"
+#include "l2o_mlp_unroll.h"
+#include "l2o_mlp_xcd.h"
+#include "l2o_mlp_deep.h"
+#include "l2o_mlp_hvp.h"
+#include "l2o_mnist_conv.h"
+#include "l2o_cifar_conv.h"
+#include "l2o_lenet.h"
+#include "l2o_confocal.h"
+#include "l2o_confocal_unroll.h"
+#include "l2o_generic.h"
+#include "l2o_atb.h"
+#include "l2o_bwd.h"
+#include "l2o_bwd_mfma.h"
+#include "l2o_vecops.h"
+#include "l2o_util_kernels.h"
 
 using namespace l2o;
 
@@ -49,881 +74,22 @@ static int fail(int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(L2O_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-static inline int tiles_per_problem(int64_t D) { return (int)((D + kTile - 1) / kTile); }
-
-// ---------------------------------------------------------------------------
-// kernel parameter blocks (plain structs passed by value)
-// ---------------------------------------------------------------------------
-struct NetParams {
-  const float* wpack;
-  float scale;
-  float k_inv_ln2;   // ln2 / k   (LogAndSign: log(.)/k == log2(.) * ln2/k)
-  float exp_k;       // fp32(e^k)
-  float beta1, beta2, omb1, omb2;   // fp32(beta), fp32(1 - beta)
-  int tanh_output;
-};
-
-struct ProbParams {
-  int kind, B_local, D, M;
-  int w_shared;      // W is one [M, D] matrix for every problem
-  int hvp;           // Hessian-vector mode (l2o_problem_hvp): the residual is W xs (no y), no separable terms
-  float inv_bg;      // 1 / B_global
-  float l1, alpha;
-  float twopi;       // 2*pi (rastrigin) or 2*3.1415926 (square_cos, DM/problems.py:989)
-  const float* W;
-  const float* y;
-  const float* C;
-  const float* x_scale;
-};
-
-// ---------------------------------------------------------------------------
-// K1: step-granular optimizer step on a gradient panel (state in HBM).
-// One wave per 16-coordinate tile, grid-stride over tiles; weights live in VGPRs.
-// HBM traffic per coordinate: 320 B state read + 320 B write + g + x r/w.
-// ---------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
-// s_waitcnt vmcnt(n) for a run-time n from the small set the step kernel needs
-__device__ __forceinline__ void wait_vmcnt_le(int n) {
-#define L2O_VMCASE(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-  switch (n) {
-    L2O_VMCASE(0) L2O_VMCASE(5) L2O_VMCASE(7) L2O_VMCASE(9) L2O_VMCASE(10) L2O_VMCASE(12) L2O_VMCASE(14)
-    L2O_VMCASE(15) L2O_VMCASE(17) L2O_VMCASE(18) L2O_VMCASE(19) L2O_VMCASE(22) L2O_VMCASE(23) L2O_VMCASE(24)
-    L2O_VMCASE(28) L2O_VMCASE(29) L2O_VMCASE(33)
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-#undef L2O_VMCASE
-}
-
-constexpr int kStepRing = 4;       // LDS ring slots per wave
-constexpr int kStepAhead = 3;      // tiles in flight ahead of the one being computed
-
-// up to kMaxStepSegs (variable, state) panels updated by one launch of the same network
-constexpr int kMaxStepSegs = 8;
-struct StepSegs {
-  int n;
-  int tile_end[kMaxStepSegs];     // running tile count (exclusive end) per segment
-  int tpp[kMaxStepSegs], D[kMaxStepSegs];
-  const float* g[kMaxStepSegs];
-  float* m[kMaxStepSegs];
-  float* v[kMaxStepSegs];
-  float* st[kMaxStepSegs];
-  float* x[kMaxStepSegs];
-  float* st_out[kMaxStepSegs];    // where the new state / moments go (== st / m / v unless the caller records history)
-  float* m_out[kMaxStepSegs];
-  float* v_out[kMaxStepSegs];
-};
-
-template <int PRE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_cwlstm_step(
-    NetParams np, StepSegs sg, float om1, float om2) {
-  // One wave per SIMD (the bf16x3 weights take 180-240 registers), so memory latency is
-  // hidden by DEPTH instead of occupancy: a wave walks its tiles with the next three tiles'
-  // inputs in flight as LDS-DMA (global_load_lds: packed state 5 x dwordx4 per lane, and
-  // g / x / m / v one dword each -- no staging registers), consumed after a counted
-  // s_waitcnt.  VMEM operations retire in issue order, so "at most N outstanding" with
-  // N = (later prefetches) x (loads per prefetch) + (later tiles' state stores) guarantees
-  // that this tile has landed; the masked x / m / v stores only make the wait stricter.
-  constexpr int NL = PRE == L2O_PRE_FC_ELU ? 9 : 7;              // VMEM loads per prefetched tile
-  constexpr int kSlotF4 = 5 * 64 + 64;                           // float4 per slot: state + {g,x,m,v} rows
-  __shared__ float4 sbuf[4][kStepRing][kSlotF4];
-  __shared__ __attribute__((aligned(16))) float bias_s[bx::kBiasWords];   // the gate biases = accumulator inits
-  bx::stage_bias(bias_s, np.wpack, PRE, threadIdx.x, blockDim.x);       // (ordered by the __syncthreads() of the fragment staging)
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // scalar: the waits below branch on it
-  const int c = lane & 15, q = lane >> 4;
-  const int wave = blockIdx.x * (blockDim.x >> 6) + wv;
-  const int nwaves = gridDim.x * (blockDim.x >> 6);
-  const int ntiles = sg.tile_end[sg.n - 1];
-  // ---- the bf16x3 weight fragments (60 / 80 KB) reach the four waves through LDS: one DMA copy per
-  // workgroup instead of four L2 reads; the staging area is the (not yet used) prefetch ring
-  constexpr bool PK = bx::packed_default(PRE);
-  bx::NetWB<PRE, PK> w;
-  {
-    constexpr int kFrags = bx::nchunks(PRE) * kNT * bx::frags(PK);   // 1 KB each = one wave-wide dwordx4
-    static_assert(kFrags * 1024 <= (int)sizeof(sbuf), "staging area");
-    float4* stage = &sbuf[0][0][0];
-    const float* src = np.wpack + bx::frag_off(PRE, PK, 0, 0, 0) + lane * 4;
-#pragma unroll
-    for (int f = 0; f < (kFrags + 3) / 4; ++f) {
-      const int fr = 4 * f + wv;
-      if (fr < kFrags)
-        __builtin_amdgcn_global_load_lds((gbl_void*)(src + fr * bx::kFragWords), (lds_void*)(stage + fr * 64), 16, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-#pragma unroll
-    for (int ch = 0; ch < bx::NetWB<PRE, PK>::NCH; ++ch)
-#pragma unroll
-      for (int t = 0; t < kNT; ++t)
-#pragma unroll
-        for (int s3 = 0; s3 < bx::frags(PK); ++s3) {
-          const float4 v4 = stage[((ch * kNT + t) * bx::frags(PK) + s3) * 64 + lane];
-          w.a[ch][t][s3] = __builtin_bit_cast(bx::u32x4, v4);
-        }
-    __syncthreads();                                               // everyone holds its copy: the ring may be used
-#pragma unroll
-    for (int ch = 0; ch < bx::NetWB<PRE, PK>::NCH; ++ch)           // fragments -> AGPRs (MFMA reads them there)
-#pragma unroll
-      for (int t = 0; t < kNT; ++t)
-#pragma unroll
-        for (int s3 = 0; s3 < bx::frags(PK); ++s3) asm volatile("" : "+a"(w.a[ch][t][s3]));
-  }
-  if (wave >= ntiles) return;
-  const int ntl = (ntiles - wave + nwaves - 1) / nwaves;         // tiles of this wave
-  // global tile index -> segment (wave-uniform scalar work)
-  struct Loc { const float* g; float *m, *v, *st, *x, *st_out, *m_out, *v_out; int tile, tpp, D; };
-  Loc L0;                                                        // the common single-panel launch: fields read once
-  L0.tile = 0; L0.g = sg.g[0]; L0.m = sg.m[0]; L0.v = sg.v[0]; L0.st = sg.st[0]; L0.x = sg.x[0];
-  L0.st_out = sg.st_out[0]; L0.m_out = sg.m_out[0]; L0.v_out = sg.v_out[0];
-  L0.tpp = sg.tpp[0]; L0.D = sg.D[0];
-  const bool single = sg.n == 1;
-  auto locate = [&](int tile) {
-    Loc L = L0;
-    if (single) {
-      L.tile = tile;
-      return L;
-    }
-    int sidx = 0;
-    while (sidx + 1 < sg.n && tile >= sg.tile_end[sidx]) ++sidx;
-    L.tile = tile - (sidx ? sg.tile_end[sidx - 1] : 0);
-    L.g = sg.g[sidx]; L.m = sg.m[sidx]; L.v = sg.v[sidx]; L.st = sg.st[sidx]; L.x = sg.x[sidx];
-    L.st_out = sg.st_out[sidx]; L.m_out = sg.m_out[sidx]; L.v_out = sg.v_out[sidx];
-    L.tpp = sg.tpp[sidx]; L.D = sg.D[sidx];
-    return L;
-  };
-  bx::load_netw<PRE, false>(w, np.wpack, lane);                  // the small fp32 weights
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // weights landed: the VMEM queue is empty
-  bx::set_bias(w, bias_s, q);
-  // dead lanes (j >= D in the last tile of a problem) read the problem's last coordinate:
-  // branch-free loads, masked where they are used
-  auto prefetch = [&](int k, int kslot) {
-    const Loc L = locate(wave + k * nwaves);
-    const int tile = L.tile, tpp = L.tpp, D = L.D;
-    const float *g = L.g, *x = L.x, *mbuf = L.m, *vbuf = L.v, *st = L.st;
-    float4* slot = sbuf[wv][kslot % kStepRing];
-    const float* src = st + (size_t)tile * kStateFloatsPerTile + lane * 4;
-#pragma unroll
-    for (int jj = 0; jj < 5; ++jj)
-      __builtin_amdgcn_global_load_lds((gbl_void*)(src + jj * 256), (lds_void*)(slot + jj * 64), 16, 0, 0);
-    const int b_ = tile / tpp, tw_ = tile - b_ * tpp;
-    const size_t idx_ = (size_t)b_ * D + min(tw_ * kTile + c, D - 1);
-    float* aux = reinterpret_cast<float*>(slot + 5 * 64);
-    __builtin_amdgcn_global_load_lds((gbl_void*)(g + idx_), (lds_void*)(aux), 4, 0, 0);
-    __builtin_amdgcn_global_load_lds((gbl_void*)(x + idx_), (lds_void*)(aux + 64), 4, 0, 0);
-    if (PRE == L2O_PRE_FC_ELU) {
-      __builtin_amdgcn_global_load_lds((gbl_void*)(mbuf + idx_), (lds_void*)(aux + 128), 4, 0, 0);
-      __builtin_amdgcn_global_load_lds((gbl_void*)(vbuf + idx_), (lds_void*)(aux + 192), 4, 0, 0);
-    }
-  };
-  // unconditional prologue (a wave with fewer than three tiles re-fetches its last one): a
-  // static VMEM count keeps hipcc from draining the queue at the loop entry
-#pragma unroll
-  for (int k = 0; k < kStepAhead; ++k) prefetch(min(k, ntl - 1), k);
-  for (int k = 0; k < ntl; ++k) {
-    const Loc L = locate(wave + k * nwaves);
-    const int tile = L.tile, tpp = L.tpp, D = L.D;
-    float *x = L.x, *mbuf = L.m_out, *vbuf = L.v_out, *st = L.st_out;
-    const int b = tile / tpp, tw = tile - b * tpp;
-    const int j = tw * kTile + c;
-    const bool live = j < D;
-    const size_t idx = (size_t)b * D + j;
-#ifndef L2O_ABLATE_STEP_LOAD
-    wait_vmcnt_le(NL * min(kStepAhead - 1, ntl - 1 - k) + 5 * min(k, kStepAhead));
-#endif
-    // the slot is read with inline-asm ds_reads: hipcc cannot tell the ring slots apart and
-    // would drain the whole VMEM queue (vmcnt(0)) before an ordinary LDS read of sbuf
-    const unsigned slot_addr =
-        (unsigned)(size_t)(__attribute__((address_space(3))) char*)(&sbuf[wv][k % kStepRing][0]) + lane * 16;
-    const unsigned aux_addr = slot_addr - lane * 12 + 5 * 1024;
-    TileState s;
-    float gv, xv, m = 0.f, v = 0.f;
-    {
-      float4 v0, v1, v2, v3, v4;
-      if (PRE == L2O_PRE_FC_ELU)
-        asm volatile(
-            "ds_read_b128 %0, %9\n\tds_read_b128 %1, %9 offset:1024\n\tds_read_b128 %2, %9 offset:2048\n\t"
-            "ds_read_b128 %3, %9 offset:3072\n\tds_read_b128 %4, %9 offset:4096\n\t"
-            "ds_read_b32 %5, %10\n\tds_read_b32 %6, %10 offset:256\n\tds_read_b32 %7, %10 offset:512\n\t"
-            "ds_read_b32 %8, %10 offset:768\n\ts_waitcnt lgkmcnt(0)"
-            : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3), "=&v"(v4), "=&v"(gv), "=&v"(xv), "=&v"(m), "=&v"(v)
-            : "v"(slot_addr), "v"(aux_addr)
-            : "memory");
-      else
-        asm volatile(
-            "ds_read_b128 %0, %7\n\tds_read_b128 %1, %7 offset:1024\n\tds_read_b128 %2, %7 offset:2048\n\t"
-            "ds_read_b128 %3, %7 offset:3072\n\tds_read_b128 %4, %7 offset:4096\n\t"
-            "ds_read_b32 %5, %8\n\tds_read_b32 %6, %8 offset:256\n\ts_waitcnt lgkmcnt(0)"
-            : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3), "=&v"(v4), "=&v"(gv), "=&v"(xv)
-            : "v"(slot_addr), "v"(aux_addr)
-            : "memory");
-      // slot k is in registers now; slot (k+3)%4 = (k-1)%4 is free for the next prefetch
-      const float e[20] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y,
-                           v2.z, v2.w, v3.x, v3.y, v3.z, v3.w, v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-      for (int t = 0; t < kNT; ++t) { s.h1[t] = e[t]; s.c1[t] = e[5 + t]; s.h2[t] = e[10 + t]; s.c2[t] = e[15 + t]; }
-    }
-    if (!live) { gv = 0.0f; m = 0.0f; v = 0.0f; }
-#ifndef L2O_ABLATE_STEP_LOAD
-    if (k + kStepAhead < ntl) prefetch(k + kStepAhead, k + kStepAhead);
-#endif
-    float in0, in1;
-    if (PRE == L2O_PRE_FC_ELU) {
-      rnnprop_inputs(gv, m, v, np.beta1, np.beta2, np.omb1, np.omb2, om1, om2, in0, in1);
-      if (!live) { in0 = 0.0f; in1 = 0.0f; }
-      if (live && q == 0) { mbuf[idx] = m; vbuf[idx] = v; }
-    } else {
-      preprocess_grad<PRE>(gv, np.k_inv_ln2, np.exp_k, in0, in1);
-    }
-    float d = bx::tile_step<PRE>(w, s, in0, in1, q);
-    if (np.tanh_output) d = tanhf_(d);
-    d *= np.scale;
-    if (live && q == 0) x[idx] = xv + d;
-#ifndef L2O_ABLATE_STEP_STORE
-    store_tile_state(s, st + (size_t)tile * kStateFloatsPerTile, lane);
-#else
-    if (d == 1234.5f) store_tile_state(s, st + (size_t)tile * kStateFloatsPerTile, lane);
-#endif
+// the run-time preprocess kind as a template argument: f(std::integral_constant<int, L2O_PRE_...>{}), FC_ELU for every other value
+template <class F>
+static auto with_pre(int pre, F&& f) {
+  switch (pre) {
+    case L2O_PRE_IDENTITY: return f(std::integral_constant<int, L2O_PRE_IDENTITY>{});
+    case L2O_PRE_LOGSIGN: return f(std::integral_constant<int, L2O_PRE_LOGSIGN>{});
+    default: return f(std::integral_constant<int, L2O_PRE_FC_ELU>{});
   }
 }
-
-// layers == (): StandardDeepLSTM with no cores = Linear on the preprocessed gradient
-// (DM/networks.py:225-232 with an empty DeepRNN; used by the meta_test.py:50-69 KAT).
-// lw = {w0, w1, b}
-template <int PRE>
-__global__ void k_linear_step(NetParams np, const float* __restrict__ g, float* __restrict__ x, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float w0 = np.wpack[0], w1 = np.wpack[1], bl = np.wpack[2];
-  float in0, in1;
-  preprocess_grad<PRE>(g[i], np.k_inv_ln2, np.exp_k, in0, in1);
-  float d = __builtin_fmaf(in1, w1, in0 * w0) + bl;
-  if (np.tanh_output) d = tanhf_(d);
-  x[i] += d * np.scale;
-}
-
-// ---------------------------------------------------------------------------
-// K2: optimizee forward + gradient for arbitrary sizes (matrix streamed from HBM/L2).
-// One 256-thread workgroup per problem.
-//   pass 1  r = W xs - y      rows over waves, columns over lanes (coalesced), wave reduce
-//   pass 2  g = W^T r         columns over threads (coalesced), rows split over thread groups
-// ---------------------------------------------------------------------------
-constexpr int kFgThreads = 512;
-constexpr int kFgWaves = kFgThreads / 64;
-
-__device__ __forceinline__ float block_sum_fg(float v, float* red /* >= kFgWaves floats */) {
-  v = wave_sum64(v);
-  const int wv = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[wv] = v;
-  __syncthreads();
-  float s = red[0];
-#pragma unroll
-  for (int k = 1; k < kFgWaves; ++k) s += red[k];
-  return s;
-}
-
-// VEC = true: D % 4 == 0 and 16-byte aligned rows -> dwordx4 loads, 4 rows (r pass) /
-// 4 row-strided loads (g pass) in flight per lane; VEC = false: scalar fallback.
-template <bool VEC>
-__global__ __launch_bounds__(kFgThreads) void k_problem_fg(ProbParams pp, const float* __restrict__ x,
-                                                            float* __restrict__ f_part,
-                                                            float* __restrict__ gout) {
-  extern __shared__ float sm[];
-  const int D = pp.D, M = pp.M;
-  float* xs = sm;                       // [D4]  scaled x (padded to a multiple of 4)
-  const int D4 = (D + 3) & ~3;
-  float* rs = xs + D4;                  // [M]   residual
-  float* part = rs + ((M + 3) & ~3);    // [4 * kFgThreads] partial column sums
-  float* red = part + 4 * kFgThreads;   // [kFgWaves]
-  const int b = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const float* xb = x + (size_t)b * D;
-  const float* sb = pp.x_scale ? pp.x_scale + (size_t)b * D : nullptr;
-
-  float facc = 0.0f;   // per-thread contribution to f_b
-  for (int j = tid; j < D4; j += kFgThreads) {
-    float xv = 0.0f;
-    if (j < D) {
-      xv = xb[j] * (sb ? sb[j] : 1.0f);
-      if (pp.kind == L2O_PROB_SIMPLE) facc += xv * xv;
-      if (pp.kind == L2O_PROB_LASSO) facc += pp.l1 * __builtin_fabsf(xv);
-      if (pp.kind == L2O_PROB_RASTRIGIN || pp.kind == L2O_PROB_SQUARE_COS)
-        facc += pp.alpha - pp.alpha * pp.C[(size_t)b * D + j] * l2o::cos_f(pp.twopi * xv);
-    }
-    xs[j] = xv;
-  }
-  __syncthreads();
-
-  if (pp.kind != L2O_PROB_SIMPLE) {
-    const float* Wb = pp.W + (pp.w_shared ? (size_t)0 : (size_t)b * M * D);
-    const float* yb = pp.y + (size_t)b * M;
-    const float coef = (pp.kind == L2O_PROB_QUADRATIC || pp.kind == L2O_PROB_SQUARE_COS) ? 1.0f : 0.5f;
-    if (VEC) {
-      // ---- pass 1: r = W xs - y ; each wave takes 4 rows at a time -> 4 x (D/256) dwordx4 in flight
-      for (int i0 = wv * 4; i0 < M; i0 += kFgWaves * 4) {
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int j = lane * 4; j < D; j += 256) {
-          const float4 xv4 = *reinterpret_cast<const float4*>(xs + j);
-          float4 w4[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int i = i0 + k < M ? i0 + k : M - 1;       // clamp: result of a clamped row is discarded
-            w4[k] = *reinterpret_cast<const float4*>(Wb + (size_t)i * D + j);
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            acc[k] = __builtin_fmaf(w4[k].x, xv4.x, acc[k]);
-            acc[k] = __builtin_fmaf(w4[k].y, xv4.y, acc[k]);
-            acc[k] = __builtin_fmaf(w4[k].z, xv4.z, acc[k]);
-            acc[k] = __builtin_fmaf(w4[k].w, xv4.w, acc[k]);
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float a = wave_sum64(acc[k]);
-          if (lane == 0 && i0 + k < M) {
-            const float r = a - (pp.hvp ? 0.0f : yb[i0 + k]);
-            rs[i0 + k] = r;
-            facc += coef * r * r;
-          }
-        }
-      }
-    } else {
-      for (int i = wv; i < M; i += kFgWaves) {
-        const float* row = Wb + (size_t)i * D;
-        float acc = 0.0f;
-        for (int j = lane; j < D; j += 64) acc = __builtin_fmaf(row[j], xs[j], acc);
-        acc = wave_sum64(acc);
-        if (lane == 0) {
-          const float r = acc - (pp.hvp ? 0.0f : yb[i]);
-          rs[i] = r;
-          facc += coef * r * r;
-        }
-      }
-    }
-  }
-  const float fb = block_sum_fg(facc, red);   // contains a __syncthreads: rs is visible after it
-  if (tid == 0) f_part[b] = fb;
-  if (gout == nullptr) return;
-
-  float* gb = gout + (size_t)b * D;
-  if (pp.kind == L2O_PROB_SIMPLE) {
-    for (int j = tid; j < D; j += kFgThreads) gb[j] = 2.0f * xs[j] * pp.inv_bg * (sb ? sb[j] : 1.0f);
-    return;
-  }
-  const float* Wb = pp.W + (pp.w_shared ? (size_t)0 : (size_t)b * M * D);
-  const float cg = (pp.kind == L2O_PROB_QUADRATIC || pp.kind == L2O_PROB_SQUARE_COS) ? 2.0f : 1.0f;
-  auto finish = [&](int j, float s) {
-    float gj = cg * s;
-    const float xv = xs[j];
-    if (!pp.hvp) {
-      if (pp.kind == L2O_PROB_LASSO) gj += pp.l1 * (xv > 0.f ? 1.f : (xv < 0.f ? -1.f : 0.f));
-      if (pp.kind == L2O_PROB_RASTRIGIN || pp.kind == L2O_PROB_SQUARE_COS)
-        gj += pp.twopi * pp.alpha * pp.C[(size_t)b * D + j] * l2o::sin_f(pp.twopi * xv);
-    }
-    gb[j] = gj * pp.inv_bg * (sb ? sb[j] : 1.0f);
-  };
-  if (VEC) {
-    // ---- pass 2: g = W^T r ; a thread owns 4 adjacent columns, row groups are strided over
-    // RP thread groups; 4 dwordx4 loads in flight per thread
-    const int ncol4 = D >> 2;
-    const int CP4 = ncol4 >= kFgThreads ? kFgThreads : ((ncol4 + 63) & ~63);
-    const int RP = kFgThreads / CP4;
-    const int jc = tid % CP4, rp = tid / CP4;
-    for (int j0 = 0; j0 < ncol4; j0 += CP4) {
-      const int j4 = j0 + jc;
-      float4 a = {0.f, 0.f, 0.f, 0.f};
-      if (j4 < ncol4 && rp < RP) {
-        const float* col = Wb + 4 * (size_t)j4;
-        int i = rp;
-        for (; i + 3 * RP < M; i += 4 * RP) {
-          const float4 w0 = *reinterpret_cast<const float4*>(col + (size_t)i * D);
-          const float4 w1 = *reinterpret_cast<const float4*>(col + (size_t)(i + RP) * D);
-          const float4 w2 = *reinterpret_cast<const float4*>(col + (size_t)(i + 2 * RP) * D);
-          const float4 w3 = *reinterpret_cast<const float4*>(col + (size_t)(i + 3 * RP) * D);
-          const float r0 = rs[i], r1 = rs[i + RP], r2 = rs[i + 2 * RP], r3 = rs[i + 3 * RP];
-          a.x += (w0.x * r0 + w1.x * r1) + (w2.x * r2 + w3.x * r3);
-          a.y += (w0.y * r0 + w1.y * r1) + (w2.y * r2 + w3.y * r3);
-          a.z += (w0.z * r0 + w1.z * r1) + (w2.z * r2 + w3.z * r3);
-          a.w += (w0.w * r0 + w1.w * r1) + (w2.w * r2 + w3.w * r3);
-        }
-        for (; i < M; i += RP) {
-          const float4 w0 = *reinterpret_cast<const float4*>(col + (size_t)i * D);
-          const float r0 = rs[i];
-          a.x = __builtin_fmaf(w0.x, r0, a.x); a.y = __builtin_fmaf(w0.y, r0, a.y);
-          a.z = __builtin_fmaf(w0.z, r0, a.z); a.w = __builtin_fmaf(w0.w, r0, a.w);
-        }
-      }
-      __syncthreads();
-      *reinterpret_cast<float4*>(part + 4 * tid) = a;
-      __syncthreads();
-      if (rp == 0 && j4 < ncol4) {
-        float4 s4 = *reinterpret_cast<const float4*>(part + 4 * jc);
-        for (int p = 1; p < RP; ++p) {
-          const float4 t4 = *reinterpret_cast<const float4*>(part + 4 * (p * CP4 + jc));
-          s4.x += t4.x; s4.y += t4.y; s4.z += t4.z; s4.w += t4.w;
-        }
-        finish(4 * j4, s4.x); finish(4 * j4 + 1, s4.y); finish(4 * j4 + 2, s4.z); finish(4 * j4 + 3, s4.w);
-      }
-    }
-  } else {
-    const int CP = D >= kFgThreads ? kFgThreads : ((D + 63) & ~63);
-    const int RP = kFgThreads / CP;
-    const int jc = tid % CP, rp = tid / CP;
-    for (int j0 = 0; j0 < D; j0 += CP) {
-      const int j = j0 + jc;
-      float a0 = 0.f, a1 = 0.f;
-      if (j < D && rp < RP) {
-        int i = rp;
-        for (; i + RP < M; i += 2 * RP) {
-          a0 = __builtin_fmaf(Wb[(size_t)i * D + j], rs[i], a0);
-          a1 = __builtin_fmaf(Wb[(size_t)(i + RP) * D + j], rs[i + RP], a1);
-        }
-        for (; i < M; i += RP) a0 = __builtin_fmaf(Wb[(size_t)i * D + j], rs[i], a0);
-      }
-      __syncthreads();
-      part[tid] = a0 + a1;
-      __syncthreads();
-      if (rp == 0 && j < D) {
-        float s = part[jc];
-        for (int p = 1; p < RP; ++p) s += part[p * CP + jc];
-        finish(j, s);
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// K2b: the same forward + gradient with the matrix read ONCE.  A wave keeps the rows it visits in
-// registers between their two uses: lane l holds the row's columns 4 (64 v + l) .. + 3 (v < NV: coalesced
-// 1 KB pieces), r_i = dot(row, xs) - y_i is a wave sum that every lane receives, and the same registers
-// then feed g += r_i * row.  Eight waves walk the rows in groups of four (4 NV dwordx4 loads in flight per
-// lane); their partial gradients are added in a fixed order through LDS.  Halves the HBM traffic of the
-// step-granular path's matrix-bound optimizees (config 3: 256 x 512 per problem, 128 MiB per batch).
-// D % 4 == 0, D <= 256 NV.
-// ---------------------------------------------------------------------------
-template <int NV>
-__global__ __launch_bounds__(kFgThreads) void k_problem_fg1(ProbParams pp, const float* __restrict__ x,
-                                                             float* __restrict__ f_part,
-                                                             float* __restrict__ gout) {
-  extern __shared__ float sm[];
-  const int D = pp.D, M = pp.M;
-  float* part = sm;                     // [kFgWaves][D] partial gradients
-  float* red = part + kFgWaves * D;     // [kFgWaves]
-  const int b = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const float* xb = x + (size_t)b * D;
-  const float* sb = pp.x_scale ? pp.x_scale + (size_t)b * D : nullptr;
-  const float* Wb = pp.W + (pp.w_shared ? (size_t)0 : (size_t)b * M * D);
-  const l2o_cfp yb = (l2o_cfp)(pp.y + (size_t)b * M);
-  const bool want_g = gout != nullptr;
-  const float coef = (pp.kind == L2O_PROB_QUADRATIC || pp.kind == L2O_PROB_SQUARE_COS) ? 1.0f : 0.5f;
-
-  float4 xv[NV], sv[NV], ga[NV];
-  float facc = 0.0f;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    const int j = 4 * (64 * v + lane);
-    const float4 zero = {0.f, 0.f, 0.f, 0.f}, one = {1.f, 1.f, 1.f, 1.f};
-    xv[v] = zero; sv[v] = one; ga[v] = zero;
-    if (j < D) {
-      xv[v] = *reinterpret_cast<const float4*>(xb + j);
-      if (sb) sv[v] = *reinterpret_cast<const float4*>(sb + j);
-      xv[v].x *= sv[v].x; xv[v].y *= sv[v].y; xv[v].z *= sv[v].z; xv[v].w *= sv[v].w;
-      if (wv == 0) {                                        // the separable terms of f: once per problem
-        const float xe[4] = {xv[v].x, xv[v].y, xv[v].z, xv[v].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (pp.kind == L2O_PROB_LASSO) facc += pp.l1 * __builtin_fabsf(xe[e]);
-          if (pp.kind == L2O_PROB_RASTRIGIN || pp.kind == L2O_PROB_SQUARE_COS)
-            facc += pp.alpha - pp.alpha * pp.C[(size_t)b * D + j + e] * l2o::cos_f(pp.twopi * xe[e]);
-        }
-      }
-    }
-  }
-  // software pipeline: the next group of four rows is requested before the current one is reduced (one wave
-  // has 4 NV dwordx4 per lane in flight while it computes; without it every group pays a full memory latency)
-  auto load4 = [&](int i0, float4 (&w4)[4][NV]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int i = i0 + k < M ? i0 + k : M - 1;             // clamped rows contribute r = 0 below
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        const int j = 4 * (64 * v + lane);
-        const float4 zero = {0.f, 0.f, 0.f, 0.f};
-        w4[k][v] = j < D ? *reinterpret_cast<const float4*>(Wb + (size_t)i * D + j) : zero;
-      }
-    }
-  };
-  auto use4 = [&](int i0, const float4 (&w4)[4][NV]) {
-    float acc[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float a = 0.0f;
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        a = __builtin_fmaf(w4[k][v].x, xv[v].x, a);
-        a = __builtin_fmaf(w4[k][v].y, xv[v].y, a);
-        a = __builtin_fmaf(w4[k][v].z, xv[v].z, a);
-        a = __builtin_fmaf(w4[k][v].w, xv[v].w, a);
-      }
-      acc[k] = a;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const bool ok = i0 + k < M;
-      const float r = ok ? wave_sum64(acc[k]) - (pp.hvp ? 0.0f : yb[ok ? i0 + k : 0]) : 0.0f;
-      if (lane == 0) facc += coef * r * r;
-      if (want_g) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          ga[v].x = __builtin_fmaf(r, w4[k][v].x, ga[v].x);
-          ga[v].y = __builtin_fmaf(r, w4[k][v].y, ga[v].y);
-          ga[v].z = __builtin_fmaf(r, w4[k][v].z, ga[v].z);
-          ga[v].w = __builtin_fmaf(r, w4[k][v].w, ga[v].w);
-        }
-      }
-    }
-  };
-  {
-    constexpr int STEP = kFgWaves * 4;
-    float4 wa[4][NV], wb[4][NV];
-    int i0 = wv * 4;
-    if (i0 < M) load4(i0, wa);
-    for (; i0 < M; i0 += 2 * STEP) {
-      if (i0 + STEP < M) load4(i0 + STEP, wb);
-      use4(i0, wa);
-      if (i0 + STEP < M) {
-        if (i0 + 2 * STEP < M) load4(i0 + 2 * STEP, wa);
-        use4(i0 + STEP, wb);
-      }
-    }
-  }
-  if (want_g) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const int j = 4 * (64 * v + lane);
-      if (j < D) *reinterpret_cast<float4*>(part + wv * D + j) = ga[v];
-    }
-  }
-  const float fb = block_sum_fg(facc, red);   // contains __syncthreads: the partial gradients are visible after it
-  if (tid == 0) f_part[b] = fb;
-  if (!want_g) return;
-  float* gb = gout + (size_t)b * D;
-  const float cg = (pp.kind == L2O_PROB_QUADRATIC || pp.kind == L2O_PROB_SQUARE_COS) ? 2.0f : 1.0f;
-  for (int j = tid; j < D; j += kFgThreads) {
-    float s = part[j];
-#pragma unroll
-    for (int w = 1; w < kFgWaves; ++w) s += part[w * D + j];
-    const float sc = sb ? sb[j] : 1.0f;
-    const float xj = xb[j] * sc;
-    float gj = cg * s;
-    if (!pp.hvp) {
-      if (pp.kind == L2O_PROB_LASSO) gj += pp.l1 * (xj > 0.f ? 1.f : (xj < 0.f ? -1.f : 0.f));
-      if (pp.kind == L2O_PROB_RASTRIGIN || pp.kind == L2O_PROB_SQUARE_COS)
-        gj += pp.twopi * pp.alpha * pp.C[(size_t)b * D + j] * l2o::sin_f(pp.twopi * xj);
-    }
-    gb[j] = gj * pp.inv_bg * sc;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// K3: the fused persistent unroll.  One workgroup per problem, one wave per
-// 16-coordinate tile (<= 8 waves), T steps in ONE launch.
-//   LDS  : the problem matrix TWICE -- W_b row-major and W_b^T row-major, row stride
-//          S = SQ + 16 floats (S/4 == 4 or 12 mod 16 -> ds_read_b128 of a (row, 16-byte
-//          column chunk) per lane is bank-conflict free) -- plus y, x*s and the residual r
-//   VGPR : optimizer weights (MFMA A fragments), LSTM state, x, m, v
-//   HBM  : W_b read once per launch; x/state/m/v read+written once; one float per
-//          (step, problem)
-// Per step and wave (lane l also plays the GEMV role (row = 16*wave + l/4, chunk = l%4)):
-//   xs <- x*s ; barrier
-//   r  = W xs - y           || the 25 layer-2 MFMAs fed by the previous h2
-//   f_b partial ; barrier
-//   g  = W^T r (own 16 coordinates) || the 25 layer-1 MFMAs fed by the previous h1
-//   preprocess(g) -> input MFMAs -> gates -> layer-2 MFMAs -> gates -> Linear -> x += delta
-// i.e. 50 of the 80 MFMAs of a step depend only on the previous step's state and are
-// issued interleaved with the GEMV's LDS reads and FMAs (separate pipes).
-// ---------------------------------------------------------------------------
-struct UnrollArgs {
-  NetParams np;
-  ProbParams pp;
-  float* x;
-  float* st;
-  float* m;
-  float* v;
-  float* fx_part;
-  int T;
-  float p1_hi, p1_lo, p2_hi, p2_lo;   // beta^step0 as float-float
-  // optional per-step history for the meta-gradient (l2o_unroll_record): packed state BEFORE
-  // step t, the gradient fed to the network at step t, RNNProp moments AFTER step t, and the
-  // gradient at x_T.  All NULL for a plain unroll.
-  float *hist_st, *hist_g, *hist_m, *hist_v, *hist_gfinal;
-  // restart (l2o_unroll_reduce): read the iterate from x_in (x receives x_T) / start from the zero LSTM state and
-  // zero moments instead of reading st, m, v -- `reset` + the first unroll in one launch, no memset / copy pass
-  const float* x_in;
-  int zero_state;
-  long long* ticks;   // where k_unroll_lds leaves the step-loop cycle count of problem 0 (PairWs::ticks), or NULL
-};
-
-#ifdef L2O_ABLATE_BARRIER
-#define L2O_SYNC() ((void)0)
-#else
-#define L2O_SYNC() __syncthreads()
-#endif
-// a.b accumulated into FOUR independent partial sums (x, y, z, w lanes of `acc`): the
-// chunk loop then carries 4 short dependency chains instead of one long one
-__device__ __forceinline__ void dot4(const float4 a, const float4 b, float4& acc) {
-#ifdef L2O_ABLATE_GEMV
-  acc.x += a.x;
-  return;
-#endif
-  acc.x = __builtin_fmaf(a.x, b.x, acc.x);
-  acc.y = __builtin_fmaf(a.y, b.y, acc.y);
-  acc.z = __builtin_fmaf(a.z, b.z, acc.z);
-  acc.w = __builtin_fmaf(a.w, b.w, acc.w);
-}
-__device__ __forceinline__ float hsum4(const float4 a) { return (a.x + a.y) + (a.z + a.w); }
-
-template <int PRE, int KIND, int CH, bool HIST, bool EXACT = false>
-__global__ __launch_bounds__(CH <= 4 ? 256 : 512) void k_unroll(UnrollArgs a) {
-  // CH <= 4 <=> at most 4 waves per workgroup = one wave per SIMD: the bf16x3 gate GEMM with
-  // its weights in VGPR + AGPR; CH == 8 (5..8 waves) keeps the fp32 MFMA form (as does EXACT: L2O_OPT_EXACT_GATES)
-  using Core = LstmCore<PRE, (CH <= 4) && !EXACT>;
-  constexpr int SQ = 16 * CH;      // padded square size of the LDS-resident matrix
-  constexpr int S = SQ + 16;       // row stride (floats)
-  extern __shared__ float sm[];
-  const ProbParams& pp = a.pp;
-  const int D = pp.D, M = pp.M;
-  float* Ws = sm;                  // [SQ][S]  W   (rows i, columns j)
-  float* WTs = Ws + SQ * S;        // [SQ][S]  W^T (rows j, columns i)
-  float* xs = WTs + SQ * S;        // [SQ]
-  float* rs = xs + SQ;             // [SQ]
-  float* ys = rs + SQ;             // [SQ]
-  float* fpart = ys + SQ;          // [8]
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
-  const int c = lane & 15, q = lane >> 4;      // LSTM role: coordinate c, unit group q
-  const int grow = wv * kTile + (lane >> 2);   // GEMV role: matrix row (r pass) / coordinate (g pass)
-  const int gq = lane & 3;                     //            16-byte column chunk inside a 64-byte group
-  const int b = blockIdx.x;
-
-  // ---- stage the problem into LDS (zero padded), both orientations ---------
-  const float* Wb = pp.W + (pp.w_shared ? (size_t)0 : (size_t)b * M * D);
-  for (int i = tid; i < 2 * SQ * S + 3 * SQ; i += blockDim.x) sm[i] = 0.0f;
-  __syncthreads();
-  for (int e = tid; e < M * D; e += blockDim.x) {
-    const int i = e / D, j = e - i * D;
-    const float v = Wb[e];
-    Ws[i * S + j] = v;
-    WTs[j * S + i] = v;
-  }
-  for (int i = tid; i < M; i += blockDim.x) ys[i] = pp.y[(size_t)b * M + i];
-
-  // ---- per-lane persistent registers -------------------------------------
-  Core core;
-  core.load(a.np.wpack, lane);
-  core.pin();   // (bf16x3 forms: fragments -> AGPRs; without it 125-133 v_accvgpr_read per step)
-  __shared__ __attribute__((aligned(16))) float bias_s[Core::kBiasFloats];   // the gate biases = accumulator inits
-  core.stage_bias(bias_s, a.np.wpack, tid, blockDim.x, q);
-  const int j = wv * kTile + c;             // this lane's coordinate (LSTM role)
-  const bool live = j < D;
-  const size_t idx = (size_t)b * D + j;
-  const int tile = b * nw + wv;
-  TileState s;
-  float* st_tile = a.st + (size_t)tile * kStateFloatsPerTile;
-  if (a.zero_state) {
-#pragma unroll
-    for (int t5 = 0; t5 < kNT; ++t5) s.h1[t5] = s.c1[t5] = s.h2[t5] = s.c2[t5] = 0.0f;
-  } else {
-    load_tile_state(s, st_tile, lane);
-  }
-  float xv = live ? (a.x_in ? a.x_in : a.x)[idx] : 0.0f;
-  const float sc = (live && pp.x_scale) ? pp.x_scale[idx] : 1.0f;
-  float cj = 0.0f;
-  constexpr bool kCos = KIND == L2O_PROB_RASTRIGIN || KIND == L2O_PROB_SQUARE_COS;
-  if (kCos) cj = live ? pp.C[idx] : 0.0f;
-  float mv = 0.0f, vv = 0.0f;
-  if (PRE == L2O_PRE_FC_ELU && !a.zero_state) { mv = live ? a.m[idx] : 0.0f; vv = live ? a.v[idx] : 0.0f; }
-  float p1h = a.p1_hi, p1l = a.p1_lo, p2h = a.p2_hi, p2l = a.p2_lo;
-  constexpr bool kSq = KIND == L2O_PROB_QUADRATIC || KIND == L2O_PROB_SQUARE_COS;
-  const float coef = kSq ? 1.0f : 0.5f;
-  const float cg = (KIND == L2O_PROB_QUADRATIC ? 2.0f : 1.0f) * pp.inv_bg;   // x2 folded in (exact)
-  const float kTwoPi = pp.twopi;
-  const float* wrow = Ws + grow * S + 4 * gq;
-  const float* wtrow = WTs + grow * S + 4 * gq;
-  const float* xsq = xs + 4 * gq;
-  const float* rsq = rs + 4 * gq;
-  const int perm_src = (4 * c) << 2;        // byte index of lane 4*c for ds_bpermute
-
-  // software pipeline of the matrix work: acc1 always holds bias + (h1 of the previous step)
-  // part of layer 1; it is produced at the END of the previous step (overlapping that step's
-  // layer-2 gate math), here for step 0.
-  f32x4 acc1[kNT], acc2[kNT];
-  core.init(s, q);
-  __syncthreads();                                           // the bias table is staged
-  core.preload(acc1, acc2);
-  core.template issue_l1_prev<0, Core::kTotal>(s, acc1);
-
-  const size_t hist_n = (size_t)pp.B_local * D;
-  for (int t = 0;; ++t) {
-    const float xsv = xv * sc;
-    if (live && q == 0) xs[j] = xsv;
-    if (HIST && t < a.T)
-      store_tile_state(s, a.hist_st + ((size_t)t * pp.B_local * nw + tile) * kStateFloatsPerTile, lane);
-    L2O_SYNC();                                             // B1: xs complete
-    // ---- r = W xs - y  ||  first 12 layer-2 MFMAs of the previous h2 -----------
-    float4 racc = {0.f, 0.f, 0.f, 0.f};
-    static_for<0, CH>([&](auto mc) {
-      constexpr int m = decltype(mc)::value;
-      const float4 wv4 = *reinterpret_cast<const float4*>(wrow + 16 * m);
-      const float4 xv4 = *reinterpret_cast<const float4*>(xsq + 16 * m);
-      core.template issue_l2_prev<(Core::kHalf * m) / CH, (Core::kHalf * (m + 1)) / CH>(s, acc2);
-      dot4(wv4, xv4, racc);
-    });
-    const float r = quad_sum(hsum4(racc)) - ys[grow];
-    float contrib = 0.0f;
-    if (gq == 0) {
-      rs[grow] = r;                       // rows >= M: W row and y are zero -> r == 0
-      contrib = coef * r * r;
-    }
-    if (live && q == 0) {
-      if (KIND == L2O_PROB_LASSO) contrib += pp.l1 * __builtin_fabsf(xsv);
-      if (kCos) contrib += pp.alpha - pp.alpha * cj * l2o::cos_f(kTwoPi * xsv);
-    }
-    contrib = wave_sum64(contrib);
-    if (lane == 0) fpart[wv] = contrib;
-    L2O_SYNC();                                             // B2: rs, fpart complete
-    if (tid == 0) {
-      float f = fpart[0];
-      for (int k = 1; k < nw; ++k) f += fpart[k];
-      a.fx_part[(size_t)t * pp.B_local + b] = f;
-    }
-    if (t == a.T && !HIST) break;
-
-    // ---- g = W^T r for this wave's 16 coordinates  ||  the other 13 of those MFMAs ----
-    float4 gacc4 = {0.f, 0.f, 0.f, 0.f};
-    static_for<0, CH>([&](auto mc) {
-      constexpr int m = decltype(mc)::value;
-      const float4 wt4 = *reinterpret_cast<const float4*>(wtrow + 16 * m);
-      const float4 rv4 = *reinterpret_cast<const float4*>(rsq + 16 * m);
-      core.template issue_l2_prev<Core::kHalf + ((Core::kTotal - Core::kHalf) * m) / CH,
-                                  Core::kHalf + ((Core::kTotal - Core::kHalf) * (m + 1)) / CH>(s, acc2);
-      dot4(wt4, rv4, gacc4);
-    });
-    const float gacc = quad_sum(hsum4(gacc4));                 // lanes 4k..4k+3 hold g of coordinate 16*wv + k
-    float gv = __int_as_float(__builtin_amdgcn_ds_bpermute(perm_src, __float_as_int(gacc)));
-    if (KIND == L2O_PROB_SQUARE_COS) gv *= 2.0f;            // only the ||wx-y||^2 part carries the 2
-    if (KIND == L2O_PROB_LASSO) gv += pp.l1 * (xsv > 0.f ? 1.f : (xsv < 0.f ? -1.f : 0.f));
-    if (kCos) gv += kTwoPi * pp.alpha * cj * l2o::sin_f(kTwoPi * xsv);
-    gv = live ? gv * cg * sc : 0.0f;
-    if (HIST && live && q == 0) {
-      if (t < a.T) a.hist_g[(size_t)t * hist_n + idx] = gv;
-      else a.hist_gfinal[idx] = gv;
-    }
-    if (HIST && t == a.T) break;                            // (history mode: the gradient at x_T was still needed)
-
-    // ---- optimizer network ----------------------------------------------------
-    float in0, in1;
-    if (PRE == L2O_PRE_FC_ELU) {
-      // beta^k as a float-float running product (k = step0 + t)
-      rnnprop_inputs(gv, mv, vv, a.np.beta1, a.np.beta2, a.np.omb1, a.np.omb2, 1.0f - p1h, 1.0f - p2h, in0, in1);
-      if (HIST && live && q == 0) { a.hist_m[(size_t)t * hist_n + idx] = mv; a.hist_v[(size_t)t * hist_n + idx] = vv; }
-      if (!live) { in0 = 0.0f; in1 = 0.0f; }
-      {
-        float hi = p1h * a.np.beta1, er = __builtin_fmaf(p1h, a.np.beta1, -hi);
-        float lo = __builtin_fmaf(p1l, a.np.beta1, er), sum = hi + lo;
-        p1l = lo - (sum - hi); p1h = sum;
-        hi = p2h * a.np.beta2; er = __builtin_fmaf(p2h, a.np.beta2, -hi);
-        lo = __builtin_fmaf(p2l, a.np.beta2, er); sum = hi + lo;
-        p2l = lo - (sum - hi); p2h = sum;
-      }
-    } else {
-      preprocess_grad<PRE>(gv, a.np.k_inv_ln2, a.np.exp_k, in0, in1);
-    }
-    PhaseClock pc;
-    float d = core.template finish<true>(s, acc1, acc2, in0, in1, q, pc);
-    if (a.np.tanh_output) d = tanhf_(d);
-    xv = __builtin_fmaf(d, a.np.scale, xv);
-  }
-
-  if (live && q == 0) {
-    a.x[idx] = xv;
-    if (PRE == L2O_PRE_FC_ELU) { a.m[idx] = mv; a.v[idx] = vv; }
-  }
-  store_tile_state(s, st_tile, lane);
-}
-
-#include "l2o_unroll_pair.h"
-#include "l2o_unroll_lds.h"
-
-#include "l2o_unroll_cu.h"
-#include "l2o_unroll_cu8.h"
-
-#include "l2o_ilp_kernels.h"   // the plain two-CU / eight-wave unrolls: code in l2o_kernels_ilp.hip, `extern template` here
-#ifndef L2O_TU_ILP             // (everything below belongs to the main translation unit only)
-
-#include "l2o_mlp.h"
-
-#include "l2o_mlp_unroll.h"
-#include "l2o_mlp_xcd.h"
-#include "l2o_mlp_deep.h"
-#include "l2o_mlp_hvp.h"
-#include "l2o_mnist_conv.h"
-#include "l2o_cifar_conv.h"
-#include "l2o_lenet.h"
-#include "l2o_confocal.h"
-#include "l2o_confocal_unroll.h"
-
-#include "l2o_generic.h"
-
-#include "l2o_atb.h"
-
-#include "l2o_bwd.h"
-
-#include "l2o_bwd_mfma.h"
-#include "l2o_vecops.h"
-
-// ---------------------------------------------------------------------------
-// small utility kernels
-// ---------------------------------------------------------------------------
-// reference layout [B*D, 20] x 4  <->  packed tile layout
-__global__ void k_state_repack(float* __restrict__ h1, float* __restrict__ c1, float* __restrict__ h2,
-                               float* __restrict__ c2, float* __restrict__ st, int B, int D, int tpp,
-                               int to_packed) {
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t total = (size_t)B * tpp * 64 * 20;
-  if (gid >= total) return;
-  const int e = gid % 20;                 // element of the lane: 4*jv + wv
-  const int lane = (gid / 20) % 64;
-  const size_t tile = gid / (20 * 64);
-  const int b = tile / tpp, tw = tile % tpp;
-  const int c = lane & 15, q = lane >> 4;
-  const int j = tw * kTile + c;
-  const int arr = e / 5, t = e % 5, u = 4 * t + q;
-  const size_t paddr = tile * kStateFloatsPerTile + ((size_t)(e >> 2) * 64 + lane) * 4 + (e & 3);
-  float* ref = arr == 0 ? h1 : (arr == 1 ? c1 : (arr == 2 ? h2 : c2));
-  if (j < D) {
-    const size_t raddr = ((size_t)b * D + j) * kH + u;
-    if (to_packed) st[paddr] = ref[raddr];
-    else ref[raddr] = st[paddr];
-  } else if (to_packed) {
-    st[paddr] = 0.0f;
-  }
-}
-
-// fx[t] = (sum_b fx_part[t][b]) / B_global, fixed order: each wave sums a strided slice
-// sequentially, then a fixed butterfly.
-__global__ void k_reduce_fx(const float* __restrict__ fx_part, int T1, int B_local, float inv_bg,
-                            float* __restrict__ fx) {
-  const int t = blockIdx.x;
-  const int lane = threadIdx.x;   // 64 threads
-  float acc = 0.0f;
-  for (int b = lane; b < B_local; b += 64) acc += fx_part[(size_t)t * B_local + b];
-  acc = wave_sum64(acc);
-  if (lane == 0) fx[t] = acc * inv_bg;
+// a launch with `lds` bytes of dynamic LDS: raise the kernel's limit (every time: no host-side state), launch, check
+template <class K, class... A>
+static int launch(K fn, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(fn, grid, block, lds, s, args...);
+  HIP_TRY(hipGetLastError());
+  return L2O_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -1084,21 +250,6 @@ static int coresident_cus(hipStream_t s) {
   return n;
 }
 
-// The probe: one workgroup per CU (100 KB of LDS each), every workgroup counts itself, waits a FIXED ~30 us (the
-// dispatch of a grid this size takes a few) and records how many had arrived by then; the minimum over the workgroups
-// is the number that were resident together (a second wave of workgroups sees the full count, the first wave its own
-// size).  Bounded: no workgroup waits for another.
-__global__ __launch_bounds__(256) void k_coresident_probe(unsigned* ctr, unsigned* min_seen) {
-  extern __shared__ float probe_lds[];
-  if (threadIdx.x == 0) {
-    probe_lds[0] = 1.0f;
-    atomicAdd(ctr, 1u);
-    for (int i = 0; i < 8; ++i) __builtin_amdgcn_s_sleep(127);        // 8 x 127 x 64 clocks ~ 28 us
-    const unsigned v = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    atomicMin(min_seen, v);
-  }
-}
-
 // Split every problem over two workgroups when that still leaves all of them co-resident.
 // Problems per launch of the two-CU form, 0 = not this form.  Every problem of a launch must be co-resident with its
 // partner: at most #CU / 2 per launch.  A larger batch shard runs as consecutive launches of equal chunks (a multiple
@@ -1152,9 +303,8 @@ static int launch_unroll_ch(const UnrollArgs& a, const UnrollGeom& g, hipStream_
       al.ticks = workspace ? &reinterpret_cast<PairWs*>(workspace)->ticks : nullptr;
       void (*fl)(UnrollArgs) = hist ? k_unroll_lds<PRE, KIND, true> : k_unroll_lds<PRE, KIND, false>;
       const size_t lds = sizeof(float) * ((size_t)LstmCoreLds<PRE>::kFragWords + 2 * 128 + 8);
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(fl, dim3(a.pp.B_local), dim3(64 * g.nw), lds, s, al);
-      HIP_TRY(hipGetLastError());
+      const int rc = launch(fl, dim3(a.pp.B_local), dim3(64 * g.nw), lds, s, al);
+      if (rc) return rc;
       note_form(L2O_FORM_UNROLL_LDS);
       note_variant(0, hist, false, false, 0, 0);
       return L2O_OK;
@@ -1221,10 +371,8 @@ static int launch_unroll_ch(const UnrollArgs& a, const UnrollGeom& g, hipStream_
     case 4: fn = hist ? k_unroll<PRE, KIND, 4, true> : (exact1 ? k_unroll<PRE, KIND, 4, false, true> : k_unroll<PRE, KIND, 4, false>); break;
     default: fn = hist ? k_unroll<PRE, KIND, 8, true> : k_unroll<PRE, KIND, 8, false>; break;
   }
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)g.lds));
-  hipLaunchKernelGGL(fn, dim3(a.pp.B_local), dim3(64 * g.nw), g.lds, s, a);
-  HIP_TRY(hipGetLastError());
+  const int rc = launch(fn, dim3(a.pp.B_local), dim3(64 * g.nw), g.lds, s, a);
+  if (rc) return rc;
   note_form(L2O_FORM_UNROLL);
   note_variant(g.CH, hist, exact1 && g.CH <= 4, false, 0, 0);     // (CH == 8 has no EXACT instantiation: fp32 MFMA always)
   return L2O_OK;
@@ -1258,12 +406,9 @@ static int launch_unroll_cu8(const UnrollArgs& a, hipStream_t s) {
   const bool hist = a.hist_st != nullptr;
   void (*fn)(UnrollArgs) = a.pp.D <= 256 ? (hist ? k_unroll_cu8<PRE, 1, KR, true> : k_unroll_cu8<PRE, 1, KR, false>)
                                          : (hist ? k_unroll_cu8<PRE, 2, KR, true> : k_unroll_cu8<PRE, 2, KR, false>);
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
-  hipLaunchKernelGGL(fn, dim3(a.pp.B_local), dim3(kCu8Threads), L.lds, s, a);
   note_form(L2O_FORM_UNROLL_CU8);
   note_variant(0, hist, false, false, KR, a.pp.D <= 256 ? 1 : 2);
-  HIP_TRY(hipGetLastError());
-  return L2O_OK;
+  return launch(fn, dim3(a.pp.B_local), dim3(kCu8Threads), L.lds, s, a);
 }
 template <int PRE>
 static int launch_unroll_cu(const UnrollArgs& a_in, hipStream_t s) {
@@ -1289,33 +434,23 @@ static int launch_unroll_cu(const UnrollArgs& a_in, hipStream_t s) {
   const bool hist = a.hist_st != nullptr;
   void (*fn)(UnrollArgs) = a.pp.D <= 256 ? (hist ? k_unroll_cu<PRE, 1, true> : k_unroll_cu<PRE, 1, false>)
                                          : (hist ? k_unroll_cu<PRE, 2, true> : k_unroll_cu<PRE, 2, false>);
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)L.lds));
-  hipLaunchKernelGGL(fn, dim3(a.pp.B_local), dim3(kCuThreads), L.lds, s, a);
   note_form(L2O_FORM_UNROLL_CU);
   note_variant(0, hist, false, false, 0, a.pp.D <= 256 ? 1 : 2);
-  HIP_TRY(hipGetLastError());
-  return L2O_OK;
+  return launch(fn, dim3(a.pp.B_local), dim3(kCuThreads), L.lds, s, a);
 }
 
 // the fused unroll of the confocal optimizee (csrc/l2o_confocal_unroll.h): one workgroup per batch row
 template <int PRE>
 static int launch_confocal_unroll(const CfUnrollArgs& a, bool hist, size_t lds, hipStream_t s) {
   void (*fn)(CfUnrollArgs) = hist ? k_cf_unroll<PRE, true> : k_cf_unroll<PRE, false>;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(fn, dim3(a.batch), dim3(kCfThreads), lds, s, a);
-  HIP_TRY(hipGetLastError());
-  return L2O_OK;
+  return launch(fn, dim3(a.batch), dim3(kCfThreads), lds, s, a);
 }
 
 // ... and several instances per launch: n_inst x batch workgroups, the pointers out of the tables in device scratch
 template <int PRE>
 static int launch_confocal_unroll_multi(const CfUnrollMultiArgs& a, int n_inst, bool hist, size_t lds, hipStream_t s) {
   void (*fn)(CfUnrollMultiArgs) = hist ? k_cf_unroll<PRE, true, true> : k_cf_unroll<PRE, false, true>;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(fn, dim3(n_inst * a.batch), dim3(kCfThreads), lds, s, a);
-  HIP_TRY(hipGetLastError());
-  return L2O_OK;
+  return launch(fn, dim3(n_inst * a.batch), dim3(kCfThreads), lds, s, a);
 }
 
 extern "C" {
@@ -1334,193 +469,6 @@ size_t l2o_wpack_floats(const l2o_net_cfg* cfg) {
   if (cfg->n_layers == 0) return 4;
   if (!net_ok_for_mfma(cfg)) return 0;
   return (size_t)wp_rows(cfg->preprocess) * 64 + (size_t)bx::words(cfg->preprocess) + (size_t)bxb::words(cfg->preprocess);
-}
-
-// ---- bf16x3 section of wpack (l2o_lstm_bx3.h) --------------------------------
-__host__ __device__ static inline uint16_t bf16_rne(float f) {
-  uint32_t u = __builtin_bit_cast(uint32_t, f);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__host__ __device__ static inline double bf16_value(uint16_t h) {
-  return (double)__builtin_bit_cast(float, (uint32_t)h << 16);
-}
-__host__ __device__ static inline void bf16_split3(double v, uint16_t (&out)[3]) {
-  for (int s = 0; s < 3; ++s) {
-    out[s] = bf16_rne((float)v);
-    v -= bf16_value(out[s]);
-  }
-}
-
-// Lane l's share of the packed weights (the buffer is zero beforehand): the host packer runs it for
-// l = 0..63, the device packer (l2o_wpack_device, the meta-training step) with one thread per lane.
-// The lanes write disjoint words.
-// [t_lo, t_hi): unit slices of the forward sections, [tile_lo, tile_hi): M-tiles of the BPTT section (the device
-// packer gives every (lane, slice) and (lane, tile) its own thread: the float64 splits are the cost).
-// (ch_lo, ch_hi): the gate-GEMM chunks of slices [t_lo, t_hi) this call packs -- everything of a slice that is not a
-// chunk fragment rides with chunk 0; (r_lo, r_hi): the gate types of the BPTT M-tiles [tile_lo, tile_hi).  The host
-// packer passes the full ranges; k_wpack one (slice, chunk) or one (tile, gate type) per block.
-__host__ __device__ static void wpack_lane(int pre, int l, int t_lo, int t_hi, int tile_lo, int tile_hi,
-                                           const float* wg1, const float* bg1, const float* wg2,
-                                           const float* bg2, const float* wl, const float* bl, const float* wfc,
-                                           const float* bfc, float* out, int ch_lo = 0, int ch_hi = 4, int r_lo = 0,
-                                           int r_hi = 4) {
-  const bool fc = pre == L2O_PRE_FC_ELU;
-  const int P = fc ? kH : (pre == L2O_PRE_LOGSIGN ? 2 : 1);
-  const int G = 4 * kH;
-  auto col = [](int t, int rho) { return (rho & 3) * kH + 4 * t + (rho >> 2); };
-  const int rho = l & 15, kq = l >> 4;   // A-fragment view of the lane
-  const int q = l >> 4;                  // C/D + B view of the lane
-  for (int t = t_lo; t < t_hi && ch_lo == 0; ++t) {
-    const int cA = col(t, rho);
-    // layer 1
-    if (fc) {
-      for (int kk = 0; kk < 10; ++kk) {
-        const int row = kk < 5 ? 4 * kk + kq : kH + 4 * (kk - 5) + kq;   // fc features, then h1
-        out[(wp_row_a1(pre) + kk * kNT + t) * 64 + l] = wg1[row * G + cA];
-      }
-    } else {
-      for (int kk = 0; kk < 5; ++kk)
-        out[(wp_row_a1(pre) + kk * kNT + t) * 64 + l] = wg1[(P + 4 * kk + kq) * G + cA];
-      float v = 0.0f;
-      if (kq == 0) v = wg1[0 * G + cA];
-      else if (kq == 1) v = P == 2 ? wg1[1 * G + cA] : 0.0f;
-      else if (kq == 2) v = bg1[cA];
-      out[(wp_row_a1(pre) + 5 * kNT + t) * 64 + l] = v;
-    }
-    // layer 2: kk 0..4 <- h1 (rows 0..19), kk 5..9 <- h2 (rows 20..39)
-    for (int kk = 0; kk < 10; ++kk) {
-      const int row = kk < 5 ? 4 * kk + kq : kH + 4 * (kk - 5) + kq;
-      out[(wp_row_a2(pre) + kk * kNT + t) * 64 + l] = wg2[row * G + cA];
-    }
-    for (int r = 0; r < 4; ++r) {
-      const int cD = col(t, 4 * q + r);
-      out[(wp_row_b1(pre) + t * 4 + r) * 64 + l] = fc ? bg1[cD] : 0.0f;
-      out[(wp_row_b2(pre) + t * 4 + r) * 64 + l] = bg2[cD];
-    }
-    out[(wp_row_wl(pre) + t) * 64 + l] = wl[4 * t + q];
-    if (fc) {
-      out[(wp_row_fc(pre) + t) * 64 + l] = wfc[0 * kH + 4 * t + q];
-      out[(wp_row_fc(pre) + kNT + t) * 64 + l] = wfc[1 * kH + 4 * t + q];
-      out[(wp_row_fc(pre) + 2 * kNT + t) * 64 + l] = bfc[4 * t + q];
-    }
-  }
-  if (t_lo == 0 && t_hi > 0 && ch_lo == 0) out[wp_row_bl(pre) * 64 + l] = bl[0];
-  // ---- bf16x3 fragments: gate rows pre-scaled to exp2 arguments, split from float64 ----
-  {
-    uint32_t* ow = reinterpret_cast<uint32_t*>(out);
-    constexpr double kL2E = 1.4426950408889634074;
-    auto gscale = [&](int r) { return r == 1 ? 2.0 * kL2E : -kL2E; };      // rows i, j, f, o
-    for (int t = t_lo; t < t_hi; ++t) {
-      const int cA = col(t, rho), r = rho & 3;
-      for (int ch = ch_lo; ch < ch_hi && ch < bx::nchunks(pre); ++ch) {
-        uint16_t sl[5][3], bs[3] = {0, 0, 0};
-        for (int i = 0; i < 5; ++i) {
-          const int u = 4 * i + kq;
-          double v;
-          if (ch == bx::kChL1H) v = wg1[(P + u) * G + cA];
-          else if (ch == bx::kChL2A) v = wg2[u * G + cA];
-          else if (ch == bx::kChL2B) v = wg2[(kH + u) * G + cA];
-          else v = wg1[u * G + cA];                              // kChL1X: the fc features
-          bf16_split3(v * gscale(r), sl[i]);
-        }
-        // (the bias slots of the fragments stay ZERO since round 3: the bias is the accumulator init, bx::bias_off)
-        // 6-product form: K-slots 0..4 = the units, slot 7 = the bias (q == 0), one fragment per split level
-        for (int sp = 0; sp < 3; ++sp)
-          for (int rg = 0; rg < 4; ++rg) {
-            auto slot = [&](int i) -> uint32_t { return i < 5 ? sl[i][sp] : (i == 7 && kq == 0 ? bs[sp] : 0); };
-            ow[bx::frag_off(pre, false, ch, t, sp) + l * 4 + rg] = slot(2 * rg) | (slot(2 * rg + 1) << 16);
-          }
-        // packed K-slots (l2o_lstm_bx3.h, slot_desc): the weight level that multiplies the slot's activation level
-        {
-          for (int j = 0; j < bx::kPack; ++j)
-            for (int rg = 0; rg < 4; ++rg) {
-              uint32_t word = 0;
-              for (int h = 0; h < 2; ++h) {
-                const bx::SlotDesc d = bx::slot_desc(j, rg, h);
-                uint16_t v16 = 0;
-                if (d.unit < 5) v16 = sl[d.unit][d.w];
-                else if (bx::bias_level(kq, h) >= 0) v16 = bs[bx::bias_level(kq, h)];
-                word |= (uint32_t)v16 << (16 * h);
-              }
-              ow[bx::frag_off(pre, true, ch, t, j) + l * 4 + rg] = word;
-            }
-        }
-      }
-      if (ch_lo != 0) continue;                                 // (the rest of the slice rides with chunk 0)
-      if ((l & 15) == 0)                                        // one lane per lane group writes its 4 gate rows
-        for (int rr = 0; rr < 4; ++rr) {
-          const int cD = col(t, 4 * q + rr);
-          const double fb = rr == 2 ? 1.0 : 0.0;                  // forget_bias
-          out[bx::bias_off(pre) + ((0 * kNT + t) * 4 + q) * 4 + rr] = (float)(((double)bg1[cD] + fb) * gscale(rr));
-          out[bx::bias_off(pre) + ((1 * kNT + t) * 4 + q) * 4 + rr] = (float)(((double)bg2[cD] + fb) * gscale(rr));
-        }
-      if (!fc)
-        for (int rr = 0; rr < 4; ++rr) {
-          const int cD = col(t, 4 * q + rr);
-          out[bx::win_off(pre) + t * 256 + l * 4 + rr] = (float)((double)wg1[0 * G + cD] * gscale(rr));
-          out[bx::win_off(pre) + (kNT + t) * 256 + l * 4 + rr] =
-              P == 2 ? (float)((double)wg1[1 * G + cD] * gscale(rr)) : 0.0f;
-        }
-    }
-  }
-  // ---- bf16x3 fragments of the transposed products of the BPTT step (l2o_bwd_mfma.h): W itself,
-  //      unscaled; M-tile rows = input rows of W, K-chunk r = gate type r (Sonnet column block) ----
-  {
-    uint32_t* ow = reinterpret_cast<uint32_t*>(out) + bxb::base(pre);
-    for (int tile = tile_lo; tile < tile_hi; ++tile) {
-      const bool l2 = tile < bxb::tiles2();
-      const int m = l2 ? tile : tile - bxb::tiles2();
-      const float* W = l2 ? wg2 : wg1;
-      const int first = l2 ? 0 : (fc ? 0 : -1), second = l2 ? kH : (fc ? kH : P);
-      const int row = bxb::src_row(m, rho, first, second);
-      if (row < 0) continue;
-      for (int r = r_lo; r < r_hi; ++r) {
-        uint16_t sl[8][3];
-        for (int i = 0; i < 8; ++i)
-          for (int sp = 0; sp < 3; ++sp) sl[i][sp] = 0;
-        for (int i = 0; i < 5; ++i) bf16_split3((double)W[row * G + r * kH + 4 * i + kq], sl[i]);
-        for (int sp = 0; sp < 3; ++sp)
-          for (int j = 0; j < 4; ++j)
-            ow[bxb::frag_rel(tile, r, sp) + l * 4 + j] = (uint32_t)sl[2 * j][sp] | ((uint32_t)sl[2 * j + 1][sp] << 16);
-      }
-    }
-  }
-}
-
-__global__ void k_wpack(int pre, const float* wg1, const float* bg1, const float* wg2, const float* bg2, const float* wl,
-                        const float* bl, const float* wfc, const float* bfc, float* out) {
-  // one block per (slice, chunk), then one per (BPTT M-tile, gate type): 35 / 44 blocks of one wave (10 / 11 blocks
-  // before: 12.5 us on the critical path between the meta-step and the next unroll)
-  const int b = blockIdx.x, nch = bx::nchunks(pre);
-  if (b < kNT * nch) {
-    const int t = b / nch, ch = b - t * nch;
-    wpack_lane(pre, threadIdx.x, t, t + 1, 0, 0, wg1, bg1, wg2, bg2, wl, bl, wfc, bfc, out, ch, ch + 1, 0, 0);
-  } else {
-    const int e = b - kNT * nch, tile = e >> 2, r = e & 3;
-    wpack_lane(pre, threadIdx.x, 0, 0, tile, tile + 1, wg1, bg1, wg2, bg2, wl, bl, wfc, bfc, out, 0, 0, r, r + 1);
-  }
-}
-
-// tf.train.AdamOptimizer._apply_dense (TF 1.x) on one flat fp32 vector, every operation rounded separately
-// like the NumPy expression it replaces (no contraction): bit-equal to the host update
-// guard != nullptr: the status word of the unroll whose gradients these are (the head of its workspace); a non-zero
-// status (a partner timeout: the recorded history is garbage) leaves w, m, v untouched
-// map != nullptr: the gradient of weight i is g[map[i]] (map[i] < 0: zero) -- the weight-gradient blocks are read
-// straight out of the contraction's [KA][KB] result (l2o_adam_step_gather)
-__global__ void k_adam(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g,
-                       long n, float lr_t, float b1, float omb1, float b2, float omb2, float eps,
-                       const unsigned* __restrict__ guard, const int* __restrict__ map) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if (guard && __builtin_nontemporal_load(guard) != 0u) return;
-  float gi;
-  if (map) { const int j = map[i]; gi = j >= 0 ? g[j] : 0.0f; }
-  else gi = g[i];
-  const float mi = __fadd_rn(__fmul_rn(b1, m[i]), __fmul_rn(omb1, gi));
-  const float vi = __fadd_rn(__fmul_rn(b2, v[i]), __fmul_rn(__fmul_rn(omb2, gi), gi));
-  m[i] = mi; v[i] = vi;
-  w[i] = __fsub_rn(w[i], __fdiv_rn(__fmul_rn(lr_t, mi), __fadd_rn(__fsqrt_rn(vi), eps)));
 }
 
 int l2o_wpack_host(const l2o_net_cfg* cfg, const float* wg1, const float* bg1, const float* wg2,
@@ -1625,17 +573,10 @@ static int launch_problem_fg(const ProbParams& pp, const float* x, float* f_part
     const size_t lds1 = sizeof(float) * ((size_t)kFgWaves * pp.D + kFgWaves);
     void (*f1)(ProbParams, const float*, float*, float*) =
         pp.D <= 256 ? k_problem_fg1<1> : pp.D <= 512 ? k_problem_fg1<2> : pp.D <= 1024 ? k_problem_fg1<4> : k_problem_fg1<8>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(f1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-    hipLaunchKernelGGL(f1, dim3(pp.B_local), dim3(kFgThreads), lds1, (hipStream_t)stream, pp, x, f_part, g);
-    HIP_TRY(hipGetLastError());
-    return L2O_OK;
+    return launch(f1, dim3(pp.B_local), dim3(kFgThreads), lds1, (hipStream_t)stream, pp, x, f_part, g);
   }
   void (*fn)(ProbParams, const float*, float*, float*) = vec ? k_problem_fg<true> : k_problem_fg<false>;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds));
-  hipLaunchKernelGGL(fn, dim3(pp.B_local), dim3(kFgThreads), lds, (hipStream_t)stream, pp, x, f_part, g);
-  HIP_TRY(hipGetLastError());
-  return L2O_OK;
+  return launch(fn, dim3(pp.B_local), dim3(kFgThreads), lds, (hipStream_t)stream, pp, x, f_part, g);
 }
 
 int l2o_problem_fg(const l2o_problem* prob, const float* x, float* f_part, float* g, void* stream) {
@@ -1644,15 +585,6 @@ int l2o_problem_fg(const l2o_problem* prob, const float* x, float* f_part, float
   if (rc) return rc;
   if (!x || !f_part) return fail(L2O_ERR_ARG, "l2o_problem_fg: NULL x / f_part");
   return launch_problem_fg(make_prob_params(prob), x, f_part, g, stream);
-}
-
-// out += s * inv_bg * f''(x s) * s * u for the separable cosine term (rastrigin / square_cos)
-__global__ void k_hvp_sep(ProbParams pp, const float* __restrict__ x, const float* __restrict__ u, float* __restrict__ out, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float sc = pp.x_scale ? pp.x_scale[i] : 1.0f;
-  const float xs = x[i] * sc;
-  out[i] += sc * pp.inv_bg * (pp.twopi * pp.twopi * pp.alpha * pp.C[i] * l2o::cos_f(pp.twopi * xs)) * sc * u[i];
 }
 
 int l2o_problem_hvp(const l2o_problem* prob, const float* x, const float* u, float* out, float* scratch, void* stream) {
@@ -1707,24 +639,14 @@ int l2o_mlp_fg(const l2o_mlp* mlp, const int32_t* indices, const float* w1, cons
     const int nkb20 = (p.n_in + 63) / 64;
     size_t lds20 = sizeof(float) * (size_t)kMlpBwdWaves * 64 * (kMlp20 + 1);
     if (lds_small > lds20) lds20 = lds_small;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_bwd20), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds20));
-    hipLaunchKernelGGL(k_mlp_bwd20, dim3(nkb20 + 1), dim3(64 * kMlpBwdWaves), lds20, s, p);
-    HIP_TRY(hipGetLastError());
-    return L2O_OK;
+    return launch(k_mlp_bwd20, dim3(nkb20 + 1), dim3(64 * kMlpBwdWaves), lds20, s, p);
   }
   void (*ffwd)(MlpParams) = HP == 20 ? k_mlp_fwd<20> : k_mlp_fwd<kMlpMaxH>;
   void (*fbwd)(MlpParams) = HP == 20 ? k_mlp_bwd<20> : k_mlp_bwd<kMlpMaxH>;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ffwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds_f));
-  hipLaunchKernelGGL(ffwd, dim3((p.batch + kMlpSPB - 1) / kMlpSPB), dim3(256), lds_f, s, p);
-  HIP_TRY(hipGetLastError());
+  const int rc = launch(ffwd, dim3((p.batch + kMlpSPB - 1) / kMlpSPB), dim3(256), lds_f, s, p);
+  if (rc) return rc;
   const int nkb = (p.n_in + kMlpKPB - 1) / kMlpKPB;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fbwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds_b));
-  hipLaunchKernelGGL(fbwd, dim3(nkb + 1), dim3(256), lds_b, s, p);
-  HIP_TRY(hipGetLastError());
-  return L2O_OK;
+  return launch(fbwd, dim3(nkb + 1), dim3(256), lds_b, s, p);
 }
 
 size_t l2o_mlp_scratch_floats(const l2o_mlp* mlp) {
@@ -2016,20 +938,11 @@ static int mlp_unroll_launch(const l2o_net_cfg* cfg, const float* wpack, const l
   }
   HIP_TRY(hipMemsetAsync(wsb + L.p_off, 0, L.total - L.p_off, s));   // the granules only: the header survives
   const dim3 grid(L.nwg), block(256);
-  void (*fn)(MlpUnrollArgs) = nullptr;
-  if (hist) {
-    switch (cfg->preprocess) {
-      case L2O_PRE_IDENTITY: fn = L.fast ? k_mlp_unroll<L2O_PRE_IDENTITY, true, true> : k_mlp_unroll<L2O_PRE_IDENTITY, false, true>; break;
-      case L2O_PRE_LOGSIGN: fn = L.fast ? k_mlp_unroll<L2O_PRE_LOGSIGN, true, true> : k_mlp_unroll<L2O_PRE_LOGSIGN, false, true>; break;
-      default: fn = L.fast ? k_mlp_unroll<L2O_PRE_FC_ELU, true, true> : k_mlp_unroll<L2O_PRE_FC_ELU, false, true>;
-    }
-  } else {
-    switch (cfg->preprocess) {
-      case L2O_PRE_IDENTITY: fn = L.fast ? k_mlp_unroll<L2O_PRE_IDENTITY, true> : k_mlp_unroll<L2O_PRE_IDENTITY, false>; break;
-      case L2O_PRE_LOGSIGN: fn = L.fast ? k_mlp_unroll<L2O_PRE_LOGSIGN, true> : k_mlp_unroll<L2O_PRE_LOGSIGN, false>; break;
-      default: fn = L.fast ? k_mlp_unroll<L2O_PRE_FC_ELU, true> : k_mlp_unroll<L2O_PRE_FC_ELU, false>;
-    }
-  }
+  void (*fn)(MlpUnrollArgs) = with_pre(cfg->preprocess, [&](auto pre) -> void (*)(MlpUnrollArgs) {
+    constexpr int PRE = decltype(pre)::value;
+    if (hist) return L.fast ? k_mlp_unroll<PRE, true, true> : k_mlp_unroll<PRE, false, true>;
+    return L.fast ? k_mlp_unroll<PRE, true> : k_mlp_unroll<PRE, false>;
+  });
   hipLaunchKernelGGL(fn, grid, block, 0, s, a);
   HIP_TRY(hipGetLastError());
   note_form(!L.fast ? L2O_FORM_MLP_UNROLL_GENERIC : (a.hier_R1 ? L2O_FORM_MLP_UNROLL_HIER : L2O_FORM_MLP_UNROLL));
@@ -2458,12 +1371,7 @@ static int confocal_unroll_launch(const char* who, const l2o_net_cfg* cfg, const
   hipStream_t s = (hipStream_t)stream;
   if (hist) hipLaunchKernelGGL(k_cf_hist_table, dim3(1), dim3(256), 0, s, hp, tab);
   const size_t lds = sizeof(float) * (size_t)a.rx * a.ry * a.rz;
-  int rc;
-  switch (cfg->preprocess) {
-    case L2O_PRE_IDENTITY: rc = launch_confocal_unroll<L2O_PRE_IDENTITY>(a, hist != nullptr, lds, s); break;
-    case L2O_PRE_LOGSIGN: rc = launch_confocal_unroll<L2O_PRE_LOGSIGN>(a, hist != nullptr, lds, s); break;
-    default: rc = launch_confocal_unroll<L2O_PRE_FC_ELU>(a, hist != nullptr, lds, s);
-  }
+  const int rc = with_pre(cfg->preprocess, [&](auto pre) { return launch_confocal_unroll<decltype(pre)::value>(a, hist != nullptr, lds, s); });
   if (rc != L2O_OK) return rc;
   hipLaunchKernelGGL(k_reduce_fx, dim3(T + 1), dim3(64), 0, s, a.fx_part, (int)(T + 1), (int)a.batch, a.rb, fx);
   HIP_TRY(hipGetLastError());
@@ -2555,12 +1463,7 @@ static int confocal_unroll_multi_launch(const char* who, const l2o_net_cfg* cfg,
   pow_ff(cfg->beta2, step0, &a.p2_hi, &a.p2_lo);
   a.tab = tab;
   const size_t lds = sizeof(float) * (size_t)a.rx * a.ry * a.rz;
-  int rc;
-  switch (cfg->preprocess) {
-    case L2O_PRE_IDENTITY: rc = launch_confocal_unroll_multi<L2O_PRE_IDENTITY>(a, n_inst, hist != nullptr, lds, s); break;
-    case L2O_PRE_LOGSIGN: rc = launch_confocal_unroll_multi<L2O_PRE_LOGSIGN>(a, n_inst, hist != nullptr, lds, s); break;
-    default: rc = launch_confocal_unroll_multi<L2O_PRE_FC_ELU>(a, n_inst, hist != nullptr, lds, s);
-  }
+  const int rc = with_pre(cfg->preprocess, [&](auto pre) { return launch_confocal_unroll_multi<decltype(pre)::value>(a, n_inst, hist != nullptr, lds, s); });
   if (rc != L2O_OK) return rc;
   hipLaunchKernelGGL(k_cf_reduce_fx_multi, dim3(T + 1, n_inst), dim3(64), 0, s, tab, (int)a.batch, a.rb);
   HIP_TRY(hipGetLastError());
@@ -2683,42 +1586,19 @@ static int mlp_unroll_multi_launch(const l2o_net_cfg* cfg, const float* wpack, c
   }
   HIP_TRY(hipMemsetAsync(wsb + L.team_off, 0, L.total - L.team_off, s));   // team counters + granules: the header survives
   const bool b128 = mlp->batch == 128;
-  size_t lds = 0;
-  switch (cfg->preprocess) {
-    case L2O_PRE_IDENTITY: lds = b128 ? mlp_xcd_lds_bytes<L2O_PRE_IDENTITY, 128>() : mlp_xcd_lds_bytes<L2O_PRE_IDENTITY, 64>(); break;
-    case L2O_PRE_LOGSIGN: lds = b128 ? mlp_xcd_lds_bytes<L2O_PRE_LOGSIGN, 128>() : mlp_xcd_lds_bytes<L2O_PRE_LOGSIGN, 64>(); break;
-    default: lds = b128 ? mlp_xcd_lds_bytes<L2O_PRE_FC_ELU, 128>() : mlp_xcd_lds_bytes<L2O_PRE_FC_ELU, 64>();
-  }
   // one workgroup per CU of the whole chip: the 32 that land on XCD j < n_inst form instance j's team, the others exit
   const dim3 grid(kMxMaxInst * kMxMembers), block(four ? kMxThreads4 : kMxThreads);
-  if (hist) {
-    void (*fn)(MlpXcdHistArgs) = nullptr;
-    switch (cfg->preprocess) {
-      case L2O_PRE_IDENTITY:
-        fn = b128 ? k_mlp_xcd<L2O_PRE_IDENTITY, 8, true, 128> : four ? k_mlp_xcd<L2O_PRE_IDENTITY, 4, true> : k_mlp_xcd<L2O_PRE_IDENTITY, 8, true>;
-        break;
-      case L2O_PRE_LOGSIGN:
-        fn = b128 ? k_mlp_xcd<L2O_PRE_LOGSIGN, 8, true, 128> : four ? k_mlp_xcd<L2O_PRE_LOGSIGN, 4, true> : k_mlp_xcd<L2O_PRE_LOGSIGN, 8, true>;
-        break;
-      default: fn = b128 ? k_mlp_xcd<L2O_PRE_FC_ELU, 8, true, 128> : four ? k_mlp_xcd<L2O_PRE_FC_ELU, 4, true> : k_mlp_xcd<L2O_PRE_FC_ELU, 8, true>;
+  const int rc = with_pre(cfg->preprocess, [&](auto pre) {
+    constexpr int PRE = decltype(pre)::value;
+    const size_t lds = b128 ? mlp_xcd_lds_bytes<PRE, 128>() : mlp_xcd_lds_bytes<PRE, 64>();
+    if (hist) {
+      void (*fn)(MlpXcdHistArgs) = b128 ? k_mlp_xcd<PRE, 8, true, 128> : four ? k_mlp_xcd<PRE, 4, true> : k_mlp_xcd<PRE, 8, true>;
+      return launch(fn, grid, block, lds, s, a);
     }
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(fn, grid, block, lds, s, a);
-  } else {
-    void (*fn)(MlpXcdArgs) = nullptr;
-    switch (cfg->preprocess) {
-      case L2O_PRE_IDENTITY:
-        fn = b128 ? k_mlp_xcd<L2O_PRE_IDENTITY, 8, false, 128> : four ? k_mlp_xcd<L2O_PRE_IDENTITY, 4> : k_mlp_xcd<L2O_PRE_IDENTITY, 8>;
-        break;
-      case L2O_PRE_LOGSIGN:
-        fn = b128 ? k_mlp_xcd<L2O_PRE_LOGSIGN, 8, false, 128> : four ? k_mlp_xcd<L2O_PRE_LOGSIGN, 4> : k_mlp_xcd<L2O_PRE_LOGSIGN, 8>;
-        break;
-      default: fn = b128 ? k_mlp_xcd<L2O_PRE_FC_ELU, 8, false, 128> : four ? k_mlp_xcd<L2O_PRE_FC_ELU, 4> : k_mlp_xcd<L2O_PRE_FC_ELU, 8>;
-    }
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(fn, grid, block, lds, s, static_cast<const MlpXcdArgs&>(a));
-  }
-  HIP_TRY(hipGetLastError());
+    void (*fn)(MlpXcdArgs) = b128 ? k_mlp_xcd<PRE, 8, false, 128> : four ? k_mlp_xcd<PRE, 4> : k_mlp_xcd<PRE, 8>;
+    return launch(fn, grid, block, lds, s, static_cast<const MlpXcdArgs&>(a));
+  });
+  if (rc) return rc;
   note_form(L2O_FORM_MLP_XCD);
   return L2O_OK;
 }
@@ -2781,11 +1661,7 @@ int l2o_cwlstm_step_multi(const l2o_net_cfg* cfg, const float* wpack, const l2o_
   if (blocks > 256) blocks = 256;            // one 4-wave block per CU (one wave per SIMD), grid-stride beyond
   const dim3 grid(blocks), block(256);
   const float om1 = (float)(1.0 - pow1), om2 = (float)(1.0 - pow2);
-  switch (cfg->preprocess) {
-    case L2O_PRE_IDENTITY: hipLaunchKernelGGL(k_cwlstm_step<L2O_PRE_IDENTITY>, grid, block, 0, s, np, sg, om1, om2); break;
-    case L2O_PRE_LOGSIGN: hipLaunchKernelGGL(k_cwlstm_step<L2O_PRE_LOGSIGN>, grid, block, 0, s, np, sg, om1, om2); break;
-    default: hipLaunchKernelGGL(k_cwlstm_step<L2O_PRE_FC_ELU>, grid, block, 0, s, np, sg, om1, om2);
-  }
+  with_pre(cfg->preprocess, [&](auto pre) { hipLaunchKernelGGL(k_cwlstm_step<decltype(pre)::value>, grid, block, 0, s, np, sg, om1, om2); });
   HIP_TRY(hipGetLastError());
   return L2O_OK;
 }
@@ -2805,26 +1681,12 @@ static int launch_bwd_tile(const BwdParams& p, int pre, hipStream_t s) {
   if (opt(L2O_OPT_BWD_BLOCKS) > 0) cap = (size_t)opt(L2O_OPT_BWD_BLOCKS);
   if (nblk > cap && p.T <= 1) nblk = cap;                  // (a T-step launch keeps one workgroup per four tiles: each lives T steps)
   const dim3 grid((unsigned)nblk), block(256);
-  void (*fn)(BwdParams) = nullptr;
-  size_t lds = 0;
-  if (p.wpack && opt(L2O_OPT_BWD_KERNEL) == 0) {                // the matrix-core form needs the packed weights
-    switch (pre) {
-      case L2O_PRE_IDENTITY: fn = k_cwlstm_bwd_mfma<L2O_PRE_IDENTITY>; lds = BwdMfmaGeom<L2O_PRE_IDENTITY>::kLdsFloats; break;
-      case L2O_PRE_LOGSIGN: fn = k_cwlstm_bwd_mfma<L2O_PRE_LOGSIGN>; lds = BwdMfmaGeom<L2O_PRE_LOGSIGN>::kLdsFloats; break;
-      default: fn = k_cwlstm_bwd_mfma<L2O_PRE_FC_ELU>; lds = BwdMfmaGeom<L2O_PRE_FC_ELU>::kLdsFloats;
-    }
-  } else {
-    switch (pre) {
-      case L2O_PRE_IDENTITY: fn = k_cwlstm_bwd_tile<L2O_PRE_IDENTITY>; lds = BwdTileGeom<L2O_PRE_IDENTITY>::kLdsFloats; break;
-      case L2O_PRE_LOGSIGN: fn = k_cwlstm_bwd_tile<L2O_PRE_LOGSIGN>; lds = BwdTileGeom<L2O_PRE_LOGSIGN>::kLdsFloats; break;
-      default: fn = k_cwlstm_bwd_tile<L2O_PRE_FC_ELU>; lds = BwdTileGeom<L2O_PRE_FC_ELU>::kLdsFloats;
-    }
-  }
-  lds *= sizeof(float);
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(fn, grid, block, lds, s, p);
-  HIP_TRY(hipGetLastError());
-  return L2O_OK;
+  const bool mfma = p.wpack && opt(L2O_OPT_BWD_KERNEL) == 0;   // the matrix-core form needs the packed weights
+  return with_pre(pre, [&](auto pr) {
+    constexpr int PRE = decltype(pr)::value;
+    if (mfma) return launch(k_cwlstm_bwd_mfma<PRE>, grid, block, sizeof(float) * BwdMfmaGeom<PRE>::kLdsFloats, s, p);
+    return launch(k_cwlstm_bwd_tile<PRE>, grid, block, sizeof(float) * BwdTileGeom<PRE>::kLdsFloats, s, p);
+  });
 }
 
 static void fill_bwd_net(BwdParams& p, const l2o_net_cfg* cfg, const l2o_net_weights* w, double pow1, double pow2) {
@@ -2997,19 +1859,13 @@ int l2o_cwlstm_bwd_step(const l2o_net_cfg* cfg, const l2o_net_weights* w, const 
       p.seg_g[0] = io->g; p.seg_m[0] = io->m; p.seg_v[0] = io->v; p.seg_st[0] = io->st_prev; p.seg_dx[0] = io->dx_next;
       p.rows_total = (long)N;
       return launch_bwd_tile(p, pre, s);
-      return L2O_OK;
     }
   }
   const size_t lds = 0;                                   // static LDS only (the per-thread input column)
   const dim3 grid((unsigned)((N + 63) / 64)), block(64);
-  switch (pre) {
-    case L2O_PRE_IDENTITY: hipLaunchKernelGGL(k_cwlstm_bwd_step<L2O_PRE_IDENTITY>, grid, block, lds, s, p); break;
-    case L2O_PRE_LOGSIGN: hipLaunchKernelGGL(k_cwlstm_bwd_step<L2O_PRE_LOGSIGN>, grid, block, lds, s, p); break;
-    default:
-      if (!io->m || !io->v || !io->feats || !io->du || !w->w_fc || !w->b_fc)
-        return fail(L2O_ERR_ARG, "l2o_cwlstm_bwd_step: RNNProp needs m, v, feats, du and the fc weights");
-      hipLaunchKernelGGL(k_cwlstm_bwd_step<L2O_PRE_FC_ELU>, grid, block, lds, s, p);
-  }
+  if (pre != L2O_PRE_IDENTITY && pre != L2O_PRE_LOGSIGN && (!io->m || !io->v || !io->feats || !io->du || !w->w_fc || !w->b_fc))
+    return fail(L2O_ERR_ARG, "l2o_cwlstm_bwd_step: RNNProp needs m, v, feats, du and the fc weights");
+  with_pre(pre, [&](auto pr) { hipLaunchKernelGGL(k_cwlstm_bwd_step<decltype(pr)::value>, grid, block, lds, s, p); });
   HIP_TRY(hipGetLastError());
   return L2O_OK;
 }
@@ -3160,17 +2016,11 @@ static int unroll_impl(const l2o_net_cfg* cfg, const float* wpack, const l2o_pro
   rc = L2O_OK;
   if (cfg->preprocess == L2O_PRE_FC_ELU && (!m || !v)) return fail(L2O_ERR_ARG, "l2o_unroll: RNNProp needs m and v");
   if (!lds_form) {
-    switch (cfg->preprocess) {
-      case L2O_PRE_IDENTITY: rc = launch_unroll_cu<L2O_PRE_IDENTITY>(a, s); break;
-      case L2O_PRE_LOGSIGN: rc = launch_unroll_cu<L2O_PRE_LOGSIGN>(a, s); break;
-      default: rc = launch_unroll_cu<L2O_PRE_FC_ELU>(a, s);
-    }
+    rc = with_pre(cfg->preprocess, [&](auto pre) { return launch_unroll_cu<decltype(pre)::value>(a, s); });
   } else {
-    switch (cfg->preprocess) {
-      case L2O_PRE_IDENTITY: rc = launch_unroll_kind<L2O_PRE_IDENTITY>(a, g, prob->kind, s, prob, workspace, fx, &fx_done); break;
-      case L2O_PRE_LOGSIGN: rc = launch_unroll_kind<L2O_PRE_LOGSIGN>(a, g, prob->kind, s, prob, workspace, fx, &fx_done); break;
-      default: rc = launch_unroll_kind<L2O_PRE_FC_ELU>(a, g, prob->kind, s, prob, workspace, fx, &fx_done);
-    }
+    rc = with_pre(cfg->preprocess, [&](auto pre) {
+      return launch_unroll_kind<decltype(pre)::value>(a, g, prob->kind, s, prob, workspace, fx, &fx_done);
+    });
   }
   if (rc) return rc;
   if (fx && !fx_done)                                       // forms without the fused epilogue: the separate reduction
@@ -3237,5 +2087,3 @@ int l2o_rnnprop_input_adjoint(const float* Bm, int64_t ldb, int32_t du_col, int3
 }
 
 }  // extern "C"
-
-#endif  // L2O_TU_ILP

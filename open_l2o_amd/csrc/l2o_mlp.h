@@ -9,6 +9,7 @@
 //   k_mlp_bwd : 64 input rows of gw1 per workgroup (coalesced image rows), one extra
 //               workgroup for gw2, gb2, gb1 and the fixed-order loss sum
 #pragma once
+#include "l2o_params.h"
 
 constexpr int kMlpMaxH = 32;
 constexpr int kMlpMaxO = 16;

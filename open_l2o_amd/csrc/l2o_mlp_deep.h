@@ -10,6 +10,7 @@
 //   k_mlp_deep_grad     one thread per weight / bias coordinate: the sum over the samples of input x delta, in sample order
 //                       (fixed order: bit-reproducible); thread 0 of block 0 also adds the per-sample losses
 #pragma once
+#include "l2o_params.h"
 
 namespace l2o {
 

@@ -1,7 +1,7 @@
 // l2o_mlp_hvp.h -- Hessian-vector product of the problems.mnist loss on one minibatch (l2o_mlp_hvp): out = H(w) u with H the
 // Hessian of the mean softmax cross-entropy l2o_mlp_deep_fg differentiates (1 / batch included).  What second_derivatives=True
-// adds to the meta-gradient of an MLP optimizee (DM/meta.py:322-329 without the tf.stop_gradient).  Included by
-// l2o_kernels.hip after l2o_mlp_deep.h (its limits and its layer order); written for gfx950 only.
+// adds to the meta-gradient of an MLP optimizee (DM/meta.py:322-329 without the tf.stop_gradient).  Builds on
+// l2o_mlp_deep.h (its limits and its layer order); written for gfx950 only.
 //
 // The FULL Hessian (not Gauss-Newton), forward-over-reverse (Pearlmutter's R-operator).  Per sample, tangents Vw_l, Vb_l = u:
 //   z_l = a_{l-1} W_l + b_l          Rz_l = Ra_{l-1} W_l + a_{l-1} Vw_l + Vb_l     (Ra_{-1} = 0: the image has no tangent)
@@ -20,6 +20,7 @@
 //                      their terms in fp32).  No atomics: two calls on the same inputs are bit-identical; every scratch entry
 //                      that is read was written by this call, every output entry is written.
 #pragma once
+#include "l2o_mlp_deep.h"
 
 #include "../../include/l2o_mlp_hvp_abi.h"
 

@@ -28,6 +28,8 @@
 // double-buffered by step parity (their publishers run at most one evaluation ahead of the slowest reader).
 // Every spin is bounded; a timeout raises the sticky status word of the workspace header.
 #pragma once
+#include "l2o_lstm_bx3.h"
+#include "l2o_params.h"
 
 #ifndef L2O_MU_SLEEP2
 #define L2O_MU_SLEEP2 1    // back-off between two polls of a granule pair (x 64 clocks)

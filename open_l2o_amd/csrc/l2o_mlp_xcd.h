@@ -1,7 +1,7 @@
 // l2o_mlp_xcd.h -- the fused persistent unroll of the neural optimizee (l2o_mlp_unroll.h; DM/problems.py:246-288 stepped
 // by ONE coordinate-wise LSTM optimizer, DM/meta_rnnprop_train.py:371-423) with every optimizee INSTANCE confined to ONE
 // XCD: up to eight independent unrolls per launch, one per XCD (round 6).
-// Included by l2o_kernels.hip after l2o_mlp_unroll.h (its granule helpers); written for gfx950 only.
+// Builds on l2o_mlp_unroll.h (its granule helpers); written for gfx950 only.
 //
 // Why: k_mlp_unroll puts ONE instance on the whole chip -- 996 tiles on 996 SIMDs of 249 workgroups on 8 XCDs -- and its
 // step is three exchange hops (local reduce, fabric, local gather) around 670 cycles of LSTM work per tile: 54 % of the wave
@@ -30,6 +30,7 @@
 //   fallback protocol, no cross-XCD traffic at all.  What it costs: eight tile-steps per SIMD and step instead of one, so
 //   the LATENCY of a single unroll is worse than k_mlp_unroll's -- the form is selected per call (l2o_mlp_unroll_multi).
 #pragma once
+#include "l2o_mlp_unroll.h"
 
 namespace l2o {
 

@@ -19,6 +19,7 @@
 // Forward only (g == NULL): the first three (up to the loss) and the loss sum.
 // BN variance: per-sample (mean, M2) merged as M2 = sum M2_s + n sum (mean_s - mean)^2 (never E[z^2] - E[z]^2).
 #pragma once
+#include "l2o_params.h"
 
 namespace l2o {
 

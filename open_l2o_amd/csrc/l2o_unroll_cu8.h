@@ -1,5 +1,5 @@
 // l2o_unroll_cu8.h -- the streaming fused unroll (l2o_unroll_cu.h: D <= 512, any M: BASELINE config 3) with EIGHT waves per
-// workgroup -- two per SIMD.  Included by l2o_kernels.hip after l2o_unroll_cu.h; written for gfx950 only.
+// workgroup -- two per SIMD.  Builds on l2o_unroll_cu.h (layout, slot helpers); written for gfx950 only.
 //
 // Why (round 4, after k_unroll_lds): k_unroll_cu's step is an 11 us matrix stream followed by a 17 us optimizer phase in
 // which every SIMD runs ONE wave through eight tile steps, one after the other -- and a single wave is issue-bound
@@ -14,6 +14,7 @@
 //   per step:  GEMV phase (8 waves x M/8 rows, a ring of 2 row groups per wave) -> partial g, partial f -> barrier B1 ->
 //              optimizer phase (wave w: tiles w, w + 8, ...) -> x, x*s in LDS -> barrier B2
 #pragma once
+#include "l2o_unroll_cu.h"
 
 namespace l2o {
 

@@ -1,5 +1,5 @@
 // l2o_unroll_lds.h -- the fused persistent unroll for LARGE shards: one problem per workgroup / CU, EIGHT waves
-// (two per SIMD), the bf16x3 gate GEMM with its weight fragments in LDS.  Included by l2o_kernels.hip after k_unroll.
+// (two per SIMD), the bf16x3 gate GEMM with its weight fragments in LDS.  Builds on l2o_unroll_pair.h (its GEMV helpers).
 //
 // Why (round 4): a shard of more than #CU / 2 problems runs the two-CU kernel as consecutive chunk launches -- every
 // chunk pays the cross-CU exchange and leaves each SIMD with one latency-bound wave (BASELINE config 4 on one GPU: 8 chunks,
@@ -16,6 +16,7 @@
 // 65 <= padded size <= 128 (5..8 tiles); DM nets (identity / LogAndSign preprocessing: three packed chunks, 60 KB) and
 // RNNProp (fc + ELU: four chunks, 80 KB).
 #pragma once
+#include "l2o_unroll_pair.h"
 
 // (timing ablations, scripts/ab.sh ablate_lds: L2O_LDS_ABL_NOBAR drops the two barriers, _NOGEMV the xs / rs reads,
 //  _NOFRAG (l2o_lstm_bx3.h) the fragment reads -- each gives wrong numerics and is never shipped)

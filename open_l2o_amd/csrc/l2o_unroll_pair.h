@@ -1,5 +1,5 @@
 // l2o_unroll_pair.h -- the fused persistent unroll with every problem split over TWO
-// workgroups (two CUs).  Included by l2o_kernels.hip after k_unroll.
+// workgroups (two CUs).  Launched by l2o_kernels.hip (launch_unroll_ch).
 //
 // Why: a batch of B <= #CU/2 problems (BASELINE config 2: B = 128 on 256 CUs) leaves half
 // the chip idle with one problem per CU, and the per-step critical path of a problem is
@@ -26,6 +26,8 @@
 // floats per lane), because with W in LDS the two GEMV passes were LDS-bandwidth bound
 // (1 KB per wave ds_read_b128 x 32 per wave per pass = 1024 cycles per CU).
 #pragma once
+#include "l2o_lstm_bx3.h"
+#include "l2o_params.h"
 
 struct PairWs {               // header of the caller-owned workspace (never cleared by the library)
   unsigned status;            // 0 ok, 1 = partner timeout.  STICKY: raised by the kernel, cleared by the caller
@@ -102,7 +104,7 @@ __device__ __forceinline__ void lds_load_f4(l2o::f32x4 (&v)[N], const float* p) 
 #pragma unroll
   for (int m = 0; m < N; ++m) v[m] = q[4 * m];             // (+64 bytes per read: the row / column chunk of tile m)
 }
-// (dot4 of l2o_kernels.hip with the LDS operand as an ext-vector register quad: no float4 <-> f32x4 copies)
+// (dot4 of l2o_params.h with the LDS operand as an ext-vector register quad: no float4 <-> f32x4 copies)
 __device__ __forceinline__ void dot4v(const float4 a, const l2o::f32x4 b, float4& acc) {
   acc.x = __builtin_fmaf(a.x, b[0], acc.x);
   acc.y = __builtin_fmaf(a.y, b[1], acc.y);
@@ -584,81 +586,3 @@ __global__ __launch_bounds__(256) void k_unroll_pair(UnrollPairArgs pa) {
   if constexpr (FAST) unroll_pair_body<PRE, KIND, CH, HIST, EXACT>(pa);
   else unroll_pair_body_gather<PRE, KIND, CH, HIST, EXACT>(pa);
 }
-
-// The epilogue of a two-CU unroll, one workgroup (64 threads) per step t; runs after every workgroup of the unroll
-// has finished:
-//   fx_part[t][b] = sum of the 2 x NWH per-wave partials of (step t, problem b), fixed order
-//   fx[t]         = (sum_b fx_part[t][b]) / B_global, the summation order of k_reduce_fx (optional)
-//   the exchange granules are zeroed for the NEXT launch (tag 0 is never valid; no memset launch per unroll)
-//   the launch sequence word the next launch salts its tags with advances
-#ifndef L2O_TU_ILP       // (not a template: defined in the main translation unit only, see l2o_ilp_kernels.h)
-__global__ __launch_bounds__(256) void k_combine_halves(const float* __restrict__ fx_half, float* __restrict__ fx_part,
-                                                        int nb, int nparts, float inv_bg, float* __restrict__ fx,
-                                                        unsigned long long* __restrict__ xbuf, long xwords, PairWs* ws,
-                                                        int b0, int B_local) {
-  // nb problems of this launch = problems [b0, b0 + nb) of the shard (fx_part rows have B_local entries).  256 threads:
-  // waves 1..3 zero the granules, wave 0 forms the sums.  The kernel sits between two unrolls of a bench step, so what
-  // counts is its chain of dependent memory round trips (round 13): the sequence word is fetched at entry, not in front
-  // of its store; a lane has the partials of BOTH its problems (nb <= 128: lane and lane + 64) in flight before its first
-  // add -- clamped addresses and selects, no loop whose loads wait for its counter; the granules go out 16 bytes per
-  // store, from waves that have no load pending (stores and loads share the wave's memory counter: in one wave the second
-  // round of stores waited for the loads).  The adds and their order are what they were: per problem ((p0 + p1) + p2) +
-  // ..., per lane 0 + f(lane) + f(lane + 64), then wave_sum64.
-  const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  if (tid >= 64) {
-    // block t zeroes pairs [t per2, (t + 1) per2) of the xwords / 2 whole pairs of granules (the area is 16-byte aligned:
-    // it follows the 192-byte header); the last granule of an odd count is wave 0's, below
-    const long npairs = xwords >> 1;
-    const long per2 = (npairs + gridDim.x - 1) / gridDim.x;
-    const long lo = (long)t * per2, hi = lo + per2 < npairs ? lo + per2 : npairs;
-    ulonglong2* xpair = reinterpret_cast<ulonglong2*>(xbuf);
-    for (long e = lo + (tid - 64); e < hi; e += 192) xpair[e] = make_ulonglong2(0ull, 0ull);
-    return;
-  }
-  const bool bump = t == 0 && tid == 0;
-  unsigned seq0 = 0;
-  if (bump) seq0 = ws->seq;
-  float acc = 0.0f;
-  if (nb <= 128 && (nparts == 2 || nparts == 4 || nparts == 8)) {
-    const int bA = lane, bB = lane + 64;
-    const bool hA = bA < nb, hB = bB < nb;
-    const float* pA = fx_half + ((size_t)t * nb + (hA ? bA : 0)) * nparts;
-    const float* pB = fx_half + ((size_t)t * nb + (hB ? bB : 0)) * nparts;
-    float fA, fB;
-    if (nparts == 8) {
-      const float4 a0 = *reinterpret_cast<const float4*>(pA), a1 = *reinterpret_cast<const float4*>(pA + 4);
-      const float4 c0 = *reinterpret_cast<const float4*>(pB), c1 = *reinterpret_cast<const float4*>(pB + 4);
-      fA = ((a0.x + a0.y) + a0.z) + a0.w;
-      fA = (((fA + a1.x) + a1.y) + a1.z) + a1.w;
-      fB = ((c0.x + c0.y) + c0.z) + c0.w;
-      fB = (((fB + c1.x) + c1.y) + c1.z) + c1.w;
-    } else if (nparts == 4) {
-      const float4 a0 = *reinterpret_cast<const float4*>(pA), c0 = *reinterpret_cast<const float4*>(pB);
-      fA = ((a0.x + a0.y) + a0.z) + a0.w;
-      fB = ((c0.x + c0.y) + c0.z) + c0.w;
-    } else {
-      const float2 a0 = *reinterpret_cast<const float2*>(pA), c0 = *reinterpret_cast<const float2*>(pB);
-      fA = a0.x + a0.y;
-      fB = c0.x + c0.y;
-    }
-    if (hA) { fx_part[(size_t)t * B_local + b0 + bA] = fA; acc += fA; }
-    if (hB) { fx_part[(size_t)t * B_local + b0 + bB] = fB; acc += fB; }
-  } else {
-    for (int b = lane; b < nb; b += 64) {                  // (any other shape: the loop of rounds 7-12)
-      const float* p = fx_half + ((size_t)t * nb + b) * nparts;
-      float f = p[0];
-      for (int k = 1; k < nparts; ++k) f += p[k];
-      fx_part[(size_t)t * B_local + b0 + b] = f;
-      acc += f;
-    }
-  }
-  if (fx) {                                               // (single-launch batches only: nb == B_local)
-    acc = l2o::wave_sum64(acc);
-    if (lane == 0) fx[t] = acc * inv_bg;
-  }
-  if (bump) {
-    if (xwords & 1) xbuf[xwords - 1] = 0ull;
-    ws->seq = seq0 + 1u;
-  }
-}
-#endif

@@ -1,5 +1,5 @@
-// l2o_unroll_pair_loop.h -- NOT a header of its own: the step loop and the epilogue of the two-CU unroll, the text both
-// bodies of l2o_unroll_pair.h (unroll_pair_body_gather, unroll_pair_body) include behind their prologue, inside the
+// l2o_unroll_pair_loop.h -- a fragment of l2o_unroll_pair.h, NOT a header of its own: the step loop and the epilogue of the
+// two-CU unroll, the text both bodies (unroll_pair_body_gather, unroll_pair_body) include behind their prologue, inside the
 // function.  One text, so the two kernels cannot drift apart; two functions, so the code in front of the loop of one
 // does not move the schedule of the other (profiles/r08_launch_fixed_cost.txt, section 8).  No include guard: included twice.
   f32x4 acc1[kNT], acc2[kNT];

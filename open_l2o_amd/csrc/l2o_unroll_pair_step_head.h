@@ -1,5 +1,5 @@
-// l2o_unroll_pair_step_head.h -- NOT a header of its own: the first half of a step of the two-CU unroll, from the scaled
-// iterate to this wave's loss partial of f(x_t).  Text of l2o_unroll_pair_loop.h, which includes it inside the step loop AND
+// l2o_unroll_pair_step_head.h -- a fragment of l2o_unroll_pair.h, NOT a header of its own: the first half of a step, from the
+// scaled iterate to this wave's loss partial of f(x_t).  Text of l2o_unroll_pair_loop.h, which includes it inside the step loop AND
 // once more behind the loop of the plain kernel (the final loss evaluation f(x_T)).  Expects `t` in scope.  No include guard.
     const float xsv = xv * sc;
     const unsigned tag = salt | ((unsigned)t + 1u);     // (T + 1 < 65 535 when salt != 0; the handshake tag ends in 0xffff)

@@ -1,5 +1,5 @@
-// l2o_unroll_pair_step_tail.h -- NOT a header of its own: the second half of a step of the two-CU unroll, from the gradient
-// g = W^T r through the optimizer net to the next scaled iterate.  Text of l2o_unroll_pair_loop.h, included inside the step
+// l2o_unroll_pair_step_tail.h -- a fragment of l2o_unroll_pair.h, NOT a header of its own: the second half of a step, from the
+// gradient g = W^T r through the optimizer net to the next scaled iterate.  Text of l2o_unroll_pair_loop.h, included inside the step
 // loop behind l2o_unroll_pair_step_head.h, whose locals (xsv, trig, rv4v) it reads.  No include guard.
     // ---- g = W^T r for this wave's 16 coordinates ------------------------------
     // all CH residual reads are issued back to back (hipcc serialises them on one register

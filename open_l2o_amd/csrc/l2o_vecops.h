@@ -4,6 +4,7 @@
 // of them once or T times on a few thousand to a few hundred thousand floats -- but the training path now runs on l2o_*
 // entry points only.  Included by l2o_kernels.hip.
 #pragma once
+#include "l2o_params.h"
 
 // out[t][i] = g_final[i] + sum_{tau > t} g[tau][i]  for t = T-1 .. 0: dL/d(delta_t) of loss = sum_t f(x_t)
 // (DM/meta.py:372-376 with the optimizee gradients held constant, DM/meta.py:328-329).  g: a device table of T
