@@ -24,6 +24,7 @@ PROB_MNIST_CONV = 6
 PROB_CIFAR_CONV = 7
 PROB_LENET = 8
 PROB_CONFOCAL = 9
+PROB_VGG16 = 10           # include/l2o_vgg16_abi.h (added after ABI v15)
 
 # every symbol include/l2o_abi.h declares (tests check the library exports all of them)
 SYMBOLS = (
@@ -46,6 +47,8 @@ CONFOCAL_MULTI_SYMBOLS = ("l2o_confocal_unroll_multi", "l2o_confocal_unroll_mult
                           "l2o_confocal_unroll_multi_supported", "l2o_confocal_unroll_multi_scratch_floats")
 # ... and include/l2o_mlp_hvp_abi.h (the Hessian-vector product of the MLP optimizee: second_derivatives=True on problems.mnist)
 MLP_HVP_SYMBOLS = ("l2o_mlp_hvp", "l2o_mlp_hvp_scratch_floats")
+# ... and include/l2o_vgg16_abi.h (problems.vgg16_cifar10); bound when the library has them
+VGG16_SYMBOLS = ("l2o_vgg16_fg", "l2o_vgg16_scratch_floats")
 
 
 # option ids of include/l2o_abi.h ("options": per call, caller-owned -- the LIBRARY keeps no option state since ABI v9).
@@ -226,10 +229,18 @@ class MlpInstance(C.Structure):        # l2o_mlp_instance: one replica of l2o_ml
                 ("v", C.c_void_p * 4), ("x_scale", C.c_void_p * 4), ("fx", C.c_void_p)]
 
 
+class Vgg16(C.Structure):
+    """struct l2o_vgg16 (include/l2o_vgg16_abi.h)"""
+    _fields_ = [("batch", C.c_int32), ("n_data", C.c_int32), ("flags", C.c_int32), ("channels", C.c_int32 * 5),
+                ("images", C.c_void_p), ("labels", C.c_void_p)]
+
+
 # the step-path optimizees: (descriptor struct, symbol stem).  Every one exports <stem>_scratch_floats(const struct *) ->
 # size_t and <stem>_fg(const struct *, 6 pointers) -> int: lib() declares both from this list
 STEP_FG = ((MlpDeep, "l2o_mlp_deep"), (MnistConv, "l2o_mnist_conv"), (CifarConv, "l2o_cifar_conv"), (Lenet, "l2o_lenet"),
            (Confocal, "l2o_confocal"))
+# ... and those added after ABI v15 (the same two exports per stem), declared when the library has them
+STEP_FG_LATER = ((Vgg16, "l2o_vgg16"),)
 
 
 class GenNet(C.Structure):
@@ -307,7 +318,7 @@ def source_build_id():
     csrc = os.path.join(_HERE, "csrc")
     names = ["l2o_kernels.hip", "l2o_kernels_ilp.hip", "Makefile", "../../include/l2o_abi.h",
              "../../include/l2o_confocal_unroll_abi.h", "../../include/l2o_confocal_multi_abi.h",
-             "../../include/l2o_mlp_hvp_abi.h"] + [
+             "../../include/l2o_mlp_hvp_abi.h", "../../include/l2o_vgg16_abi.h"] + [
         os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.h"))]
     h = hashlib.sha256()
     try:
@@ -412,7 +423,7 @@ def lib():
     L.l2o_mlp_unroll_record.restype = C.c_int
     L.l2o_mlp_unroll_record.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Mlp), vp, vp, vp, vp, vp, vp, i32, i32, vp,
                                         C.POINTER(MlpHist), vp, vp]
-    for struct, stem in STEP_FG:
+    for struct, stem in STEP_FG + tuple(e for e in STEP_FG_LATER if hasattr(L, e[1] + "_fg")):
         floats, fg = getattr(L, stem + "_scratch_floats"), getattr(L, stem + "_fg")
         floats.restype, floats.argtypes = C.c_size_t, [C.POINTER(struct)]
         fg.restype, fg.argtypes = C.c_int, [C.POINTER(struct)] + [vp] * 6

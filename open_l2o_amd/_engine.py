@@ -116,6 +116,16 @@ class LenetDesc(ImageNetDesc):
 
 
 @dataclasses.dataclass
+class Vgg16Desc:
+    """Device-side view of problems.vgg16_cifar10 (struct l2o_vgg16): images [n_data, 3072] (32x32x3) and the widths of the
+    five blocks."""
+    batch: int
+    channels: tuple           # five multiples of 8 in [8, 512]; the reference: (64, 128, 256, 512, 512)
+    images: torch.Tensor
+    labels: torch.Tensor
+
+
+@dataclasses.dataclass
 class ConfocalDesc:
     """Device-side view of problems.confocal_microscopy_3d (struct l2o_confocal)."""
     batch: int
@@ -142,7 +152,13 @@ STEP_OPTIMIZEES = {
     _abi.PROB_CONFOCAL: StepOptimizee("confocal_fg", ConfocalDesc, _abi.Confocal, "l2o_confocal", "_confocal_scratch",
                                       lambda d: 6 * d.num_points + 1, False),
 }
-_ENTRY_OF_METHOD = {entry.method: entry for entry in STEP_OPTIMIZEES.values()}
+# ... and the kinds added since that table's keys were pinned (tests/test_step_optimizees_cpu.py): the same entry type.
+# ALL_STEP_OPTIMIZEES, the union, is what the graph and meta.py look a term's kind up in.
+LATER_STEP_OPTIMIZEES = {
+    _abi.PROB_VGG16: StepOptimizee("vgg16_fg", Vgg16Desc, _abi.Vgg16, "l2o_vgg16", "_vgg16_scratch", lambda d: 28, True),
+}
+ALL_STEP_OPTIMIZEES = {**STEP_OPTIMIZEES, **LATER_STEP_OPTIMIZEES}
+_ENTRY_OF_METHOD = {entry.method: entry for entry in ALL_STEP_OPTIMIZEES.values()}
 
 
 def _ptr(t):
@@ -456,6 +472,27 @@ class HipEngine(object):
     def lenet_fg(self, d: LenetDesc, indices, ws, loss, grads):
         """problems.LeNet (l2o_lenet_fg): 14 variables with batch norm, 10 without."""
         self._image_net_fg("lenet_fg", d, indices, ws, loss, grads)
+
+    def vgg16_fg(self, d: Vgg16Desc, indices, ws, loss, grads):
+        """problems.vgg16_cifar10 (l2o_vgg16_fg): 28 variables -- weights and biases of the 13 conv layers, then of fc.  ws /
+        grads: lists of device tensors in the graph's variable order (grads may be None: forward only)."""
+        entry = _ENTRY_OF_METHOD["vgg16_fg"]
+        if not hasattr(self.lib, "l2o_vgg16_fg"):
+            raise RuntimeError("libl2o_hip.so has no l2o_vgg16_fg: rebuild it (make -C open_l2o_amd/csrc)")
+        c = entry.struct()
+        c.batch, c.n_data, c.flags = d.batch, int(d.images.shape[0]), 0
+        channels = tuple(int(n) for n in d.channels)
+        for k, n in enumerate(channels[:5]):
+            c.channels[k] = n
+        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
+        scr = self._step_scratch(entry, c) if len(channels) == 5 else None
+        if scr is None:
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_vgg16_fg: unsupported minibatch %d or channels %r"
+                                      % (d.batch, channels))
+        if len(ws) != entry.nvars(d) or (grads is not None and len(grads) != len(ws)):
+            raise ValueError("l2o_vgg16_fg: %d variables (it takes %d)" % (len(ws), entry.nvars(d)))
+        _abi.check(self.lib.l2o_vgg16_fg(C.byref(c), C.c_void_p(indices.data_ptr()), _ptr_array(ws), _ptr(loss),
+                                         _ptr_array(grads), _ptr(scr), self._stream()))
 
     def confocal_fg(self, d: ConfocalDesc, theta, sim, loss, grads):
         """Loss and gradients of the confocal optimizee (l2o_confocal_fg).  theta / sim / grads: lists of 6 num_points + 1

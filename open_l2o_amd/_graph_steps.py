@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _abi, networks
-from ._engine import STEP_OPTIMIZEES, MlpDesc
+from ._engine import ALL_STEP_OPTIMIZEES, STEP_OPTIMIZEES, MlpDesc
 from ._graph_core import PackedState, _DevGrad, _LazyHost, _term_vars, _world, rng  # noqa: F401
 
 # the optimizees that are ONE term over several variables, evaluated by an entry point of their own with the random x-scaling
@@ -18,6 +18,10 @@ from ._graph_core import PackedState, _DevGrad, _LazyHost, _term_vars, _world, r
 # of them that draw a minibatch per evaluation (all but the last)
 _MULTIVAR = tuple(sorted(STEP_OPTIMIZEES))
 _SAMPLED = tuple(k for k in _MULTIVAR if STEP_OPTIMIZEES[k].sampled)
+# ... and the same two tuples over every kind, the later additions (problems.vgg16_cifar10) included: what the graph and
+# meta.py test a term's kind against (the two above keep the values tests/test_step_optimizees_cpu.py pins)
+MULTIVAR_KINDS = tuple(sorted(ALL_STEP_OPTIMIZEES))
+SAMPLED_KINDS = tuple(k for k in MULTIVAR_KINDS if ALL_STEP_OPTIMIZEES[k].sampled)
 
 # the optimizees that also have a fused unroll -- the T steps in ONE launch: the term's problem kind, the engine's
 # single-launch method (<method>_supported answers for a (net, descriptor) pair) and the kind's own conditions on the graph
@@ -266,7 +270,7 @@ class StepPlanMixin(object):
         if self.__dict__.get("_reuse_minibatches") and bufs:
             return                                          # (recovery re-run of an unroll: the minibatches it drew)
         for k, term in enumerate(self.terms):
-            if term.kind not in _SAMPLED:
+            if term.kind not in SAMPLED_KINDS:
                 continue
             d = self._mlp_desc(term)
             sampler = term.hyper.get("sampler")
@@ -290,7 +294,7 @@ class StepPlanMixin(object):
         """The engine's descriptor of a step-path term (the class its STEP_OPTIMIZEES entry names; MlpDesc for problems.mnist
         with one hidden layer), its data set uploaded once per (images object, batch, batch_norm)."""
         cache = self.__dict__.setdefault("_mlp_cache", {})
-        entry, hyper, eng = STEP_OPTIMIZEES[term.kind], term.hyper, self.engine
+        entry, hyper, eng = ALL_STEP_OPTIMIZEES[term.kind], term.hyper, self.engine
         if term.kind == _abi.PROB_CONFOCAL:                    # no data set: one descriptor per term
             key = (id(term), "confocal")
             if key not in cache:
@@ -299,9 +303,12 @@ class StepPlanMixin(object):
                                                roi=tuple(hyper["roi"]), img=None if img is None else eng.tensor(img)))
             return cache[key][1]
         if term.kind != _abi.PROB_MLP:                         # the image nets
-            key = (id(hyper["images"]), entry.stem, hyper["batch_size"], hyper["batch_norm"])
+            # what tells two descriptors of one data set apart: batch norm, or (vgg16, which has none) the block widths
+            variant = {"channels": tuple(hyper["channels"])} if "channels" in hyper else \
+                {"batch_norm": bool(hyper["batch_norm"])}
+            key = (id(hyper["images"]), entry.stem, hyper["batch_size"]) + tuple(variant.values())
             if key not in cache:
-                cache[key] = entry.desc(batch=int(hyper["batch_size"]), batch_norm=bool(hyper["batch_norm"]),
+                cache[key] = entry.desc(batch=int(hyper["batch_size"]), **variant,
                                         images=eng.tensor(np.ascontiguousarray(hyper["images"], np.float32)),
                                         labels=eng.int_tensor(hyper["labels"]))
             return cache[key]
@@ -320,7 +327,7 @@ class StepPlanMixin(object):
     def _step_fg(self, k, term, js):
         """fg(t, xin, out, grads): one evaluation of the step-path term number k over the variables js.  The engine method
         and the descriptor are resolved here, once per unroll; per step there is only the call."""
-        eng, d, entry = self.engine, self._mlp_desc(term), STEP_OPTIMIZEES[term.kind]
+        eng, d, entry = self.engine, self._mlp_desc(term), ALL_STEP_OPTIMIZEES[term.kind]
         if term.kind == _abi.PROB_MLP and len(js) == 4:        # one hidden layer: l2o_mlp_fg takes w1, b1, w2, b2
             call, idx = eng.mlp_fg, self._mlp_idx[k]
             return lambda t, xin, out, grads: call(d, idx[t], *xin, out, grads)
@@ -348,13 +355,13 @@ class StepPlanMixin(object):
         # the step-path terms: their variables and their evaluation, bound once per unroll
         step_terms = {}
         for k, term in enumerate(self.terms):
-            if term.kind in _MULTIVAR:
+            if term.kind in MULTIVAR_KINDS:
                 js = [index_of[tv.name] for tv in _term_vars(term)]
                 step_terms[k] = (js, self._step_fg(k, term, js))
         # one analytic term of weight 1: the per-problem losses of all T+1 steps are kept and
         # reduced over the batch by ONE launch at the end (like the fused path) instead of a
         # tiny reduction kernel per step
-        defer = single and self.terms[0].kind not in _MULTIVAR
+        defer = single and self.terms[0].kind not in MULTIVAR_KINDS
         if defer:
             jd = index_of[self.terms[0].var.name]
             f_all = self._scratch("f_all", (T + 1) * descs[jd].B_local)

@@ -35,6 +35,7 @@
 #include "l2o_mnist_conv.h"
 #include "l2o_cifar_conv.h"
 #include "l2o_lenet.h"
+#include "l2o_vgg16.h"
 #include "l2o_confocal.h"
 #include "l2o_confocal_unroll.h"
 #include "l2o_generic.h"
@@ -1256,6 +1257,120 @@ int l2o_lenet_fg(const l2o_lenet* m, const int32_t* indices, const float* const*
   }
   const long nthreads = g ? kLnGradThreads : 1;
   hipLaunchKernelGGL(k_ln_grad, dim3((unsigned)((nthreads + kLnThreads - 1) / kLnThreads)), blk, 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return L2O_OK;
+}
+
+// ---- problems.vgg16_cifar10 (csrc/l2o_vgg16.h, include/l2o_vgg16_abi.h) -------------------------------------------------
+static bool vgg16_ok(const l2o_vgg16* m) {
+  if (!m || m->batch < 2 || m->batch > kVgMaxBatch || m->n_data < 1) return false;
+  for (int b = 0; b < 5; ++b)
+    if (m->channels[b] < 8 || m->channels[b] > 512 || m->channels[b] % 8) return false;
+  return true;
+}
+// The scratch of one call, in floats from its start: the gathered images, the output of every conv layer and of pools 1-4,
+// pool 5's output, dz, the per-sample losses, two gradient buffers of the largest activation and the weight-gradient
+// partials.  Every size is a multiple of 4 floats.
+struct VgScratch {
+  size_t x0, act[kVgLayers], pool[4], pooled, dz, loss_s, grad[2], part, total;
+};
+static VgScratch vgg16_scratch(const l2o_vgg16* m, const VgLayer* L) {
+  VgScratch s;
+  const size_t B = (size_t)m->batch;
+  size_t p = 0, gmax = 0, pmax = 0;
+  auto take = [&](size_t n) { const size_t at = p; p += (n + 3) & ~(size_t)3; return at; };
+  s.x0 = take(B * 3072);
+  int np = 0;
+  for (int l = 0; l < kVgLayers; ++l) {
+    const size_t n = (B << (2 * L[l].lw)) * L[l].cout;
+    s.act[l] = take(n);
+    if (L[l].pool && l != kVgLayers - 1) s.pool[np++] = take(n / 4);
+    if (n > gmax) gmax = n;
+    int per;
+    const size_t pn = (size_t)vg_wgrad_splits(m->batch, L[l], &per) * (9 * L[l].cin + 1) * L[l].cout;
+    if (pn > pmax) pmax = pn;
+  }
+  s.pooled = take(B * m->channels[4]);
+  s.dz = take(B * 16);
+  s.loss_s = take(B);
+  s.grad[0] = take(gmax);
+  s.grad[1] = take(gmax);
+  s.part = take(pmax);
+  s.total = p;
+  return s;
+}
+size_t l2o_vgg16_scratch_floats(const l2o_vgg16* m) {
+  if (!vgg16_ok(m)) return 0;
+  VgLayer L[kVgLayers];
+  vg_plan(m->channels, L);
+  return vgg16_scratch(m, L).total;
+}
+int l2o_vgg16_fg(const l2o_vgg16* m, const int32_t* indices, const float* const* w, float* loss, float* const* g,
+                 float* scratch, void* stream) {
+  if (!vgg16_ok(m))
+    return fail(L2O_ERR_UNSUPPORTED, "l2o_vgg16_fg: batch in [2, %d], channels multiples of 8 in [8, 512], n_data >= 1",
+                kVgMaxBatch);
+  if (!indices || !w || !loss || !scratch || !m->images || !m->labels) return fail(L2O_ERR_ARG, "l2o_vgg16_fg: NULL argument");
+  if ((uintptr_t)scratch & 15) return fail(L2O_ERR_ARG, "l2o_vgg16_fg: scratch must be 16-byte aligned");
+  for (int k = 0; k < L2O_VGG16_VARS; ++k)
+    if (!w[k] || (g && !g[k])) return fail(L2O_ERR_ARG, "l2o_vgg16_fg: NULL buffer of variable %d", k);
+  VgLayer L[kVgLayers];
+  vg_plan(m->channels, L);
+  const VgScratch sc = vgg16_scratch(m, L);
+  hipStream_t s = (hipStream_t)stream;
+  const int B = m->batch;
+  const dim3 blk(kVgThreads);
+  auto blocks = [](size_t n) { return dim3((unsigned)((n + kVgThreads - 1) / kVgThreads)); };
+  auto tiles = [](int n, int t) { return (unsigned)((n + t - 1) / t); };
+  // ---- forward
+  hipLaunchKernelGGL(k_vg_gather, dim3(B), blk, 0, s, m->images, indices, m->n_data, scratch + sc.x0);
+  const float* in[kVgLayers];                  // the input of every conv layer
+  const float* x = scratch + sc.x0;
+  int np = 0;
+  for (int l = 0; l < kVgLayers; ++l) {
+    const int M = B << (2 * L[l].lw);
+    in[l] = x;
+    VgGemm a{x, w[2 * l], w[2 * l + 1], scratch + sc.act[l], M, L[l].lw, L[l].cin, L[l].cout, 0};
+    hipLaunchKernelGGL(k_vg_gemm<VG_FWD>, dim3(tiles(M, kVgBM), tiles(L[l].cout, kVgBN)), blk, 0, s, a);
+    x = scratch + sc.act[l];
+    if (L[l].pool && l != kVgLayers - 1) {
+      const size_t total = (size_t)(M / 4) * L[l].cout;
+      hipLaunchKernelGGL(k_vg_pool, blocks(total), blk, 0, s, x, scratch + sc.pool[np], L[l].lw, L[l].cout, total);
+      x = scratch + sc.pool[np++];
+    }
+  }
+  float* dy = scratch + sc.grad[0];            // gradient w.r.t. the pre-activation of the layer in hand
+  float* other = scratch + sc.grad[1];
+  VgHead h;
+  std::memset(&h, 0, sizeof(h));
+  h.a13 = scratch + sc.act[kVgLayers - 1]; h.wfc = w[26]; h.bfc = w[27]; h.labels = m->labels; h.idx = indices;
+  h.pooled = scratch + sc.pooled; h.dz = scratch + sc.dz; h.loss_s = scratch + sc.loss_s; h.dy13 = g ? dy : nullptr;
+  h.loss = loss; h.gwfc = g ? g[26] : nullptr; h.gbfc = g ? g[27] : nullptr;
+  h.B = B; h.C = m->channels[4]; h.n_data = m->n_data;
+  hipLaunchKernelGGL(k_vg_head, dim3(B), dim3(64), 0, s, h);
+  hipLaunchKernelGGL(k_vg_head_sum, dim3(g ? 1 + tiles(h.C * kVgClasses + kVgClasses, kVgThreads) : 1), blk, 0, s, h);
+  // ---- backward: per layer the weight (and bias) gradient, then the gradient w.r.t. its input, masked by the ReLU of the
+  // layer below -- directly, or on the way back through the pool between them
+  for (int l = kVgLayers - 1; g && l >= 0; --l) {
+    const int M = B << (2 * L[l].lw), K9 = 9 * L[l].cin;
+    int per;
+    const int splits = vg_wgrad_splits(B, L[l], &per);
+    VgGemm a{in[l], dy, nullptr, scratch + sc.part, M, L[l].lw, L[l].cin, L[l].cout, per};
+    hipLaunchKernelGGL(k_vg_gemm<VG_WGRAD>, dim3(tiles(K9, kVgBM), tiles(L[l].cout, kVgBN), splits), blk, 0, s, a);
+    hipLaunchKernelGGL(k_vg_wsum, blocks((size_t)(K9 + 1) * L[l].cout), blk, 0, s, scratch + sc.part, splits,
+                       K9 * L[l].cout, L[l].cout, g[2 * l], g[2 * l + 1]);
+    if (l == 0) break;
+    const bool pooled_input = L[l - 1].pool != 0;
+    VgGemm d{dy, w[2 * l], pooled_input ? nullptr : in[l], other, M, L[l].lw, L[l].cin, L[l].cout, 0};
+    hipLaunchKernelGGL(k_vg_gemm<VG_DGRAD>, dim3(tiles(M, kVgBM), tiles(L[l].cin, kVgBN)), blk, 0, s, d);
+    if (pooled_input) {
+      const size_t total = (size_t)M * L[l].cin;
+      hipLaunchKernelGGL(k_vg_pool_bwd, blocks(total), blk, 0, s, scratch + sc.act[l - 1], other, dy, L[l - 1].lw, L[l].cin,
+                         total);
+    } else {
+      std::swap(dy, other);
+    }
+  }
   HIP_TRY(hipGetLastError());
   return L2O_OK;
 }

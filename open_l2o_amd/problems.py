@@ -575,6 +575,53 @@ def confocal_microscopy_3d(batch_size=128, num_points=5, ROI=[28, 28, 28], stdde
     return _Build("confocal_microscopy_3d", build)
 
 
+def vgg16_cifar10(path, batch_norm=False, batch_size=128, num_threads=4, min_queue_examples=1000, mode="train", data=None,
+                  sampler=None, channels=(64, 128, 256, 512, 512)):
+    """Cifar10 classification with VGG-16.  DM/problems.py:637-694 and DM/vgg16.py:44-98, as util.get_config("vgg16")
+    (DM/util.py:192-197) calls it.
+
+    Five blocks of (2, 2, 3, 3, 3) layers of widths ``channels``, each layer conv 3x3 stride 1 SAME + bias -> ReLU, each
+    block closed by max-pool 2x2 stride 2 (32 -> 16 -> 8 -> 4 -> 2 -> 1) -> flatten (512) -> linear 512x10 + bias ->
+    softmax -> mean softmax cross-entropy that takes those PROBABILITIES as its logits (the reference's quirk):
+    loss = mean_b -log softmax(p_b)[label_b] with p_b = softmax(z_b), which lies in about [1.46, 2.46].  The reference has
+    commented its two hidden fc layers and their dropouts out, and nothing reads its ``batch_norm``, ``is_training`` or
+    ``keep_prob``: ``batch_norm`` is accepted for the reference's signature and has no effect.  Conv and fc weights are
+    drawn from N(0, 0.01^2), the conv biases are 0 and ``fc/biases`` is the constant 1.0.  Forward and gradient:
+    l2o_vgg16_fg (the step-granular path; no fused unroll; first-order meta-gradients only).
+
+    ``channels`` (an extension): the widths of the five blocks, each a multiple of 8 in [8, 512]; the default is the
+    reference's net, 14 719 818 coordinates in 28 variables.  The data and the minibatches come as in :func:`cifar10`;
+    ``num_threads`` and ``min_queue_examples`` are accepted for the reference's signature and have no effect."""
+    del batch_norm, num_threads, min_queue_examples
+    try:
+        channels = tuple(int(c) for c in channels)
+    except TypeError:
+        channels = (channels,)
+    if len(channels) != 5 or any(c % 8 or not 8 <= c <= 512 for c in channels):
+        raise NotImplementedError("problems.vgg16_cifar10 is implemented for five channels, each a multiple of 8 in [8, 512] "
+                                  "(got channels=%r)" % (channels,))
+    if data is None:
+        data = _load_cifar10(path, mode)
+    images, labels = _image_net_data("vgg16_cifar10", (32, 32, 3), data, batch_size)
+
+    def build():
+        w = random_normal_initializer(stddev=0.01)
+        vs, c_in = [], 3
+        for b, (layers, c_out) in enumerate(zip((2, 2, 3, 3, 3), channels)):
+            for i in range(layers):
+                name = "block%d_conv%d" % (b + 1, i + 1)
+                vs += [get_variable(name + "/weights", [3, 3, c_in, c_out], initializer=w),
+                       get_variable(name + "/biases", [c_out], initializer=zeros_initializer())]
+                c_in = c_out
+        vs += [get_variable("fc/weights", [c_in, 10], initializer=w),
+               get_variable("fc/biases", [10], initializer=ones_initializer())]
+        term, = _image_net_term(_abi.PROB_VGG16, vs, images, labels, batch_size, False, sampler)
+        term.hyper["channels"] = channels
+        return [term]
+
+    return _Build("vgg16_cifar10", build)
+
+
 def _not_on_hot_path(name, where):
     def factory(*args, **kwargs):
         raise NotImplementedError(
@@ -590,4 +637,3 @@ def _not_on_hot_path(name, where):
 # reference's own cifar10 does not take
 cifar_multi = _not_on_hot_path("cifar10(conv_channels=..., linear_layers=...)", "DM/util.py:212")
 NAS = _not_on_hot_path("NAS", "DM/problems.py:540")
-vgg16_cifar10 = _not_on_hot_path("vgg16_cifar10", "DM/problems.py:637")

@@ -215,12 +215,16 @@ def get_config(problem_name, path=None, mode=None, num_hidden_layer=None, net_na
         problem = problems.confocal_microscopy_3d(**with_defaults(batch_size=32, num_points=5))
         net_config = _cw2020(path)
         net_assignments = None
-    elif problem_name in ("nas",
-                          "vgg16", "cifar-multi"):
+    elif problem_name == "vgg16":                                        # DM/util.py:192-197
+        if mode is None:
+            mode = "train" if path is None else "test"
+        problem = problems.vgg16_cifar10("cifar10", **with_defaults(mode=mode))
+        net_config = {"cw": get_default_net_config(path)}
+        net_assignments = None
+    elif problem_name in ("nas", "cifar-multi"):
         # neural-network / data-dependent optimizees of DM/util.py:144-230: the net config is
         # reproduced, the problem factory raises (out of the accelerated hot path).
-        problem = getattr(problems, {"nas": "NAS", "vgg16": "vgg16_cifar10",
-                                     "cifar-multi": "cifar_multi"}[problem_name])()
+        problem = getattr(problems, {"nas": "NAS", "cifar-multi": "cifar_multi"}[problem_name])()
         net_config = {"cw": get_default_net_config(path)}
         net_assignments = None
     else:

@@ -39,7 +39,10 @@ def main():
     flags.add_argument("--synthetic_mnist", type=int, default=0,
                        help="problems.mnist on N synthetic MNIST-shaped examples (no dataset ships offline)")
     flags.add_argument("--synthetic_cifar10", type=int, default=0,
-                       help="problems.cifar10 on N synthetic CIFAR-10-shaped examples (no dataset ships offline)")
+                       help="problems.cifar10 / LeNet / vgg16_cifar10 on N synthetic CIFAR-10-shaped examples (no dataset ships offline)")
+    flags.add_argument("--vgg16_channels", default=None,
+                       help="(ours) --problem vgg16: the widths of the five blocks, comma-separated multiples of 8 in [8, 512] "
+                            "(problems.vgg16_cifar10(channels=...); the reference's net is 64,128,256,512,512)")
     flags.add_argument("--replicas", type=int, default=1,
                        help="(ours) evaluate this many independent instances of the optimizee TOGETHER (own initial weights, "
                             "own minibatches; problems.mnist with one hidden layer of 20 at --batch_size 64 or 128 (the "
@@ -60,6 +63,8 @@ def main():
     if FLAGS.synthetic_cifar10:
         from open_l2o_amd import problems
         opts["data"] = problems.synthetic_cifar10(FLAGS.synthetic_cifar10)
+    if FLAGS.vgg16_channels:
+        opts["channels"] = tuple(int(c) for c in FLAGS.vgg16_channels.split(","))
     problem, net_config, net_assignments = util.get_config(FLAGS.problem, FLAGS.path, problem_options=opts)
 
     if FLAGS.optimizer == "L2L":

@@ -13,6 +13,10 @@
   * confocal with ``--fused 1 --replicas N``: nothing but N fused unrolls as ONE launch (replicas.Replicas, form "rows":
     rows_step_us_per_instance) against the same N replicas as N single fused launches (the yardstick:
     single_step_us_per_instance) -- us per optimizer step per instance, the median of 10 event-timed rounds each;
+  * vgg16: three runs in one process of fg_us (l2o_vgg16_fg), the float32 torch-autograd yardstick (conv2d / max_pool2d of
+    the installed torch: MIOpen and rocBLAS, which may pick Winograd) and step_us (fg, 28 l2o_cwlstm_step launches and the
+    minibatch draw), at the reference's widths unless ``--channels`` narrows them; ``--loop N`` runs N bare evaluations and
+    one short unroll and nothing else, for a kernel trace;
   * mnist with ``--hvp 1``: us per l2o_mlp_hvp (784-20-10, the Hessian-vector product of second_derivatives=True) against
     l2o_mlp_deep_fg of the same shape and against the same H u through float32 torch double backward on the same GPU, three
     event-timed runs each; and one meta_minimize train step at --unroll steps with and without second_derivatives, and with
@@ -22,6 +26,8 @@
     python scripts/step_bench.py --problem {mnist_conv,cifar_conv,lenet} [--batch 128] [--iters 200] [--unroll 20] [--unrolls 10]
     python scripts/step_bench.py --problem confocal [--batch 32] [--points 5] [--roi 28] [--iters 500] [--unroll 20] [--fused 1]
                                  [--unrolls 10] [--loop N] [--replicas N]
+    python scripts/step_bench.py --problem vgg16 [--batch 128] [--channels 64,128,256,512,512] [--iters 20] [--unroll 5]
+                                 [--unrolls 3] [--loop N]
     python scripts/step_bench.py --problem mnist --hvp 1 [--batch 128] [--iters 200] [--unroll 20] [--unrolls 10]
 
 Prints one JSON line.  The image nets run on synthetic data (problems.synthetic_mnist / synthetic_cifar10); the arithmetic
@@ -148,6 +154,70 @@ def image_net_main(eng, a):
     step_us, graph = time_step(a.problem, {"data": data, "batch_size": a.batch}, a.unroll, a.unrolls)
     return {"workload": a.problem, "batch": a.batch, "coordinates": sum(int(np.prod(v.shape)) for v in graph.x),
             "fg_us": round(fg_us, 2), **yardstick, "step_us": round(step_us, 2), "unroll": a.unroll, "path": graph.last_path,
+            "device": torch.cuda.get_device_name(0)}
+
+
+# -- vgg16 -------------------------------------------------------------------------------------------------------------
+def vgg16_shapes(channels):
+    shapes, c_in = [], 3
+    for n, c in zip((2, 2, 3, 3, 3), channels):
+        for _ in range(n):
+            shapes += [(3, 3, c_in, c), (c,)]
+            c_in = c
+    return shapes + [(c_in, 10), (10,)]
+
+
+def vgg16_torch(x, y, w, iters):
+    """VGG-16 through float32 torch autograd on the GPU."""
+    dev = torch.device("cuda")
+    x = torch.tensor(x, device=dev).reshape(-1, 32, 32, 3).permute(0, 3, 1, 2).contiguous()
+    y = torch.tensor(y, device=dev, dtype=torch.int64)
+    vs = [torch.tensor(a, device=dev).requires_grad_(True) for a in w]
+    out = {}
+
+    def fg():
+        h, k = x, 0
+        for n in (2, 2, 3, 3, 3):
+            for _ in range(n):
+                h = F.relu(F.conv2d(h, vs[k].permute(3, 2, 0, 1), vs[k + 1], padding=1))
+                k += 2
+            h = F.max_pool2d(h, 2)
+        z = h.reshape(h.shape[0], -1) @ vs[26] + vs[27]
+        loss = F.cross_entropy(F.softmax(z, dim=1), y)
+        out["loss"], out["grads"] = loss, torch.autograd.grad(loss, vs)
+
+    us = _timed(fg, iters, warmup=5)
+    return us, float(out["loss"])
+
+
+def vgg16_main(eng, a):
+    channels = tuple(int(c) for c in a.channels.split(","))
+    shapes = vgg16_shapes(channels)
+    data = problems.synthetic_cifar10(4096, seed=0)
+    images = np.ascontiguousarray(data["images"], np.float32).reshape(len(data["labels"]), -1)
+    d = _engine.Vgg16Desc(a.batch, channels, eng.tensor(images), eng.int_tensor(data["labels"]))
+    rng = np.random.default_rng(0)
+    rows = rng.integers(0, len(images), a.batch)
+    idx = eng.int_tensor(rows)
+    # O(1) activations (at the reference's initialisation the float32 logits are exactly the bias): He-scaled weights
+    w = [rng.normal(0, math.sqrt(2.0 / (9 * sh[2])) if len(sh) == 4 else (1.0 / math.sqrt(sh[0]) if len(sh) == 2 else 0.1),
+                    sh).astype(np.float32) for sh in shapes]
+    ws, grads, loss = [eng.tensor(t) for t in w], [eng.zeros(*sh) for sh in shapes], eng.zeros(1)
+    fg = functools.partial(eng.vgg16_fg, d, idx, ws, loss, grads)
+    options = {"data": data, "batch_size": a.batch, "channels": channels}
+    if a.loop:
+        fg_us = _timed(fg, a.loop, warmup=2)
+        step_us, _ = time_step("vgg16", options, 2, 1, warmup=1)
+        return {"workload": "vgg16", "loop": a.loop, "fg_us": round(fg_us, 2), "step_us": round(step_us, 2)}
+    runs = []
+    for _ in range(3):
+        fg_us = _timed(fg, a.iters, warmup=3)
+        torch_us, torch_loss = vgg16_torch(images[rows], np.asarray(data["labels"])[rows], w, a.iters)
+        step_us, graph = time_step("vgg16", options, a.unroll, a.unrolls, warmup=1)
+        runs.append({"fg_us": round(fg_us, 2), "torch_autograd_fg_us": round(torch_us, 2), "step_us": round(step_us, 2)})
+    return {"workload": "vgg16", "batch": a.batch, "channels": list(channels),
+            "coordinates": sum(int(np.prod(v.shape)) for v in graph.x), "runs": runs,
+            "loss": float(eng.to_numpy(loss)[0]), "torch_loss": torch_loss, "unroll": a.unroll, "path": graph.last_path,
             "device": torch.cuda.get_device_name(0)}
 
 
@@ -361,30 +431,33 @@ def mnist_hvp_main(eng, a):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--problem", required=True, choices=list(IMAGE_NETS) + ["confocal", "mnist"])
+    p.add_argument("--problem", required=True, choices=list(IMAGE_NETS) + ["vgg16", "confocal", "mnist"])
     p.add_argument("--hvp", type=int, choices=(0, 1), default=0,
                    help="mnist: time l2o_mlp_hvp against l2o_mlp_deep_fg and torch double backward, and the train step")
     p.add_argument("--batch", type=int, help="default: 128; confocal: 32")
     p.add_argument("--iters", type=int, help="default: 200; confocal: 500")
-    p.add_argument("--unroll", type=int, default=20)
-    p.add_argument("--unrolls", type=int, default=10)
+    p.add_argument("--unroll", type=int, help="default: 20; vgg16: 5")
+    p.add_argument("--unrolls", type=int, help="default: 10; vgg16: 3")
+    p.add_argument("--channels", default="64,128,256,512,512", help="vgg16: the widths of the five blocks")
     p.add_argument("--points", type=int, default=5, help="confocal")
     p.add_argument("--roi", type=int, default=28, help="confocal")
     p.add_argument("--fused", type=int, choices=(0, 1), default=0,
                    help="confocal: 1 also times the fused unroll (fused_step_us) beside the step path (step_us)")
-    p.add_argument("--loop", type=int, default=0, help="confocal: only run this many bare evaluations (for a kernel trace)")
+    p.add_argument("--loop", type=int, default=0, help="confocal, vgg16: only run this many bare evaluations (for a kernel trace)")
     p.add_argument("--replicas", type=int, default=0,
                    help="confocal, with --fused 1: time N fused unrolls as one launch against N single launches, nothing else")
     a = p.parse_args()
     confocal = a.problem == "confocal"
     a.batch = a.batch or (32 if confocal else 128)
-    a.iters = a.iters or (500 if confocal else 200)
+    a.iters = a.iters or (500 if confocal else 20 if a.problem == "vgg16" else 200)
+    a.unroll = a.unroll or (5 if a.problem == "vgg16" else 20)
+    a.unrolls = a.unrolls or (3 if a.problem == "vgg16" else 10)
     if a.problem == "mnist" and not a.hvp:
         raise SystemExit("step_bench: --problem mnist measures the Hessian-vector product: give --hvp 1")
     eng = _engine.HipEngine()
     _engine.set_default_engine(eng)
     meta.set_random_seed(0)
-    run = confocal_main if confocal else (mnist_hvp_main if a.problem == "mnist" else image_net_main)
+    run = confocal_main if confocal else {"mnist": mnist_hvp_main, "vgg16": vgg16_main}.get(a.problem, image_net_main)
     print(json.dumps(run(eng, a)))
 
 

@@ -1,0 +1,312 @@
+"""problems.vgg16_cifar10 (DM/problems.py:637-694, DM/vgg16.py, util.get_config("vgg16")) without a GPU: the variables the
+factory declares, its refusals and the missing-data error, the float64 reference's own correctness (central differences),
+the library's new symbols and scratch sizes, the companion table of later step-path kinds, and the host wiring -- meta_loss
+/ meta_minimize over the net on an oracle engine whose vgg16_fg is the float32 torch reference (vgg16_reference.py)."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import oracle as O
+import vgg16_reference as R
+from helpers import make_params, rel_err
+from oracle_engine import OracleEngine
+from open_l2o_amd import _abi, _engine, _graph_steps, meta, meta_rnnprop_eval, problems, util
+from open_l2o_amd.session import Session
+from test_meta_api import _net_config
+from test_training_gradient import GRAD_TOL
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NARROW = R.NARROW_CHANNELS
+
+
+class Vgg16OracleEngine(OracleEngine):
+    """The oracle engine plus VGG-16's loss and gradient from the float32 torch reference."""
+
+    def vgg16_fg(self, d, indices, ws, loss, grads):
+        self.calls.append("vgg16_fg")
+        net = R.Vgg16(d.images.numpy(), d.labels.numpy(), d.channels)
+        vs = [w.numpy().reshape(sh) for w, sh in zip(ws, R.shapes(d.channels))]
+        f, g = net.fg(vs, indices.numpy(), want_grad=grads is not None)
+        loss.copy_(torch.from_numpy(np.array([f], np.float32)))
+        if grads is not None:
+            for t, a in zip(grads, g):
+                t.copy_(torch.from_numpy(np.ascontiguousarray(a, np.float32)).view_as(t))
+
+
+@pytest.fixture
+def engine():
+    eng = Vgg16OracleEngine()
+    old = _engine._default_engine
+    _engine.set_default_engine(eng)
+    yield eng
+    _engine.set_default_engine(old)
+
+
+def _data(n=64, seed=0):
+    return problems.synthetic_cifar10(n, seed=seed)
+
+
+# 1. the factory
+def test_variables_names_shapes_order_initialisers():
+    loss = problems.vgg16_cifar10("cifar10", data=_data())()
+    assert [v.name for v in loss.variables] == R.names()
+    assert [tuple(v.shape) for v in loss.variables] == R.shapes()
+    assert len(loss.variables) == 28 and all(v.trainable for v in loss.variables)
+    assert sum(int(np.prod(v.shape)) for v in loss.variables) == 14719818
+    assert loss.variables[0].name == "block1_conv1/weights" and tuple(loss.variables[0].shape) == (3, 3, 3, 64)
+    assert loss.variables[24].name == "block5_conv3/weights" and tuple(loss.variables[24].shape) == (3, 3, 512, 512)
+    assert loss.variables[26].name == "fc/weights" and tuple(loss.variables[26].shape) == (512, 10)
+    for v in loss.variables:
+        if v.name == "fc/biases":
+            assert v.initializer == ("ones",)
+        elif v.name.endswith("biases"):
+            assert v.initializer == ("zeros",), v.name
+        else:
+            assert v.initializer == ("normal", 0.0, 0.01), v.name
+    (term,) = loss.terms
+    assert term.kind == _abi.PROB_VGG16 == 10 and term.hyper["batch_size"] == 128
+    assert term.hyper["channels"] == (64, 128, 256, 512, 512) and term.hyper["images"].shape == (64, 3072)
+    # batch_norm is accepted and changes nothing
+    other = problems.vgg16_cifar10("cifar10", batch_norm=True, data=_data())()
+    assert [v.name for v in other.variables] == R.names() and other.terms[0].hyper["batch_norm"] is False
+    narrow = problems.vgg16_cifar10("cifar10", data=_data(), channels=NARROW, batch_size=2)()
+    assert [tuple(v.shape) for v in narrow.variables] == R.shapes(NARROW)
+
+
+def test_refusals():
+    data = _data(8)
+    for channels in ((8, 16, 24, 40, 70), (4, 16, 24, 40, 72), (0, 16, 24, 40, 72), (8, 16, 24, 40, 520),
+                     (8, 16, 24, 40), (8, 16, 24, 40, 72, 72), 64):
+        with pytest.raises(NotImplementedError) as ei:
+            problems.vgg16_cifar10("cifar10", data=data, channels=channels)
+        assert str(ei.value).startswith("problems.vgg16_cifar10 is implemented for five channels, each a multiple of 8 in "
+                                        "[8, 512] (got channels=")
+    for batch in (1, 1025):
+        with pytest.raises(NotImplementedError) as ei:
+            problems.vgg16_cifar10("cifar10", data=data, batch_size=batch)
+        assert str(ei.value) == "problems.vgg16_cifar10 is implemented for minibatches of 2 to 1024 (got %d)" % batch
+    bad = {"images": np.zeros((8, 5, 5, 2), np.float32), "labels": data["labels"]}
+    with pytest.raises(ValueError) as ei:
+        problems.vgg16_cifar10("cifar10", data=bad)
+    assert str(ei.value) == "problems.vgg16_cifar10 takes 32x32x3 images (got (8, 5, 5, 2))"
+    problems.vgg16_cifar10("cifar10", data=data, batch_size=2, channels=[8, 8, 8, 8, 8])
+    problems.vgg16_cifar10("cifar10", data=data, batch_size=1024, channels=(512,) * 5)
+
+
+def test_missing_data_error(tmp_path, monkeypatch):
+    monkeypatch.delenv("L2O_CIFAR10_DIR", raising=False)
+    monkeypatch.chdir(tmp_path)
+    for make in (lambda: util.get_config("vgg16"), lambda: problems.vgg16_cifar10("cifar10")):
+        with pytest.raises(FileNotFoundError) as ei:
+            make()
+        assert isinstance(ei.value, NotImplementedError) and isinstance(ei.value, problems.Cifar10DataMissing)
+        assert "L2O_CIFAR10_DIR" in str(ei.value)
+
+
+# 2. util.get_config
+def test_get_config():
+    problem, net_config, na = util.get_config("vgg16", problem_options={"data": _data()})
+    loss = problem()
+    assert [v.name for v in loss.variables] == R.names() and loss.terms[0].hyper["batch_size"] == 128
+    assert loss.terms[0].kind == _abi.PROB_VGG16
+    assert net_config["cw"]["net_options"]["preprocess_name"] == "LogAndSign" and na is None
+    problem, net_config, _ = util.get_config("vgg16", net_name="RNNprop",
+                                             problem_options={"data": _data(), "batch_size": 16, "channels": NARROW})
+    assert "rp" in net_config and problem().terms[0].hyper["batch_size"] == 16
+    assert [tuple(v.shape) for v in problem().variables] == R.shapes(NARROW)
+
+
+# 3. the companion table
+def test_later_kinds_table():
+    """The pinned table keeps its five kinds; vgg16 lives in the companion table, with the same entry type, and everything
+    that looks a kind up reads the union."""
+    assert sorted(_engine.STEP_OPTIMIZEES) == [5, 6, 7, 8, 9] and sorted(_engine.LATER_STEP_OPTIMIZEES) == [10]
+    assert sorted(_engine.ALL_STEP_OPTIMIZEES) == [5, 6, 7, 8, 9, 10]
+    e = _engine.LATER_STEP_OPTIMIZEES[_abi.PROB_VGG16]
+    assert type(e) is _engine.StepOptimizee
+    assert (e.method, e.stem, e.scratch, e.sampled) == ("vgg16_fg", "l2o_vgg16", "_vgg16_scratch", True)
+    assert e.desc is _engine.Vgg16Desc and e.struct is _abi.Vgg16 and (e.struct, e.stem) in _abi.STEP_FG_LATER
+    assert e.nvars(_engine.Vgg16Desc(2, NARROW, None, None)) == 28
+    assert _engine._ENTRY_OF_METHOD["vgg16_fg"] is e and callable(_engine.HipEngine.vgg16_fg)
+    assert _graph_steps._MULTIVAR == (5, 6, 7, 8, 9) and _graph_steps._SAMPLED == (5, 6, 7, 8)
+    assert _graph_steps.MULTIVAR_KINDS == (5, 6, 7, 8, 9, 10) and _graph_steps.SAMPLED_KINDS == (5, 6, 7, 8, 10)
+    assert C.sizeof(_abi.Vgg16) == 48 and _abi.Vgg16.__doc__.startswith("struct l2o_vgg16")
+
+
+# 4. the float64 reference itself
+def test_reference_central_differences():
+    """The float64 reference's gradient against central differences on a few coordinates of every variable, at O(1)
+    activations.  (Not at the reference's initialisation: the pre-activations there are of the order 1e-8 deep in the net,
+    so any step a difference can resolve crosses ReLU kinks.)"""
+    d = _data(16, seed=3)
+    net = R.Vgg16(d["images"], d["labels"], NARROW)
+    w = [a.astype(np.float64) for a in R.sample_weights(NARROW, 5)]
+    rng = np.random.default_rng(4)
+    rows = rng.integers(0, 16, 3)
+    f, g = net.fg(w, rows)
+    assert np.isfinite(f) and 1.46 < f < 2.47
+    h = 1e-6
+    for k, a in enumerate(w):
+        gmax = np.abs(g[k]).max()
+        assert gmax > 0, R.names()[k]
+        for j in rng.choice(a.size, size=min(3, a.size), replace=False):
+            wp = [b.copy() for b in w]
+            wm = [b.copy() for b in w]
+            wp[k].reshape(-1)[j] += h
+            wm[k].reshape(-1)[j] -= h
+            num = (net.fg(wp, rows, want_grad=False)[0] - net.fg(wm, rows, want_grad=False)[0]) / (2 * h)
+            assert abs(num - g[k].reshape(-1)[j]) < 1e-5 * max(gmax, 1e-3) + 1e-8, (R.names()[k], j, num)
+
+
+def test_reference_at_the_initialisation():
+    """At the reference's initialisation the signal shrinks by about 6e-8 through the thirteen layers: the float32 logits
+    are exactly fc/biases and the loss exactly log 10, while every gradient block is non-zero and far above float32
+    subnormals."""
+    d = _data(16, seed=3)
+    net = R.Vgg16(d["images"], d["labels"], NARROW)
+    w = R.init_weights(NARROW, 5)
+    f32, g32 = net.fg(w, np.arange(3))
+    assert np.array_equal(net.last_logits, np.ones((3, 10), np.float32)) and f32 == np.float32(math.log(10))
+    f64, g64 = net.fg([a.astype(np.float64) for a in w], np.arange(3))
+    assert abs(f64 - math.log(10)) < 1e-6
+    for nm, a in zip(R.names(), g64):
+        assert np.abs(a).max() > 1e-30, nm
+
+
+def test_float32_reference_within_a_third_of_the_bound():
+    """The bound the GPU tests hold the kernels to is GRAD_TOL of a block's largest float64 entry unless the float32
+    reference is itself further off than a third of that: it is not, at either weight scale."""
+    d = _data(64, seed=6)
+    net = R.Vgg16(d["images"], d["labels"], NARROW)
+    rows = np.random.default_rng(7).integers(0, 64, 3)
+    for make in (R.sample_weights, R.init_weights):
+        w = make(NARROW, 8)
+        f64, g64 = net.fg([a.astype(np.float64) for a in w], rows)
+        f32, g32 = net.fg(w, rows)
+        assert abs(f32 - f64) <= 1e-5 / 3 * abs(f64)
+        for nm, a, b in zip(R.names(), g32, g64):
+            assert np.abs(a - b).max() <= GRAD_TOL / 3 * np.abs(b).max(), nm
+
+
+# 5. the library
+def test_library_symbols_header_and_scratch():
+    import __graft_entry__  # noqa: F401
+    lib = _abi.lib()
+    with open(os.path.join(ROOT, "include", "l2o_vgg16_abi.h")) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    declared = set(re.findall(r"\b(l2o_\w+)\s*\(", text))
+    assert declared == set(_abi.VGG16_SYMBOLS) and len(_abi.VGG16_SYMBOLS) == 2
+    others = _abi.SYMBOLS + _abi.CONFOCAL_UNROLL_SYMBOLS + _abi.CONFOCAL_MULTI_SYMBOLS + _abi.MLP_HVP_SYMBOLS
+    assert not set(_abi.VGG16_SYMBOLS) & set(others)
+    for name in _abi.VGG16_SYMBOLS:
+        getattr(lib, name)
+    assert lib.l2o_abi_version() == 15 == _abi.L2O_ABI_VERSION and len(_abi.SYMBOLS) == 66
+    assert _abi.source_build_id() == _abi.build_id()
+    assert lib.l2o_vgg16_scratch_floats.restype is C.c_size_t and lib.l2o_vgg16_fg.argtypes == [C.POINTER(_abi.Vgg16)] + \
+        [C.c_void_p] * 6
+    m = _abi.Vgg16()
+    m.n_data = 100
+
+    def floats(batch, channels):
+        m.batch = batch
+        for k in range(5):
+            m.channels[k] = channels[k]
+        return int(lib.l2o_vgg16_scratch_floats(C.byref(m)))
+
+    for batch, ok in ((1, False), (2, True), (128, True), (1024, True), (1025, False)):
+        assert (floats(batch, NARROW) > 0) == ok, batch
+    for channels in ((8, 16, 24, 40, 70), (0, 16, 24, 40, 72), (8, 16, 24, 40, 520), (4, 8, 8, 8, 8)):
+        assert floats(2, channels) == 0, channels
+    sizes = [floats(b, NARROW) for b in (2, 3, 37, 128, 1024)]
+    assert sizes == sorted(set(sizes))
+    ref = [floats(b, R.REFERENCE_CHANNELS) for b in (2, 128, 1024)]
+    assert ref == sorted(set(ref)) and ref[0] > sizes[0]
+    # what a sample needs at the least: its image, every layer's output and two gradient buffers of the largest one
+    per_sample = 3072 + 2 * 65536 + 16384 + 2 * 32768 + 8192 + 3 * 16384 + 4096 + 3 * 8192 + 2048 + 3 * 2048 + 512 + 2 * 65536
+    assert ref[1] >= 128 * per_sample and ref[1] < 128 * per_sample * 1.5
+    assert floats(128, R.REFERENCE_CHANNELS) and lib.l2o_vgg16_fg(C.byref(m), None, None, None, None, None, None) == \
+        _abi.L2O_ERR_ARG
+    for batch in (1, 1025):
+        m.batch = batch
+        assert lib.l2o_vgg16_fg(C.byref(m), None, None, None, None, None, None) == _abi.L2O_ERR_UNSUPPORTED
+
+
+# 6. host wiring
+def _sampler(idx):
+    calls = {"n": 0}
+
+    def sampler(n_evals, b, n_data):
+        out = idx[calls["n"]:calls["n"] + n_evals]
+        calls["n"] += n_evals
+        return out
+    return sampler
+
+
+@pytest.mark.parametrize("net", ["dm_logsign", "rnnprop"])
+def test_meta_loss_wiring(engine, net):
+    """meta_loss over util.get_config("vgg16") at narrow widths on the step-granular path == the oracle's multi-variable
+    unroll over the same float32 evaluations, two chained unrolls."""
+    data = _data(32, seed=7)
+    T, batch = 2, 4
+    idx = np.random.default_rng(8).integers(0, 32, size=(2 * (T + 1), batch))
+    cfg = O.DM_LOGSIGN if net == "dm_logsign" else O.RNNPROP
+    params = make_params(cfg, seed=9, trained_like=True)
+    meta.set_random_seed(10)
+    problem = util.get_config("vgg16", problem_options={"data": data, "batch_size": batch, "channels": NARROW,
+                                                        "sampler": _sampler(idx)})[0]
+    feeds = [{}, {}]
+    if cfg.kind == "rnnprop":
+        optimizer = meta_rnnprop_eval.MetaOptimizer(0.95, 0.95, **_net_config(cfg, params, key="rp"))
+        ml, _, _, step = optimizer.meta_loss(problem, T)
+        feeds = [{step: 1}, {step: 1 + T}]
+    else:
+        optimizer = meta.MetaOptimizer(**_net_config(cfg, params))
+        ml = optimizer.meta_loss(problem, T)
+    with Session() as sess:
+        sess.run(ml.reset)
+        v0 = [v.eval() for v in optimizer.graph.x]
+        assert [tuple(a.shape) for a in v0] == R.shapes(NARROW)
+        assert np.array_equal(v0[27], np.ones(10, np.float32)) and not v0[1].any() and v0[0].any()
+        loss1, fx1, _ = sess.run([ml.loss, ml.fx, ml.update], feed_dict=feeds[0])
+        loss2, fx2, x2, _ = sess.run([ml.loss, ml.fx, ml.x, ml.update], feed_dict=feeds[1])
+    assert optimizer.graph.last_path == "steps"
+    assert engine.calls.count("vgg16_fg") == 2 * (T + 1)
+    ref = R.Vgg16(data["images"], data["labels"], NARROW)
+    states = [O.net_initial_state(cfg, a.size) for a in v0]
+    if cfg.kind == "rnnprop":
+        fx_a, va, sa, ma, va2 = O.unroll_multi(lambda vs, t, wg: ref.fg(vs, idx[t], wg), cfg, params, v0, states, T,
+                                               return_moments=True)
+        fx_b, vb, _ = O.unroll_multi(lambda vs, t, wg: ref.fg(vs, idx[T + 1 + t], wg), cfg, params, va, sa, T, ms=ma,
+                                     vs=va2, step0=1 + T)
+    else:
+        fx_a, va, sa = O.unroll_multi(lambda vs, t, wg: ref.fg(vs, idx[t], wg), cfg, params, v0, states, T)
+        fx_b, vb, _ = O.unroll_multi(lambda vs, t, wg: ref.fg(vs, idx[T + 1 + t], wg), cfg, params, va, sa, T)
+    assert rel_err(fx1, fx_a[-1]) < 1e-5 and rel_err(loss1, fx_a.sum()) < 1e-5
+    assert rel_err(fx2, fx_b[-1]) < 1e-5 and rel_err(loss2, fx_b.sum()) < 1e-5
+    for got, want in zip(x2, vb):
+        np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-7)
+
+
+def test_meta_minimize_and_refusals(engine):
+    """One first-order training step on the narrow net runs on the recording step path; second derivatives refuse it."""
+    data = _data(32, seed=11)
+    meta.set_random_seed(12)
+    opt = meta.MetaOptimizer(**_net_config(O.DM_LOGSIGN, make_params(O.DM_LOGSIGN, seed=13, trained_like=True)))
+    problem = problems.vgg16_cifar10("cifar10", batch_size=4, data=data, channels=NARROW)
+    ms = opt.meta_minimize(problem, 2, learning_rate=1e-3)
+    w0 = {m: {v: np.array(a) for v, a in d.items()} for m, d in opt._nets["cw"].variables.items()}
+    with Session() as sess:
+        sess.run(ms.reset)
+        c1 = sess.run([ms.fx, ms.update, ms.step])[0]
+    assert np.isfinite(c1) and opt.graph.last_path == "steps"
+    assert "vgg16_fg" in engine.calls
+    w1 = opt._nets["cw"].variables
+    assert any(not np.array_equal(w0[m][v], np.asarray(w1[m][v])) for m in w0 for v in w0[m])
+    opt2 = meta.MetaOptimizer(**_net_config(O.DM_LOGSIGN, make_params(O.DM_LOGSIGN, seed=13, trained_like=True)))
+    with pytest.raises(NotImplementedError, match="second_derivatives"):
+        opt2.meta_minimize(problem, 2, learning_rate=1e-3, second_derivatives=True)
