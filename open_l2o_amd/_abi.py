@@ -25,6 +25,7 @@ PROB_CIFAR_CONV = 7
 PROB_LENET = 8
 PROB_CONFOCAL = 9
 PROB_VGG16 = 10           # include/l2o_vgg16_abi.h (added after ABI v15)
+PROB_NAS = 11             # include/l2o_nas_abi.h (added after ABI v15)
 
 # every symbol include/l2o_abi.h declares (tests check the library exports all of them)
 SYMBOLS = (
@@ -49,6 +50,8 @@ CONFOCAL_MULTI_SYMBOLS = ("l2o_confocal_unroll_multi", "l2o_confocal_unroll_mult
 MLP_HVP_SYMBOLS = ("l2o_mlp_hvp", "l2o_mlp_hvp_scratch_floats")
 # ... and include/l2o_vgg16_abi.h (problems.vgg16_cifar10); bound when the library has them
 VGG16_SYMBOLS = ("l2o_vgg16_fg", "l2o_vgg16_scratch_floats")
+# ... and include/l2o_nas_abi.h (problems.NAS); bound when the library has them
+NAS_SYMBOLS = ("l2o_nas_fg", "l2o_nas_scratch_floats")
 
 
 # option ids of include/l2o_abi.h ("options": per call, caller-owned -- the LIBRARY keeps no option state since ABI v9).
@@ -202,6 +205,10 @@ class Lenet(ImageNet):
     """struct l2o_lenet"""
 
 
+class Nas(ImageNet):
+    """struct l2o_nas (include/l2o_nas_abi.h)"""
+
+
 class Confocal(C.Structure):
     """struct l2o_confocal"""
     _fields_ = [("batch", C.c_int32), ("num_points", C.c_int32), ("roi", C.c_int32 * 3), ("inference", C.c_int32),
@@ -241,6 +248,9 @@ STEP_FG = ((MlpDeep, "l2o_mlp_deep"), (MnistConv, "l2o_mnist_conv"), (CifarConv,
            (Confocal, "l2o_confocal"))
 # ... and those added after ABI v15 (the same two exports per stem), declared when the library has them
 STEP_FG_LATER = ((Vgg16, "l2o_vgg16"),)
+# ... and the OPEN list of every (struct, stem) pair declared that way: a new step-path optimizee appends its pair here and
+# nothing else in this module changes
+STEP_FG_OPEN = list(STEP_FG_LATER) + [(Nas, "l2o_nas")]
 
 
 class GenNet(C.Structure):
@@ -318,7 +328,7 @@ def source_build_id():
     csrc = os.path.join(_HERE, "csrc")
     names = ["l2o_kernels.hip", "l2o_kernels_ilp.hip", "Makefile", "../../include/l2o_abi.h",
              "../../include/l2o_confocal_unroll_abi.h", "../../include/l2o_confocal_multi_abi.h",
-             "../../include/l2o_mlp_hvp_abi.h", "../../include/l2o_vgg16_abi.h"] + [
+             "../../include/l2o_mlp_hvp_abi.h", "../../include/l2o_vgg16_abi.h", "../../include/l2o_nas_abi.h"] + [
         os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.h"))]
     h = hashlib.sha256()
     try:
@@ -423,7 +433,7 @@ def lib():
     L.l2o_mlp_unroll_record.restype = C.c_int
     L.l2o_mlp_unroll_record.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Mlp), vp, vp, vp, vp, vp, vp, i32, i32, vp,
                                         C.POINTER(MlpHist), vp, vp]
-    for struct, stem in STEP_FG + tuple(e for e in STEP_FG_LATER if hasattr(L, e[1] + "_fg")):
+    for struct, stem in STEP_FG + tuple(e for e in STEP_FG_OPEN if hasattr(L, e[1] + "_fg")):
         floats, fg = getattr(L, stem + "_scratch_floats"), getattr(L, stem + "_fg")
         floats.restype, floats.argtypes = C.c_size_t, [C.POINTER(struct)]
         fg.restype, fg.argtypes = C.c_int, [C.POINTER(struct)] + [vp] * 6

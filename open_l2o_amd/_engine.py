@@ -115,6 +115,10 @@ class LenetDesc(ImageNetDesc):
     """problems.LeNet (struct l2o_lenet): images [n_data, 3072] (32x32x3)"""
 
 
+class NasDesc(ImageNetDesc):
+    """problems.NAS (struct l2o_nas): images [n_data, 3072] (32x32x3)"""
+
+
 @dataclasses.dataclass
 class Vgg16Desc:
     """Device-side view of problems.vgg16_cifar10 (struct l2o_vgg16): images [n_data, 3072] (32x32x3) and the widths of the
@@ -153,12 +157,22 @@ STEP_OPTIMIZEES = {
                                       lambda d: 6 * d.num_points + 1, False),
 }
 # ... and the kinds added since that table's keys were pinned (tests/test_step_optimizees_cpu.py): the same entry type.
-# ALL_STEP_OPTIMIZEES, the union, is what the graph and meta.py look a term's kind up in.
+# ALL_STEP_OPTIMIZEES is the union; both are values that tests pin (tests/test_vgg16_cpu.py) and get no new entries.
 LATER_STEP_OPTIMIZEES = {
     _abi.PROB_VGG16: StepOptimizee("vgg16_fg", Vgg16Desc, _abi.Vgg16, "l2o_vgg16", "_vgg16_scratch", lambda d: 28, True),
 }
 ALL_STEP_OPTIMIZEES = {**STEP_OPTIMIZEES, **LATER_STEP_OPTIMIZEES}
-_ENTRY_OF_METHOD = {entry.method: entry for entry in ALL_STEP_OPTIMIZEES.values()}
+# The OPEN table: every step-path kind, the pinned ones and whatever came after them.  A new kind adds ONE entry here (and
+# its (struct, stem) pair to _abi.STEP_FG_OPEN); the graph and meta.py ask step_optimizee(kind) and never a literal table.
+STEP_REGISTRY = dict(ALL_STEP_OPTIMIZEES)
+STEP_REGISTRY[_abi.PROB_NAS] = StepOptimizee("nas_fg", NasDesc, _abi.Nas, "l2o_nas", "_nas_scratch",
+                                             lambda d: 18 if d.batch_norm else 10, True)
+_ENTRY_OF_METHOD = {entry.method: entry for entry in STEP_REGISTRY.values()}
+
+
+def step_optimizee(kind):
+    """The registry entry of a problem kind, or None where the kind is not a step-path optimizee."""
+    return STEP_REGISTRY.get(kind)
 
 
 def _ptr(t):
@@ -472,6 +486,10 @@ class HipEngine(object):
     def lenet_fg(self, d: LenetDesc, indices, ws, loss, grads):
         """problems.LeNet (l2o_lenet_fg): 14 variables with batch norm, 10 without."""
         self._image_net_fg("lenet_fg", d, indices, ws, loss, grads)
+
+    def nas_fg(self, d: NasDesc, indices, ws, loss, grads):
+        """problems.NAS (l2o_nas_fg): 18 variables with batch norm, 10 without."""
+        self._image_net_fg("nas_fg", d, indices, ws, loss, grads)
 
     def vgg16_fg(self, d: Vgg16Desc, indices, ws, loss, grads):
         """problems.vgg16_cifar10 (l2o_vgg16_fg): 28 variables -- weights and biases of the 13 conv layers, then of fc.  ws /

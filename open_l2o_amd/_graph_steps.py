@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _abi, networks
-from ._engine import ALL_STEP_OPTIMIZEES, STEP_OPTIMIZEES, MlpDesc
+from ._engine import ALL_STEP_OPTIMIZEES, STEP_OPTIMIZEES, MlpDesc, step_optimizee
 from ._graph_core import PackedState, _DevGrad, _LazyHost, _term_vars, _world, rng  # noqa: F401
 
 # the optimizees that are ONE term over several variables, evaluated by an entry point of their own with the random x-scaling
@@ -22,6 +22,19 @@ _SAMPLED = tuple(k for k in _MULTIVAR if STEP_OPTIMIZEES[k].sampled)
 # meta.py test a term's kind against (the two above keep the values tests/test_step_optimizees_cpu.py pins)
 MULTIVAR_KINDS = tuple(sorted(ALL_STEP_OPTIMIZEES))
 SAMPLED_KINDS = tuple(k for k in MULTIVAR_KINDS if ALL_STEP_OPTIMIZEES[k].sampled)
+
+
+# The four tuples above are values that tests pin; the graph and meta.py ask these two instead, which go over the open
+# registry (_engine.STEP_REGISTRY): a kind added there is a step-path optimizee everywhere, with no table to extend.
+def is_multivar(kind):
+    """True for a step-path optimizee: ONE term over several variables, evaluated by an entry point of its own."""
+    return step_optimizee(kind) is not None
+
+
+def is_sampled(kind):
+    """True for a step-path optimizee that draws a minibatch per evaluation."""
+    entry = step_optimizee(kind)
+    return entry is not None and entry.sampled
 
 # the optimizees that also have a fused unroll -- the T steps in ONE launch: the term's problem kind, the engine's
 # single-launch method (<method>_supported answers for a (net, descriptor) pair) and the kind's own conditions on the graph
@@ -270,7 +283,7 @@ class StepPlanMixin(object):
         if self.__dict__.get("_reuse_minibatches") and bufs:
             return                                          # (recovery re-run of an unroll: the minibatches it drew)
         for k, term in enumerate(self.terms):
-            if term.kind not in SAMPLED_KINDS:
+            if not is_sampled(term.kind):
                 continue
             d = self._mlp_desc(term)
             sampler = term.hyper.get("sampler")
@@ -294,7 +307,7 @@ class StepPlanMixin(object):
         """The engine's descriptor of a step-path term (the class its STEP_OPTIMIZEES entry names; MlpDesc for problems.mnist
         with one hidden layer), its data set uploaded once per (images object, batch, batch_norm)."""
         cache = self.__dict__.setdefault("_mlp_cache", {})
-        entry, hyper, eng = ALL_STEP_OPTIMIZEES[term.kind], term.hyper, self.engine
+        entry, hyper, eng = step_optimizee(term.kind), term.hyper, self.engine
         if term.kind == _abi.PROB_CONFOCAL:                    # no data set: one descriptor per term
             key = (id(term), "confocal")
             if key not in cache:
@@ -327,7 +340,7 @@ class StepPlanMixin(object):
     def _step_fg(self, k, term, js):
         """fg(t, xin, out, grads): one evaluation of the step-path term number k over the variables js.  The engine method
         and the descriptor are resolved here, once per unroll; per step there is only the call."""
-        eng, d, entry = self.engine, self._mlp_desc(term), ALL_STEP_OPTIMIZEES[term.kind]
+        eng, d, entry = self.engine, self._mlp_desc(term), step_optimizee(term.kind)
         if term.kind == _abi.PROB_MLP and len(js) == 4:        # one hidden layer: l2o_mlp_fg takes w1, b1, w2, b2
             call, idx = eng.mlp_fg, self._mlp_idx[k]
             return lambda t, xin, out, grads: call(d, idx[t], *xin, out, grads)
@@ -355,13 +368,13 @@ class StepPlanMixin(object):
         # the step-path terms: their variables and their evaluation, bound once per unroll
         step_terms = {}
         for k, term in enumerate(self.terms):
-            if term.kind in MULTIVAR_KINDS:
+            if is_multivar(term.kind):
                 js = [index_of[tv.name] for tv in _term_vars(term)]
                 step_terms[k] = (js, self._step_fg(k, term, js))
         # one analytic term of weight 1: the per-problem losses of all T+1 steps are kept and
         # reduced over the batch by ONE launch at the end (like the fused path) instead of a
         # tiny reduction kernel per step
-        defer = single and self.terms[0].kind not in MULTIVAR_KINDS
+        defer = single and not is_multivar(self.terms[0].kind)
         if defer:
             jd = index_of[self.terms[0].var.name]
             f_all = self._scratch("f_all", (T + 1) * descs[jd].B_local)

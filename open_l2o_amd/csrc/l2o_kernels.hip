@@ -36,6 +36,7 @@
 #include "l2o_cifar_conv.h"
 #include "l2o_lenet.h"
 #include "l2o_vgg16.h"
+#include "l2o_nas.h"
 #include "l2o_confocal.h"
 #include "l2o_confocal_unroll.h"
 #include "l2o_generic.h"
@@ -1369,6 +1370,161 @@ int l2o_vgg16_fg(const l2o_vgg16* m, const int32_t* indices, const float* const*
                          total);
     } else {
       std::swap(dy, other);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return L2O_OK;
+}
+
+// ---- problems.NAS (csrc/l2o_nas.h, include/l2o_nas_abi.h) ----------------------------------------------------------------
+static bool nas_ok(const l2o_nas* m) {
+  return m && m->batch >= 2 && m->batch <= kNsMaxBatch && m->n_data >= 1 && m->flags == 0 &&
+         (m->batch_norm == 0 || m->batch_norm == 1);
+}
+// The scratch of one call, in floats from its start (include/l2o_nas_abi.h has the formula).  Every size is a multiple of
+// 4 floats.
+struct NsScratch {
+  size_t x0, z0, zz, z13, dy1, dy0, P, stat, bsum, nf, dlog, v, loss_s, part, total;
+};
+static NsScratch nas_scratch(int batch) {
+  NsScratch s;
+  const size_t B = (size_t)batch, M = B * kNsPix;
+  size_t p = 0;
+  auto take = [&](size_t n) { const size_t at = p; p += (n + 3) & ~(size_t)3; return at; };
+  s.x0 = take(B * 3072);
+  s.z0 = take(M * 16);
+  s.zz = take(M * 32);
+  s.z13 = take(M * 16);
+  s.dy1 = take(M * 16);
+  s.dy0 = take(M * 16);
+  s.P = take(kNsLayers * kNsP);
+  s.stat = take(B * 64);
+  s.bsum = take(B * 64);
+  s.nf = take(B * 16);
+  s.dlog = take(B * 16);
+  s.v = take(B * 16);
+  s.loss_s = take(B);
+  s.part = take((size_t)ns_wgrad_groups(batch) * kNsWPart);
+  s.total = p;
+  return s;
+}
+size_t l2o_nas_scratch_floats(const l2o_nas* m) { return nas_ok(m) ? nas_scratch(m->batch).total : 0; }
+int l2o_nas_fg(const l2o_nas* m, const int32_t* indices, const float* const* w, float* loss, float* const* g, float* scratch,
+               void* stream) {
+  if (!nas_ok(m))
+    return fail(L2O_ERR_UNSUPPORTED, "l2o_nas_fg: batch in [2, %d], batch_norm 0 or 1, flags 0, n_data >= 1", kNsMaxBatch);
+  if (!indices || !w || !loss || !scratch || !m->images || !m->labels) return fail(L2O_ERR_ARG, "l2o_nas_fg: NULL argument");
+  if ((uintptr_t)scratch & 15) return fail(L2O_ERR_ARG, "l2o_nas_fg: scratch must be 16-byte aligned");
+  const int bn = m->batch_norm, per = bn ? 4 : 2, nvars = kNsLayers * per + 2;
+  for (int k = 0; k < nvars; ++k)
+    if (!w[k] || (g && !g[k])) return fail(L2O_ERR_ARG, "l2o_nas_fg: NULL buffer of variable %d", k);
+  const NsScratch sc = nas_scratch(m->batch);
+  hipStream_t s = (hipStream_t)stream;
+  const int B = m->batch;
+  const dim3 blk(kNsThreads), strips(4 * B), samples(B), one(1);
+  float* x0 = scratch + sc.x0;
+  float* z0 = scratch + sc.z0;
+  float* zz = scratch + sc.zz;           // [M][32]: n02 in columns 0-15, node1 in 16-31
+  float* z13 = scratch + sc.z13;
+  float* dy1 = scratch + sc.dy1;
+  float* dy0 = scratch + sc.dy0;
+  float* P = scratch + sc.P;
+  float* v = scratch + sc.v;
+  // layer l (node0, n02, node1, n13): its variables
+  auto W = [&](int l) { return w[l * per]; };
+  auto Bi = [&](int l) { return w[l * per + 1]; };
+  auto src = [](const float* z, int ldz, const float* dy, const float* Pl) { NsSrc r{z, dy, Pl, ldz}; return r; };
+  const NsSrc none = src(nullptr, 0, nullptr, nullptr);
+  // batch norm of layers l .. l + C / 16 - 1 whose z is the [M][C] array `z`
+  auto norm = [&](const float* z, int l, int C) {
+    if (!bn) return;
+    NsBn a{scratch + sc.stat, {w[l * per + 2], C == 32 ? w[(l + 1) * per + 2] : nullptr},
+           {w[l * per + 3], C == 32 ? w[(l + 1) * per + 3] : nullptr}, P + l * kNsP, B};
+    if (C == 32) {
+      hipLaunchKernelGGL(k_ns_stats<32>, samples, blk, 0, s, z, scratch + sc.stat);
+      hipLaunchKernelGGL(k_ns_bn<32>, one, blk, 0, s, a);
+    } else {
+      hipLaunchKernelGGL(k_ns_stats<16>, samples, blk, 0, s, z, scratch + sc.stat);
+      hipLaunchKernelGGL(k_ns_bn<16>, one, blk, 0, s, a);
+    }
+  };
+  // ---- forward
+  hipLaunchKernelGGL(k_vg_gather, samples, dim3(kVgThreads), 0, s, m->images, indices, m->n_data, x0);
+  if (!bn) hipLaunchKernelGGL(k_ns_identity, one, blk, 0, s, P);
+  {
+    NsConv a{{src(x0, 3, nullptr, nullptr), none}, v, {W(0), nullptr}, {Bi(0), nullptr}, z0, nullptr, nullptr, 0, 0};
+    hipLaunchKernelGGL((k_ns_conv<3, 16, NS_RAW>), strips, blk, 0, s, a);
+    norm(z0, 0, 16);
+  }
+  {
+    NsConv a{{src(z0, 16, nullptr, P), none}, v, {W(1), W(2)}, {Bi(1), Bi(2)}, zz, nullptr, nullptr, 0, 0};
+    hipLaunchKernelGGL((k_ns_conv<16, 32, NS_ACT>), strips, blk, 0, s, a);
+    norm(zz, 1, 32);
+  }
+  {
+    NsConv a{{src(zz + 16, 32, nullptr, P + 2 * kNsP), none}, v, {W(3), nullptr}, {Bi(3), nullptr}, z13, nullptr, nullptr, 0, 0};
+    hipLaunchKernelGGL((k_ns_conv<16, 16, NS_ACT>), strips, blk, 0, s, a);
+    norm(z13, 3, 16);
+  }
+  NsHead h;
+  std::memset(&h, 0, sizeof(h));
+  h.z0 = z0; h.zz = zz; h.z13 = z13; h.P = P; h.wfc = w[nvars - 2]; h.bfc = w[nvars - 1]; h.labels = m->labels; h.idx = indices;
+  h.nf = scratch + sc.nf; h.dlog = scratch + sc.dlog; h.v = v; h.loss_s = scratch + sc.loss_s; h.loss = loss;
+  h.gwfc = g ? g[nvars - 2] : nullptr; h.gbfc = g ? g[nvars - 1] : nullptr; h.B = B; h.n_data = m->n_data;
+  hipLaunchKernelGGL(k_ns_head, samples, blk, 0, s, h);
+  hipLaunchKernelGGL(k_ns_head_sum, one, blk, 0, s, h);
+  if (g) {
+    // ---- backward.  The sums of a layer (or of n02 and node1 together): the two means of its NsP block(s) and the
+    // gradients of gamma, beta and the bias
+    auto sums = [&](const NsSrc& s0, const NsSrc& s1, int l, int C) {
+      NsBwd a;
+      std::memset(&a, 0, sizeof(a));
+      a.src[0] = s0; a.src[1] = s1; a.v = v; a.part = scratch + sc.bsum; a.P = P + l * kNsP; a.B = B; a.bn = bn;
+      for (int i = 0; i < C / 16; ++i) {
+        a.gbias[i] = g[(l + i) * per + 1];
+        if (bn) { a.ggamma[i] = g[(l + i) * per + 2]; a.gbeta[i] = g[(l + i) * per + 3]; }
+      }
+      if (C == 32) {
+        hipLaunchKernelGGL(k_ns_bwd_sums<32>, samples, blk, 0, s, a);
+        hipLaunchKernelGGL(k_ns_bwd_fin<32>, one, blk, 0, s, a);
+      } else {
+        hipLaunchKernelGGL(k_ns_bwd_sums<16>, samples, blk, 0, s, a);
+        hipLaunchKernelGGL(k_ns_bwd_fin<16>, one, blk, 0, s, a);
+      }
+    };
+    const int groups = ns_wgrad_groups(B);
+    float* part = scratch + sc.part;
+    auto wsum = [&](int K, int NOUT, float* g0, float* g1) {
+      hipLaunchKernelGGL(k_ns_wsum, dim3((K * NOUT + kNsWsE - 1) / kNsWsE), blk, 0, s, part, groups, K, NOUT, g0, g1);
+    };
+    const NsSrc d13 = src(z13, 16, nullptr, P + 3 * kNsP);           // dy = u / 1024 under n13's mask
+    const NsSrc d02 = src(zz, 32, nullptr, P + 1 * kNsP);
+    const NsSrc d1 = src(zz + 16, 32, dy1, P + 2 * kNsP);
+    const NsSrc d0 = src(z0, 16, dy0, P);
+    // n13
+    sums(d13, none, 3, 16);
+    {
+      NsWgrad a{src(zz + 16, 32, nullptr, P + 2 * kNsP), {d13, none}, v, part, 4 * B};
+      hipLaunchKernelGGL((k_ns_wgrad<16, 16>), dim3(groups), blk, 0, s, a);
+      wsum(144, 16, g[3 * per], g[3 * per]);
+      NsConv c{{d13, none}, v, {W(3), nullptr}, {nullptr, nullptr}, dy1, zz + 16, P + 2 * kNsP, 32, 1};
+      hipLaunchKernelGGL((k_ns_conv<16, 16, NS_DZ>), strips, blk, 0, s, c);
+    }
+    // n02 and node1
+    sums(d02, d1, 1, 32);
+    {
+      NsWgrad a{src(z0, 16, nullptr, P), {d02, d1}, v, part, 4 * B};
+      hipLaunchKernelGGL((k_ns_wgrad<16, 32>), dim3(groups), blk, 0, s, a);
+      wsum(144, 32, g[1 * per], g[2 * per]);
+      NsConv c{{d02, d1}, v, {W(1), W(2)}, {nullptr, nullptr}, dy0, z0, P, 16, 0};
+      hipLaunchKernelGGL((k_ns_conv<32, 16, NS_DZ>), strips, blk, 0, s, c);
+    }
+    // node0
+    sums(d0, none, 0, 16);
+    {
+      NsWgrad a{src(x0, 3, nullptr, nullptr), {d0, none}, v, part, 4 * B};
+      hipLaunchKernelGGL((k_ns_wgrad<3, 16>), dim3(groups), blk, 0, s, a);
+      wsum(27, 16, g[0], g[0]);
     }
   }
   HIP_TRY(hipGetLastError());

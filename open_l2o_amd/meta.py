@@ -38,7 +38,7 @@ from ._graph_adam import AdamMixin
 from ._graph_bptt import BpttMixin
 from ._graph_core import (Fetch, Placeholder, Variable, PackedState, _make_nets, _DEFAULT_CONFIG, _DevGrad, _LazyHost,  # noqa: F401
                           _term_vars, _world, _all_reduce, synced_scale, local_slice, _Slot, set_random_seed, rng, _RngBox)
-from ._graph_steps import StepPlanMixin, SAMPLED_KINDS, MULTIVAR_KINDS
+from ._graph_steps import StepPlanMixin, is_sampled, is_multivar
 
 MetaLoss = collections.namedtuple("MetaLoss", "loss, update, reset, fx, x")     # DM/meta.py:158
 MetaStep = collections.namedtuple("MetaStep", "step, update, reset, fx, x")     # DM/meta.py:159
@@ -138,7 +138,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
     def _panel_shape(self, var):
         """[B_local, D] view of a variable for the kernels."""
         term = self.term_of[var.decl.name]
-        if term.kind == _abi.PROB_SIMPLE or term.kind in MULTIVAR_KINDS:   # (confocal: [batch, 1] -> one row of batch floats)
+        if term.kind == _abi.PROB_SIMPLE or is_multivar(term.kind):   # (confocal: [batch, 1] -> one row of batch floats)
             return 1, int(np.prod(var.shape)) if len(var.shape) else 1
         B = var.shape[0]
         if self.sharded:
@@ -337,7 +337,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
     def deterministic(self):
         """True when an unroll draws nothing at random (no minibatch sampling): then n committed unrolls
         of L steps are exactly one unroll of n * L steps."""
-        return all(t.kind not in SAMPLED_KINDS for t in self.terms)
+        return all(not is_sampled(t.kind) for t in self.terms)
 
     def execute_many(self, n):
         """n consecutive committed unrolls (what util.run_eval_epoch asks for with n sess.run calls,
@@ -502,7 +502,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
             ms.append(s.m if (commit or s.m is None) else s.m.clone())
             vs.append(s.v if (commit or s.v is None) else s.v.clone())
         # (a step-path optimizee has no descriptor: _run_steps evaluates it at x * scale, DM/meta_dm_train.py:384)
-        multivar = [self.term_of[v.decl.name].kind in MULTIVAR_KINDS for v in self.x]
+        multivar = [is_multivar(self.term_of[v.decl.name].kind) for v in self.x]
         descs = [None if mv else self._desc(v, sc) for v, sc, mv in zip(self.x, scales, multivar)]
         panels = [xv.view(*self._panel_shape(var)) for xv, var in zip(xs, self.x)]
         self._mlp_scales = [sc if mv else None for sc, mv in zip(scales, multivar)]
@@ -971,7 +971,7 @@ class MetaOptimizer(object):
         """What second_derivatives=True is implemented for, refused here -- at graph build, with the reason -- and not in
         the middle of the first train step: the analytic optimizees (l2o_problem_hvp) under any net the BPTT takes, and
         problems.mnist (l2o_mlp_hvp) when ALL its variables are stepped by ONE (20, 20) LSTM net."""
-        if any(t.kind in MULTIVAR_KINDS and t.kind != _abi.PROB_MLP for t in graph.terms):
+        if any(is_multivar(t.kind) and t.kind != _abi.PROB_MLP for t in graph.terms):
             raise NotImplementedError("second_derivatives=True is implemented for the analytic optimizees and problems.mnist "
                                       "(problems.mnist_conv / problems.cifar10 / problems.LeNet / "
                                       "problems.confocal_microscopy_3d have no Hessian-vector product)")

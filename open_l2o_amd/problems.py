@@ -622,6 +622,46 @@ def vgg16_cifar10(path, batch_norm=False, batch_size=128, num_threads=4, min_que
     return _Build("vgg16_cifar10", build)
 
 
+def NAS(path, batch_norm=True, batch_size=128, num_threads=4, min_queue_examples=1000, mode="train", data=None,
+        sampler=None):
+    """Cifar10 classification with a NAS cell.  DM/problems.py:540-634, as util.get_config("nas") (DM/util.py:185-190) calls
+    it.
+
+    With L(x) = relu([batch norm](conv 3x3 stride 1 SAME to 16 channels + bias)): node0 = L(image), n02 = L(node0), node1 =
+    L(node0), n13 = L(node1), node2 = avg_pool 3x3 stride 1 SAME (node1) + n02 (the pool divides by the number of valid
+    cells), node3 = node2 + n13 + node0 -> mean over the 1024 positions -> fc 16x10 -> ReLU (the reference's quirk) -> mean
+    softmax cross-entropy; batch norm as in :func:`mnist_conv`.  The variables, in the reference's creation order: per layer
+    (``node0``, ``node0_onto_node2``, ``node1``, ``node1_onto_node3``) ``weights1``, ``biases1`` and with batch norm
+    ``batch_normalization[_i]/gamma`` and ``beta``, then ``fc_weights`` and ``fc_bias``: 18 variables and 7 706 coordinates
+    with batch norm, 10 and 7 578 without.  Forward and gradient: l2o_nas_fg (the step-granular path; no fused unroll;
+    first-order meta-gradients only).
+
+    The data and the minibatches come as in :func:`cifar10`; ``num_threads`` and ``min_queue_examples`` are accepted for the
+    reference's signature and have no effect."""
+    del num_threads, min_queue_examples
+    if data is None:
+        data = _load_cifar10(path, mode)
+    images, labels = _image_net_data("NAS", (32, 32, 3), data, batch_size)
+    batch_norm = bool(batch_norm)
+
+    def build():
+        w = random_normal_initializer(stddev=0.01)
+        vs, c_in = [], 3
+        for i, name in enumerate(("node0", "node0_onto_node2", "node1", "node1_onto_node3")):
+            vs += [get_variable(name + "/weights1", [3, 3, c_in, 16], initializer=w),
+                   get_variable(name + "/biases1", [16], initializer=zeros_initializer())]
+            if batch_norm:
+                bn = "batch_normalization" + ("_%d" % i if i else "")
+                vs += [get_variable(bn + "/gamma", [16], initializer=ones_initializer()),
+                       get_variable(bn + "/beta", [16], initializer=zeros_initializer())]
+            c_in = 16
+        vs += [get_variable("fc_weights", [16, 10], initializer=w),
+               get_variable("fc_bias", [10], initializer=zeros_initializer())]
+        return _image_net_term(_abi.PROB_NAS, vs, images, labels, batch_size, batch_norm, sampler)
+
+    return _Build("NAS", build)
+
+
 def _not_on_hot_path(name, where):
     def factory(*args, **kwargs):
         raise NotImplementedError(
@@ -636,4 +676,3 @@ def _not_on_hot_path(name, where):
 # util.get_config("cifar-multi") (DM/util.py:212-230) calls cifar10 with conv_channels / linear_layers, which the
 # reference's own cifar10 does not take
 cifar_multi = _not_on_hot_path("cifar10(conv_channels=..., linear_layers=...)", "DM/util.py:212")
-NAS = _not_on_hot_path("NAS", "DM/problems.py:540")

@@ -221,10 +221,16 @@ def get_config(problem_name, path=None, mode=None, num_hidden_layer=None, net_na
         problem = problems.vgg16_cifar10("cifar10", **with_defaults(mode=mode))
         net_config = {"cw": get_default_net_config(path)}
         net_assignments = None
-    elif problem_name in ("nas", "cifar-multi"):
+    elif problem_name == "nas":                                          # DM/util.py:185-190
+        if mode is None:
+            mode = "train" if path is None else "test"
+        problem = problems.NAS("cifar10", **with_defaults(mode=mode))
+        net_config = {"cw": get_default_net_config(path)}
+        net_assignments = None
+    elif problem_name == "cifar-multi":
         # neural-network / data-dependent optimizees of DM/util.py:144-230: the net config is
         # reproduced, the problem factory raises (out of the accelerated hot path).
-        problem = getattr(problems, {"nas": "NAS", "cifar-multi": "cifar_multi"}[problem_name])()
+        problem = problems.cifar_multi()
         net_config = {"cw": get_default_net_config(path)}
         net_assignments = None
     else:

@@ -66,7 +66,7 @@ def parse_flags(rnnprop):
     p.add_argument("--synthetic_mnist", type=int, default=0,
                    help="problems.mnist on N synthetic MNIST-shaped examples (no dataset ships offline)")
     p.add_argument("--synthetic_cifar10", type=int, default=0,
-                   help="problems.cifar10 on N synthetic CIFAR-10-shaped examples (no dataset ships offline)")
+                   help="problems.cifar10 / LeNet / NAS on N synthetic CIFAR-10-shaped examples (no dataset ships offline)")
     p.add_argument("--synthetic_label_noise", type=float, default=0.0,
                    help="fraction of the synthetic labels re-drawn uniformly (problems.synthetic_mnist / synthetic_cifar10)")
     p.add_argument("--synthetic_seed", type=int, default=0)

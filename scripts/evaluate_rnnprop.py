@@ -34,7 +34,7 @@ def main():
     flags.add_argument("--synthetic_mnist", type=int, default=0,
                        help="problems.mnist on N synthetic MNIST-shaped examples (no dataset ships offline)")
     flags.add_argument("--synthetic_cifar10", type=int, default=0,
-                       help="problems.cifar10 / LeNet / vgg16_cifar10 on N synthetic CIFAR-10-shaped examples (no dataset ships offline)")
+                       help="problems.cifar10 / LeNet / NAS / vgg16_cifar10 on N synthetic CIFAR-10-shaped examples (no dataset ships offline)")
     flags.add_argument("--vgg16_channels", default=None,
                        help="(ours) --problem vgg16: the widths of the five blocks, comma-separated multiples of 8 in [8, 512] "
                             "(problems.vgg16_cifar10(channels=...); the reference's net is 64,128,256,512,512)")

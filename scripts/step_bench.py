@@ -17,6 +17,9 @@
     the installed torch: MIOpen and rocBLAS, which may pick Winograd) and step_us (fg, 28 l2o_cwlstm_step launches and the
     minibatch draw), at the reference's widths unless ``--channels`` narrows them; ``--loop N`` runs N bare evaluations and
     one short unroll and nothing else, for a kernel trace;
+  * nas: three runs in one process of fg_us (l2o_nas_fg), the float32 torch-autograd yardstick (conv2d,
+    avg_pool2d(count_include_pad=False) and batch norm by hand from var_mean) and step_us (fg, 18 l2o_cwlstm_step launches
+    and the minibatch draw); ``--loop N`` runs N bare evaluations and one short unroll and nothing else, for a kernel trace;
   * mnist with ``--hvp 1``: us per l2o_mlp_hvp (784-20-10, the Hessian-vector product of second_derivatives=True) against
     l2o_mlp_deep_fg of the same shape and against the same H u through float32 torch double backward on the same GPU, three
     event-timed runs each; and one meta_minimize train step at --unroll steps with and without second_derivatives, and with
@@ -28,6 +31,7 @@
                                  [--unrolls 10] [--loop N] [--replicas N]
     python scripts/step_bench.py --problem vgg16 [--batch 128] [--channels 64,128,256,512,512] [--iters 20] [--unroll 5]
                                  [--unrolls 3] [--loop N]
+    python scripts/step_bench.py --problem nas [--batch 128] [--iters 200] [--unroll 20] [--unrolls 10] [--loop N]
     python scripts/step_bench.py --problem mnist --hvp 1 [--batch 128] [--iters 200] [--unroll 20] [--unrolls 10]
 
 Prints one JSON line.  The image nets run on synthetic data (problems.synthetic_mnist / synthetic_cifar10); the arithmetic
@@ -217,6 +221,65 @@ def vgg16_main(eng, a):
         runs.append({"fg_us": round(fg_us, 2), "torch_autograd_fg_us": round(torch_us, 2), "step_us": round(step_us, 2)})
     return {"workload": "vgg16", "batch": a.batch, "channels": list(channels),
             "coordinates": sum(int(np.prod(v.shape)) for v in graph.x), "runs": runs,
+            "loss": float(eng.to_numpy(loss)[0]), "torch_loss": torch_loss, "unroll": a.unroll, "path": graph.last_path,
+            "device": torch.cuda.get_device_name(0)}
+
+
+# -- nas ---------------------------------------------------------------------------------------------------------------
+NAS_SHAPES = [sh for i in range(4) for sh in ((3, 3, 3 if i == 0 else 16, 16), (16,), (16,), (16,))] + [(16, 10), (10,)]
+
+
+def nas_torch(x, y, w, iters):
+    """The NAS cell with batch norm through float32 torch autograd on the GPU."""
+    dev = torch.device("cuda")
+    x = torch.tensor(x, device=dev).reshape(-1, 32, 32, 3).permute(0, 3, 1, 2).contiguous()
+    y = torch.tensor(y, device=dev, dtype=torch.int64)
+    vs = [torch.tensor(a, device=dev).requires_grad_(True) for a in w]
+    out = {}
+
+    def layer(h, k):                        # batch statistics, biased variance, eps 1e-3
+        z = F.conv2d(h, vs[k].permute(3, 2, 0, 1), vs[k + 1], padding=1)
+        var, mean = torch.var_mean(z, (0, 2, 3), unbiased=False, keepdim=True)
+        return F.relu((z - mean) * torch.rsqrt(var + 1e-3) * vs[k + 2].view(1, -1, 1, 1) + vs[k + 3].view(1, -1, 1, 1))
+
+    def fg():
+        node0 = layer(x, 0)
+        n02, node1 = layer(node0, 4), layer(node0, 8)
+        n13 = layer(node1, 12)
+        node3 = F.avg_pool2d(node1, 3, stride=1, padding=1, count_include_pad=False) + n02 + n13 + node0
+        loss = F.cross_entropy(F.relu(node3.mean(dim=(2, 3)) @ vs[16] + vs[17]), y)
+        out["loss"], out["grads"] = loss, torch.autograd.grad(loss, vs)
+
+    us = _timed(fg, iters)
+    return us, float(out["loss"])
+
+
+def nas_main(eng, a):
+    data = problems.synthetic_cifar10(4096, seed=0)
+    images = np.ascontiguousarray(data["images"], np.float32).reshape(len(data["labels"]), -1)
+    d = _engine.NasDesc(a.batch, True, eng.tensor(images), eng.int_tensor(data["labels"]))
+    rng = np.random.default_rng(0)
+    rows = rng.integers(0, len(images), a.batch)
+    idx = eng.int_tensor(rows)
+    # O(1) activations and logits on both sides of their ReLU: He-scaled conv weights, gamma 1, fc weights of std 1
+    w = [rng.normal(0, math.sqrt(2.0 / (9 * sh[2])) if len(sh) == 4 else (1.0 if len(sh) == 2 else 0.1), sh).astype(np.float32)
+         for sh in NAS_SHAPES]
+    for k in (2, 6, 10, 14):
+        w[k][:] = 1.0
+    ws, grads, loss = [eng.tensor(t) for t in w], [eng.zeros(*sh) for sh in NAS_SHAPES], eng.zeros(1)
+    fg = functools.partial(eng.nas_fg, d, idx, ws, loss, grads)
+    options = {"data": data, "batch_size": a.batch}
+    if a.loop:
+        fg_us = _timed(fg, a.loop, warmup=5)
+        step_us, _ = time_step("nas", options, 2, 1, warmup=1)
+        return {"workload": "nas", "loop": a.loop, "fg_us": round(fg_us, 2), "step_us": round(step_us, 2)}
+    runs = []
+    for _ in range(3):
+        fg_us = _timed(fg, a.iters)
+        torch_us, torch_loss = nas_torch(images[rows], np.asarray(data["labels"])[rows], w, a.iters)
+        step_us, graph = time_step("nas", options, a.unroll, a.unrolls)
+        runs.append({"fg_us": round(fg_us, 2), "torch_autograd_fg_us": round(torch_us, 2), "step_us": round(step_us, 2)})
+    return {"workload": "nas", "batch": a.batch, "coordinates": sum(int(np.prod(v.shape)) for v in graph.x), "runs": runs,
             "loss": float(eng.to_numpy(loss)[0]), "torch_loss": torch_loss, "unroll": a.unroll, "path": graph.last_path,
             "device": torch.cuda.get_device_name(0)}
 
@@ -431,7 +494,7 @@ def mnist_hvp_main(eng, a):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--problem", required=True, choices=list(IMAGE_NETS) + ["vgg16", "confocal", "mnist"])
+    p.add_argument("--problem", required=True, choices=list(IMAGE_NETS) + ["vgg16", "nas", "confocal", "mnist"])
     p.add_argument("--hvp", type=int, choices=(0, 1), default=0,
                    help="mnist: time l2o_mlp_hvp against l2o_mlp_deep_fg and torch double backward, and the train step")
     p.add_argument("--batch", type=int, help="default: 128; confocal: 32")
@@ -443,7 +506,7 @@ def main():
     p.add_argument("--roi", type=int, default=28, help="confocal")
     p.add_argument("--fused", type=int, choices=(0, 1), default=0,
                    help="confocal: 1 also times the fused unroll (fused_step_us) beside the step path (step_us)")
-    p.add_argument("--loop", type=int, default=0, help="confocal, vgg16: only run this many bare evaluations (for a kernel trace)")
+    p.add_argument("--loop", type=int, default=0, help="confocal, vgg16, nas: only run this many bare evaluations (for a kernel trace)")
     p.add_argument("--replicas", type=int, default=0,
                    help="confocal, with --fused 1: time N fused unrolls as one launch against N single launches, nothing else")
     a = p.parse_args()
@@ -457,7 +520,7 @@ def main():
     eng = _engine.HipEngine()
     _engine.set_default_engine(eng)
     meta.set_random_seed(0)
-    run = confocal_main if confocal else {"mnist": mnist_hvp_main, "vgg16": vgg16_main}.get(a.problem, image_net_main)
+    run = confocal_main if confocal else {"mnist": mnist_hvp_main, "vgg16": vgg16_main, "nas": nas_main}.get(a.problem, image_net_main)
     print(json.dumps(run(eng, a)))
 
 
