@@ -1,12 +1,12 @@
 """problems.cifar10 on the MI355X: l2o_cifar_conv_fg (csrc/l2o_cifar_conv.h) against the float64 torch reference
-(cifar_conv_reference.py), the unroll of meta_loss over the conv net against a float64 host unroll, the first-order
+(conv_reference.py), the unroll of meta_loss over the conv net against a float64 host unroll, the first-order
 meta-gradient against helpers.oracle_meta_grad, and the RNNProp evaluation driver on it.
 
-Bounds: a gradient block within 5e-4 of its largest entry, or 3 x the float32 reference's own distance from float64 where
-that is larger (test_mlp_training_gradient's rule); the conv biases under batch norm (exactly 0 in exact arithmetic)
-within 1e-6 of the largest entry of that layer's weight gradient.  The images carry a little uniform noise on top of
-problems.synthetic_cifar10, so that no two pooling candidates tie exactly (a tie broken differently by rounding moves a
-gradient to another pixel).
+Bounds (imagenet_harness.py holds them): a gradient block within 5e-4 of its largest entry, or 3 x the float32 reference's
+own distance from float64 where that is larger (test_mlp_training_gradient's rule); the conv biases under batch norm
+(exactly 0 in exact arithmetic) within 1e-6 of the largest entry of that layer's weight gradient.  The images carry a little
+uniform noise on top of problems.synthetic_cifar10, so that no two pooling candidates tie exactly (a tie broken differently
+by rounding moves a gradient to another pixel).
 
 One departure from test_mnist_conv.py: the RNNProp LSTM state carried into the second meta-training step (h1 / c1 / h2 / c2
 of conv_layer2/weights1) is held to 5 x, not 3 x, the float32 oracle's own distance from float64.  RNNProp normalises
@@ -16,58 +16,16 @@ itself more accurate (fp64 accumulation of conv2 and of the dW2 sample sum, trie
 The carried x, m and v and every meta-gradient block keep the 3 x rule.  The carry of the two conv biases under batch norm
 is not compared: their gradient is 0 in exact arithmetic, so what any implementation feeds the optimizer for them is its
 own rounding noise (test_fg_vs_float64 bounds it), and under RNNProp's g / sqrt(v) that noise steers their trajectories."""
-import math
-import os
-import re
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-import cifar_conv_reference as R
-import oracle as O
-from helpers import ORACLE_CFGS, block_errors, make_params
-from open_l2o_amd import _engine, meta, meta_rnnprop_eval, problems
-from open_l2o_amd.session import Session
-from test_meta_api import _net_config
-from test_training_gradient import CARRY_TOL, GRAD_TOL, Trainer, _carried, split_carry
+import imagenet_harness as H
+from conv_reference import CIFAR as R
+from imagenet_harness import eng  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture
-def eng():
-    e = _engine.HipEngine()
-    old = _engine._default_engine
-    _engine.set_default_engine(e)
-    yield e
-    _engine.set_default_engine(old)
-
-
-def _data(n, seed):
-    d = problems.synthetic_cifar10(n, seed=seed)
-    rng = np.random.default_rng(seed + 1000)
-    images = (d["images"].reshape(n, -1) + 0.05 * rng.random((n, 3072))).astype(np.float32)
-    return {"images": images.reshape(n, 32, 32, 3), "labels": d["labels"]}
-
-
-def _check_carry(snap, end, end32, what, state_factor):
-    """test_training_gradient.check_carry with its 3 x rule for x, m, v and ``state_factor`` x for the LSTM state."""
-    got, ref, r32 = _carried(snap), _carried(end), _carried(end32)
-    for nm in ref:
-        scale = max(float(np.abs(ref[nm]).max()), 1e-30)
-        err = float(np.abs(got[nm] - ref[nm]).max()) / scale
-        own = float(np.abs(r32[nm] - ref[nm]).max()) / scale
-        factor = state_factor if nm in ("h1", "c1", "h2", "c2") else 3
-        assert err < max(CARRY_TOL, factor * own), (what, nm, err, own)
-
-
-def _bound(got, want, g32):
-    scale = float(np.abs(want).max())
-    return float(np.abs(got - want).max()), max(GRAD_TOL * scale, 3 * float(np.abs(g32 - want).max()))
+NET = H.NETS["cifar_conv"]
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -77,38 +35,14 @@ def _bound(got, want, g32):
 @pytest.mark.parametrize("batch", [128, 37])
 def test_fg_vs_float64(eng, batch, batch_norm):
     n = 300
-    data = _data(n, seed=batch + batch_norm)
+    data = H.noisy_cifar(n, seed=batch + batch_norm)
     net = R.ConvNet(data["images"], data["labels"], batch_norm)
     w = R.sample_weights(batch_norm, seed=batch, logit_scale=3.0)
     rows = np.random.default_rng(batch).integers(0, n, batch)
     f64, g64 = net.fg([a.astype(np.float64) for a in w], rows)
     f32, g32 = net.fg(w, rows)
     assert (net.last_logits > 0).any() and (net.last_logits < 0).any()          # both sides of the ReLU on the logits
-    d = _engine.CifarConvDesc(batch, batch_norm, eng.tensor(net.images), eng.int_tensor(data["labels"]))
-    idx = eng.int_tensor(rows)
-    ws = [eng.tensor(a) for a in w]
-    grads = [eng.zeros(*a.shape) for a in w]
-    loss = eng.zeros(1)
-    eng.cifar_conv_fg(d, idx, ws, loss, grads)
-    got_f = float(eng.to_numpy(loss)[0])
-    got = [eng.to_numpy(g).astype(np.float64).reshape(a.shape) for g, a in zip(grads, g64)]
-    assert abs(got_f - f64) <= 1e-5 * abs(f64), (got_f, f64)
-    names = R.names(batch_norm)
-    for k, nm in enumerate(names):
-        if batch_norm and nm.endswith("biases1"):
-            wscale = float(np.abs(g64[k - 1]).max())
-            assert float(np.abs(got[k]).max()) <= 1e-6 * wscale, (nm, float(np.abs(got[k]).max()), wscale)
-            continue
-        err, bound = _bound(got[k], g64[k], g32[k])
-        assert err <= bound, (nm, err, bound)
-    # bit-reproducible; forward only gives the same loss
-    grads2 = [eng.zeros(*a.shape) for a in w]
-    loss2, loss3 = eng.zeros(1), eng.zeros(1)
-    eng.cifar_conv_fg(d, idx, ws, loss2, grads2)
-    eng.cifar_conv_fg(d, idx, ws, loss3, None)
-    assert eng.to_numpy(loss2)[0] == got_f and eng.to_numpy(loss3)[0] == got_f
-    for a, b in zip(grads, grads2):
-        assert np.array_equal(eng.to_numpy(a), eng.to_numpy(b))
+    H.check_fg_vs_float64(eng, NET, net, rows, w, f64, g64, f32, g32)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -117,43 +51,9 @@ def test_fg_vs_float64(eng, batch, batch_norm):
 @pytest.mark.parametrize("net", ["dm_logsign", "rnnprop"])
 def test_unroll_vs_float64(eng, net):
     T, batch, n = 20, 128, 512
-    data = _data(n, seed=41)
+    data = H.noisy_cifar(n, seed=41)
     idx = np.random.default_rng(42).integers(0, n, size=(T + 1, batch))
-    cfg = O.DM_LOGSIGN if net == "dm_logsign" else O.RNNPROP
-    params = make_params(cfg, seed=43, trained_like=True)
-    meta.set_random_seed(44)
-    problem = problems.cifar10("cifar10", batch_size=batch, data=data, sampler=lambda ne, b, nd: idx[:ne])
-    feed = {}
-    if cfg.kind == "rnnprop":
-        optimizer = meta_rnnprop_eval.MetaOptimizer(0.95, 0.95, **_net_config(cfg, params, key="rp"))
-        ml, _, _, step = optimizer.meta_loss(problem, T)
-        feed = {step: 1}
-    else:
-        optimizer = meta.MetaOptimizer(**_net_config(cfg, params))
-        ml = optimizer.meta_loss(problem, T)
-    with Session() as sess:
-        sess.run(ml.reset)
-        v0 = [v.eval() for v in optimizer.graph.x]
-        res = optimizer.graph.execute(feed, True)
-    assert optimizer.graph.last_path == "steps"
-    fx = np.asarray(res["fx_array"], np.float64)
-    xT = [np.asarray(a, np.float64) for a in res["x"]]
-    ref = R.ConvNet(data["images"], data["labels"], True)
-    outs = {}
-    for dt in (np.float64, np.float32):
-        p = {m: {v: a.astype(dt) for v, a in d.items()} for m, d in params.items()}
-        states = [tuple((h.astype(dt), c.astype(dt)) for h, c in O.net_initial_state(cfg, a.size)) for a in v0]
-        fx_r, x_r, _ = O.unroll_multi(lambda vs, t, wg: ref.fg(vs, idx[t], wg), cfg, p, [a.astype(dt) for a in v0],
-                                      states, T)
-        outs[dt] = (np.asarray(fx_r, np.float64), [np.asarray(a, np.float64) for a in x_r])
-    (fx64, x64), (fx32, x32) = outs[np.float64], outs[np.float32]
-    assert fx.shape == fx64.shape == (T + 1,)
-    for t in range(T + 1):
-        assert abs(fx[t] - fx64[t]) <= max(1e-5 * abs(fx64[t]), 3 * abs(fx32[t] - fx64[t])), (t, fx[t], fx64[t], fx32[t])
-    for k, (g, w64, w32) in enumerate(zip(xT, x64, x32)):
-        err, bound = _bound(g.reshape(w64.shape), w64, w32)
-        assert err <= bound, (R.names(True)[k], err, bound)
-
+    H.check_unroll_vs_float64(eng, NET, net, T, batch, data, idx)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -161,44 +61,12 @@ def test_unroll_vs_float64(eng, net):
 # ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["dm_logsign", "rnnprop"])
 def test_meta_gradient_vs_float64(eng, name):
-    T, batch = 10, 128
-    data = _data(1024, seed=51)
-    params = make_params(ORACLE_CFGS[name], seed=52, trained_like=True)
-    meta.set_random_seed(53)
-    tr = Trainer(eng, name, params, problems.cifar10("cifar10", batch_size=batch, data=data), T)
-    shapes = [tuple(v.shape) for v in tr.graph.x]
-    assert shapes == R.shapes(True)
-    ref = R.ConvNet(data["images"], data["labels"], True)
-    tr.reset()
-    prev = None
-    for k in range(2):
-        snap = tr.snapshot()
-        if prev is not None:
-            for j, (sv, ev, e32) in enumerate(zip(snap["vars"], split_carry(prev[0], shapes), split_carry(prev[1], shapes))):
-                if R.names(True)[j].endswith("biases1"):
-                    continue
-                _check_carry(sv, ev, e32, "step %d: carry into variable %d" % (k, j), 5 if name == "rnnprop" else 3)
-        got = tr.train_step()
-        assert tr.graph.last_path == "steps"
-        idx = eng.to_numpy(tr.graph._mlp_idx[0])
-        assert idx.shape == (T + 1, batch)
-        fg = ref.flat_fg(shapes, idx)
-        want, end = tr.reference(fg, snap)
-        g32, end32 = tr.reference(fg, snap, np.float32)
-        prev = (end, end32)
-        errs, errs32 = block_errors(got, want), block_errors(g32, want)
-        for blk, e in errs.items():
-            assert e < max(GRAD_TOL, 3 * errs32[blk]), (k, blk, e, errs32[blk])
+    H.check_meta_gradient_vs_float64(eng, NET, name, 10, 128, H.noisy_cifar(1024, seed=51),
+                                     state_factor=5 if name == "rnnprop" else 3)
 
 
 # ------------------------------------------------------------------------------------------------------------------
 # 4. the RNNProp evaluation driver with the shipped MLP-trained optimizer, pointed at the CIFAR-10 conv net
 # ------------------------------------------------------------------------------------------------------------------
 def test_evaluate_rnnprop_driver():
-    cmd = [sys.executable, os.path.join(ROOT, "scripts", "evaluate_rnnprop.py"), "--problem", "cifar_conv",
-           "--synthetic_cifar10", "1024", "--num_steps", "40",
-           "--path", os.path.join(ROOT, "tests", "golden", "trained", "rnnprop_mnist_mlp", "rp.l2l-0")]
-    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-3000:]
-    m = re.search(r"Log Mean Final Error: (\S+)", out.stdout)
-    assert m and math.isfinite(float(m.group(1))), out.stdout[-2000:]
+    H.check_driver(NET, 1024, 40, 900)

@@ -1,7 +1,7 @@
 """The three conv optimizees (l2o_mnist_conv_fg, l2o_cifar_conv_fg, l2o_lenet_fg) where their own modules do not go: the
 edges of the minibatch range the launchers accept (2 .. 1024), scratch and output discipline, pooling windows that tie
-exactly, and the graph path at a minibatch other than 128.  References: the float64 torch nets of mnist_conv_reference.py,
-cifar_conv_reference.py and lenet_reference.py.
+exactly, and the graph path at a minibatch other than 128.  References: the float64 torch nets of conv_reference.py and
+lenet_reference.py.
 
 Bounds (the project's, as test_lenet.py): the loss within 1e-5 relative; a gradient block within GRAD_TOL = 5e-4 of its
 largest float64 entry, or 3 x the float32 torch reference's own distance from float64 where that is larger; a bias that feeds
@@ -41,17 +41,14 @@ import numpy as np
 import pytest
 import torch
 
-import cifar_conv_reference
+import imagenet_harness as H
 import lenet_reference
-import mnist_conv_reference
 import oracle as O
 from helpers import make_params
-from open_l2o_amd import _abi, _engine, meta, problems
+from imagenet_harness import eng  # noqa: F401  (the fixture)
+from open_l2o_amd import meta
 from open_l2o_amd.session import Session
-from test_lenet import _data as _cifar_data          # (test_cifar_conv._data is the same function)
-from test_lenet import _lenet
 from test_meta_api import _net_config
-from test_mnist_conv import _data as _mnist_data
 from test_training_gradient import GRAD_TOL
 
 pytestmark = pytest.mark.gpu
@@ -61,30 +58,19 @@ SCRATCH_BATCHES = [2, 257, 1024]
 GUARD = 4096
 
 
-def _conv_fed(batch_norm):
-    return [(1, 0), (5, 4)] if batch_norm else []
+def _edge(name, **own):
+    return types.SimpleNamespace(**vars(H.NETS[name]), **own)
 
 
-# name -> what differs between the nets: reference module and class, engine descriptor / entry point / cached scratch
-# attribute, ABI struct and scratch-size function, images, weights, the biases that feed a batch norm, whether the logits
-# pass through a ReLU, the width of section 3's constant border
+# imagenet_harness.NETS' entries of the three nets, plus what only these cases need: weights, whether the logits pass through
+# a ReLU, the width of section 3's constant border
 NETS = {
-    "mnist_conv": types.SimpleNamespace(
-        R=mnist_conv_reference, ref=mnist_conv_reference.ConvNet, desc=_engine.MnistConvDesc, fg="mnist_conv_fg",
-        scratch="_mnist_conv_scratch", struct=_abi.MnistConv, floats="l2o_mnist_conv_scratch_floats", data=_mnist_data,
-        weights=lambda bn, seed: mnist_conv_reference.sample_weights(bn, seed=seed, logit_scale=3.0), fed=_conv_fed,
-        relu_logits=True, border=7, problem=problems.mnist_conv),
-    "cifar_conv": types.SimpleNamespace(
-        R=cifar_conv_reference, ref=cifar_conv_reference.ConvNet, desc=_engine.CifarConvDesc, fg="cifar_conv_fg",
-        scratch="_cifar_conv_scratch", struct=_abi.CifarConv, floats="l2o_cifar_conv_scratch_floats", data=_cifar_data,
-        weights=lambda bn, seed: cifar_conv_reference.sample_weights(bn, seed=seed, logit_scale=3.0), fed=_conv_fed,
-        relu_logits=True, border=8, problem=lambda **kw: problems.cifar10("cifar10", **kw)),
-    "lenet": types.SimpleNamespace(
-        R=lenet_reference, ref=lenet_reference.LeNet, desc=_engine.LenetDesc, fg="lenet_fg",
-        scratch="_lenet_scratch", struct=_abi.Lenet, floats="l2o_lenet_scratch_floats", data=_cifar_data,
-        weights=lambda bn, seed: lenet_reference.sample_weights(bn, seed=seed), fed=lenet_reference.bn_fed_biases,
-        relu_logits=False, border=8,
-        problem=_lenet),
+    "mnist_conv": _edge("mnist_conv", relu_logits=True, border=7,
+                        weights=lambda bn, seed: H.NETS["mnist_conv"].R.sample_weights(bn, seed=seed, logit_scale=3.0)),
+    "cifar_conv": _edge("cifar_conv", relu_logits=True, border=8,
+                        weights=lambda bn, seed: H.NETS["cifar_conv"].R.sample_weights(bn, seed=seed, logit_scale=3.0)),
+    "lenet": _edge("lenet", relu_logits=False, border=8,
+                   weights=lambda bn, seed: lenet_reference.sample_weights(bn, seed=seed)),
 }
 
 # seeds of (weights, minibatch rows) per (net, batch norm, minibatch); where none is listed: the minibatch size itself.
@@ -170,15 +156,6 @@ def check_inputs(c):
         assert own <= GRAD_TOL / 3, (c.names[k], own)
     # the bound in use (GRAD_TOL, by the cap just asserted) sees one wrong sample
     assert any(c.moved[k] > max(GRAD_TOL, 3 * c.own[k]) for k in c.own), c.moved
-
-
-@pytest.fixture
-def eng():
-    e = _engine.HipEngine()
-    old = _engine._default_engine
-    _engine.set_default_engine(e)
-    yield e
-    _engine.set_default_engine(old)
 
 
 class Device(object):

@@ -20,26 +20,19 @@ within 1e-5 / 3 on the loss -- at 1, 4 and 8 threads and with every weight moved
 (no cancellation: a flipped mask is 1 / (B * 1024) of a block) it is the first seed with that property.  Every case asserts
 the float32 condition before the kernel's result is looked at, so the bound in force is GRAD_TOL."""
 import ctypes as C
-import math
-import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import imagenet_harness as H
 import nas_reference as R
-import oracle as O
-from helpers import ORACLE_CFGS, block_errors, make_params
-from open_l2o_amd import _abi, _engine, meta, meta_rnnprop_eval, problems
-from open_l2o_amd.session import Session
-from test_meta_api import _net_config
-from test_training_gradient import CARRY_TOL, GRAD_TOL, Trainer, _carried, split_carry
+from imagenet_harness import eng  # noqa: F401  (the fixture)
+from open_l2o_amd import _abi, _engine
+from test_training_gradient import GRAD_TOL
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NET = H.NETS["nas"]
 N_DATA = 64
 _cache = {}
 # (batch norm, weight scale, minibatch, data) -> the seed of the minibatch
@@ -54,24 +47,14 @@ MINIBATCH_SEED = {
 }
 
 
-@pytest.fixture
-def eng():
-    e = _engine.HipEngine()
-    old = _engine._default_engine
-    _engine.set_default_engine(e)
-    yield e
-    _engine.set_default_engine(old)
-
-
 def _data(kind="uniform"):
     """Uniform images and labels; "ring": the same images, zero except for the outermost ring of pixels."""
     if kind not in _cache:
-        rng = np.random.default_rng(0)
-        images = rng.random((N_DATA, 32, 32, 3)).astype(np.float32)
-        labels = rng.integers(0, 10, N_DATA)
+        d = H.uniform_cifar(N_DATA, 0)
+        images = d["images"].copy()
         if kind == "ring":
             images[:, 1:31, 1:31, :] = 0.0
-        _cache[kind] = {"images": images, "labels": labels}
+        _cache[kind] = {"images": images, "labels": d["labels"]}
     return _cache[kind]
 
 
@@ -99,13 +82,8 @@ def _desc(eng, batch_norm, batch, kind="uniform"):
     return _engine.NasDesc(batch, batch_norm, eng.tensor(data["images"].reshape(N_DATA, -1)), eng.int_tensor(data["labels"]))
 
 
-def _run_fg(eng, d, rows, w, want_grad=True, fill=0.0):
-    idx = eng.int_tensor(rows)
-    ws = [eng.tensor(a) for a in w]
-    grads = [eng.zeros(*a.shape) + fill for a in w] if want_grad else None
-    loss = eng.zeros(1)
-    eng.nas_fg(d, idx, ws, loss, grads)
-    return eng.to_numpy(loss).copy(), None if grads is None else [eng.to_numpy(g).copy() for g in grads]
+def _run_fg(eng, d, rows, w, **kw):
+    return H.run_fg(eng, NET, d, rows, w, **kw)
 
 
 def _check_fg(eng, batch_norm, scale, batch, kind="uniform"):
@@ -145,10 +123,10 @@ def _check_fg(eng, batch_norm, scale, batch, kind="uniform"):
                 failures.append((nm, got / wscale, own / wscale))
             continue
         scale64 = float(np.abs(want).max())
-        err, own = float(np.abs(g - want).max()), float(np.abs(w32 - want).max())
-        print("%-28s err %.3e own %.3e of max %.3e" % (nm, err / scale64, own / scale64, scale64))
-        if not err <= max(GRAD_TOL * scale64, 3 * own):
-            failures.append((nm, err / scale64, own / scale64))
+        err, bnd = H.bound(g, want, w32)
+        print("%-28s err %.3e bound %.3e of max %.3e" % (nm, err / scale64, bnd / scale64, scale64))
+        if not err <= bnd:
+            failures.append((nm, err / scale64, bnd / scale64))
     assert not failures, failures
 
 
@@ -255,102 +233,21 @@ def test_bit_contracts(eng, batch_norm):
 @pytest.mark.parametrize("net", ["dm_logsign", "rnnprop"])
 def test_unroll_vs_float64(eng, net):
     T, batch = 20, 8
-    data = _data()
     idx = np.random.default_rng(42).integers(0, N_DATA, size=(T + 1, batch))
-    cfg = O.DM_LOGSIGN if net == "dm_logsign" else O.RNNPROP
-    params = make_params(cfg, seed=43, trained_like=True)
-    meta.set_random_seed(44)
-    problem = problems.NAS("cifar10", batch_size=batch, data=data, sampler=lambda ne, b, nd: idx[:ne])
-    feed = {}
-    if cfg.kind == "rnnprop":
-        optimizer = meta_rnnprop_eval.MetaOptimizer(0.95, 0.95, **_net_config(cfg, params, key="rp"))
-        ml, _, _, step = optimizer.meta_loss(problem, T)
-        feed = {step: 1}
-    else:
-        optimizer = meta.MetaOptimizer(**_net_config(cfg, params))
-        ml = optimizer.meta_loss(problem, T)
-    with Session() as sess:
-        sess.run(ml.reset)
-        v0 = [v.eval() for v in optimizer.graph.x]
-        res = optimizer.graph.execute(feed, True)
-    assert optimizer.graph.last_path == "steps"
-    fx = np.asarray(res["fx_array"], np.float64)
-    xT = [np.asarray(a, np.float64) for a in res["x"]]
-    ref = R.Nas(data["images"], data["labels"], True)
-    outs = {}
-    for dt in (np.float64, np.float32):
-        p = {m: {v: a.astype(dt) for v, a in d.items()} for m, d in params.items()}
-        states = [tuple((h.astype(dt), c.astype(dt)) for h, c in O.net_initial_state(cfg, a.size)) for a in v0]
-        fx_r, x_r, _ = O.unroll_multi(lambda vs, t, wg: ref.fg(vs, idx[t], wg), cfg, p, [a.astype(dt) for a in v0],
-                                      states, T)
-        outs[dt] = (np.asarray(fx_r, np.float64), [np.asarray(a, np.float64) for a in x_r])
-    (fx64, x64), (fx32, x32) = outs[np.float64], outs[np.float32]
-    assert fx.shape == fx64.shape == (T + 1,)
-    for t in range(T + 1):
-        print("fx", t, fx[t], fx64[t], fx32[t])
-        assert abs(fx[t] - fx64[t]) <= max(1e-5 * abs(fx64[t]), 3 * abs(fx32[t] - fx64[t])), (t, fx[t], fx64[t], fx32[t])
-    for nm, g, w64, w32 in zip(R.names(True), xT, x64, x32):
-        scale = float(np.abs(w64).max())
-        err, own = float(np.abs(g.reshape(w64.shape) - w64).max()), float(np.abs(w32 - w64).max())
-        print("x", nm, "err %.3e own %.3e" % (err / scale, own / scale))
-        assert err <= max(GRAD_TOL * scale, 3 * own), (nm, err, own)
+    H.check_unroll_vs_float64(eng, NET, net, T, batch, _data(), idx)
 
 
 # ------------------------------------------------------------------------------------------------------------------
 # 4. the meta-gradient: two consecutive train steps against helpers.oracle_meta_grad
 # ------------------------------------------------------------------------------------------------------------------
-def _check_carry(snap, end, end32, what):
-    got, ref, r32 = _carried(snap), _carried(end), _carried(end32)
-    for nm in ref:
-        scale = max(float(np.abs(ref[nm]).max()), 1e-30)
-        err = float(np.abs(got[nm] - ref[nm]).max()) / scale
-        own = float(np.abs(r32[nm] - ref[nm]).max()) / scale
-        assert err < max(CARRY_TOL, 3 * own), (what, nm, err, own)
-
-
 def test_meta_gradient_vs_float64(eng):
     """As test_cifar_conv.py: the carry of the conv biases under batch norm is not compared (their gradient is 0 in exact
     arithmetic, so what a float32 implementation feeds the optimizer for them is its own rounding noise)."""
-    T, batch = 5, 8
-    name = "dm_logsign"
-    data = _data()
-    params = make_params(ORACLE_CFGS[name], seed=52, trained_like=True)
-    meta.set_random_seed(53)
-    tr = Trainer(eng, name, params, problems.NAS("cifar10", batch_size=batch, data=data), T)
-    shapes = [tuple(v.shape) for v in tr.graph.x]
-    assert shapes == R.shapes(True)
-    ref = R.Nas(data["images"], data["labels"], True)
-    tr.reset()
-    prev = None
-    for k in range(2):
-        snap = tr.snapshot()
-        if prev is not None:
-            for j, (sv, ev, e32) in enumerate(zip(snap["vars"], split_carry(prev[0], shapes), split_carry(prev[1], shapes))):
-                if R.names(True)[j].endswith("biases1"):
-                    continue
-                _check_carry(sv, ev, e32, "step %d: carry into variable %d" % (k, j))
-        got = tr.train_step()
-        assert tr.graph.last_path == "steps"
-        idx = eng.to_numpy(tr.graph._mlp_idx[0])
-        assert idx.shape == (T + 1, batch)
-        fg = ref.flat_fg(shapes, idx)
-        want, end = tr.reference(fg, snap)
-        g32, end32 = tr.reference(fg, snap, np.float32)
-        prev = (end, end32)
-        errs, errs32 = block_errors(got, want), block_errors(g32, want)
-        for blk, e in errs.items():
-            print("meta-gradient", k, blk, "err %.3e float32 oracle %.3e" % (e, errs32[blk]))
-            assert e < max(GRAD_TOL, 3 * errs32[blk]), (k, blk, e, errs32[blk])
+    H.check_meta_gradient_vs_float64(eng, NET, "dm_logsign", 5, 8, _data())
 
 
 # ------------------------------------------------------------------------------------------------------------------
 # 5. the RNNProp evaluation driver with the shipped MLP-trained optimizer, pointed at the NAS cell
 # ------------------------------------------------------------------------------------------------------------------
 def test_evaluate_rnnprop_driver():
-    cmd = [sys.executable, os.path.join(ROOT, "scripts", "evaluate_rnnprop.py"), "--problem", "nas",
-           "--synthetic_cifar10", "256", "--num_steps", "20",
-           "--path", os.path.join(ROOT, "tests", "golden", "trained", "rnnprop_mnist_mlp", "rp.l2l-0")]
-    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-3000:]
-    m = re.search(r"Log Mean Final Error: (\S+)", out.stdout)
-    assert m and math.isfinite(float(m.group(1))), out.stdout[-2000:]
+    H.check_driver(NET, 256, 20, 600)

@@ -9,42 +9,21 @@ import re
 
 import numpy as np
 import pytest
-import torch
 
-import oracle as O
+import imagenet_harness as H
 import vgg16_reference as R
-from helpers import make_params, rel_err
-from oracle_engine import OracleEngine
-from open_l2o_amd import _abi, _engine, _graph_steps, meta, meta_rnnprop_eval, problems, util
-from open_l2o_amd.session import Session
-from test_meta_api import _net_config
+from open_l2o_amd import _abi, _engine, _graph_steps, problems, util
 from test_training_gradient import GRAD_TOL
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NARROW = R.NARROW_CHANNELS
-
-
-class Vgg16OracleEngine(OracleEngine):
-    """The oracle engine plus VGG-16's loss and gradient from the float32 torch reference."""
-
-    def vgg16_fg(self, d, indices, ws, loss, grads):
-        self.calls.append("vgg16_fg")
-        net = R.Vgg16(d.images.numpy(), d.labels.numpy(), d.channels)
-        vs = [w.numpy().reshape(sh) for w, sh in zip(ws, R.shapes(d.channels))]
-        f, g = net.fg(vs, indices.numpy(), want_grad=grads is not None)
-        loss.copy_(torch.from_numpy(np.array([f], np.float32)))
-        if grads is not None:
-            for t, a in zip(grads, g):
-                t.copy_(torch.from_numpy(np.ascontiguousarray(a, np.float32)).view_as(t))
+NET = H.NETS["vgg16"]
 
 
 @pytest.fixture
 def engine():
-    eng = Vgg16OracleEngine()
-    old = _engine._default_engine
-    _engine.set_default_engine(eng)
-    yield eng
-    _engine.set_default_engine(old)
+    with H.as_default(H.oracle_engine(NET)) as e:
+        yield e
 
 
 def _data(n=64, seed=0):
@@ -150,17 +129,9 @@ def test_reference_central_differences():
     rows = rng.integers(0, 16, 3)
     f, g = net.fg(w, rows)
     assert np.isfinite(f) and 1.46 < f < 2.47
-    h = 1e-6
-    for k, a in enumerate(w):
-        gmax = np.abs(g[k]).max()
-        assert gmax > 0, R.names()[k]
-        for j in rng.choice(a.size, size=min(3, a.size), replace=False):
-            wp = [b.copy() for b in w]
-            wm = [b.copy() for b in w]
-            wp[k].reshape(-1)[j] += h
-            wm[k].reshape(-1)[j] -= h
-            num = (net.fg(wp, rows, want_grad=False)[0] - net.fg(wm, rows, want_grad=False)[0]) / (2 * h)
-            assert abs(num - g[k].reshape(-1)[j]) < 1e-5 * max(gmax, 1e-3) + 1e-8, (R.names()[k], j, num)
+    for nm, a in zip(R.names(), g):
+        assert np.abs(a).max() > 0, nm
+    H.check_central_differences(net, w, rows, R.names(), g, rng, coords=3, rtol=1e-5)
 
 
 def test_reference_at_the_initialisation():
@@ -237,76 +208,17 @@ def test_library_symbols_header_and_scratch():
 
 
 # 6. host wiring
-def _sampler(idx):
-    calls = {"n": 0}
-
-    def sampler(n_evals, b, n_data):
-        out = idx[calls["n"]:calls["n"] + n_evals]
-        calls["n"] += n_evals
-        return out
-    return sampler
+def _check_v0(v0):
+    assert np.array_equal(v0[27], np.ones(10, np.float32)) and not v0[1].any() and v0[0].any()
 
 
 @pytest.mark.parametrize("net", ["dm_logsign", "rnnprop"])
 def test_meta_loss_wiring(engine, net):
     """meta_loss over util.get_config("vgg16") at narrow widths on the step-granular path == the oracle's multi-variable
     unroll over the same float32 evaluations, two chained unrolls."""
-    data = _data(32, seed=7)
-    T, batch = 2, 4
-    idx = np.random.default_rng(8).integers(0, 32, size=(2 * (T + 1), batch))
-    cfg = O.DM_LOGSIGN if net == "dm_logsign" else O.RNNPROP
-    params = make_params(cfg, seed=9, trained_like=True)
-    meta.set_random_seed(10)
-    problem = util.get_config("vgg16", problem_options={"data": data, "batch_size": batch, "channels": NARROW,
-                                                        "sampler": _sampler(idx)})[0]
-    feeds = [{}, {}]
-    if cfg.kind == "rnnprop":
-        optimizer = meta_rnnprop_eval.MetaOptimizer(0.95, 0.95, **_net_config(cfg, params, key="rp"))
-        ml, _, _, step = optimizer.meta_loss(problem, T)
-        feeds = [{step: 1}, {step: 1 + T}]
-    else:
-        optimizer = meta.MetaOptimizer(**_net_config(cfg, params))
-        ml = optimizer.meta_loss(problem, T)
-    with Session() as sess:
-        sess.run(ml.reset)
-        v0 = [v.eval() for v in optimizer.graph.x]
-        assert [tuple(a.shape) for a in v0] == R.shapes(NARROW)
-        assert np.array_equal(v0[27], np.ones(10, np.float32)) and not v0[1].any() and v0[0].any()
-        loss1, fx1, _ = sess.run([ml.loss, ml.fx, ml.update], feed_dict=feeds[0])
-        loss2, fx2, x2, _ = sess.run([ml.loss, ml.fx, ml.x, ml.update], feed_dict=feeds[1])
-    assert optimizer.graph.last_path == "steps"
-    assert engine.calls.count("vgg16_fg") == 2 * (T + 1)
-    ref = R.Vgg16(data["images"], data["labels"], NARROW)
-    states = [O.net_initial_state(cfg, a.size) for a in v0]
-    if cfg.kind == "rnnprop":
-        fx_a, va, sa, ma, va2 = O.unroll_multi(lambda vs, t, wg: ref.fg(vs, idx[t], wg), cfg, params, v0, states, T,
-                                               return_moments=True)
-        fx_b, vb, _ = O.unroll_multi(lambda vs, t, wg: ref.fg(vs, idx[T + 1 + t], wg), cfg, params, va, sa, T, ms=ma,
-                                     vs=va2, step0=1 + T)
-    else:
-        fx_a, va, sa = O.unroll_multi(lambda vs, t, wg: ref.fg(vs, idx[t], wg), cfg, params, v0, states, T)
-        fx_b, vb, _ = O.unroll_multi(lambda vs, t, wg: ref.fg(vs, idx[T + 1 + t], wg), cfg, params, va, sa, T)
-    assert rel_err(fx1, fx_a[-1]) < 1e-5 and rel_err(loss1, fx_a.sum()) < 1e-5
-    assert rel_err(fx2, fx_b[-1]) < 1e-5 and rel_err(loss2, fx_b.sum()) < 1e-5
-    for got, want in zip(x2, vb):
-        np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-7)
+    H.check_meta_loss_wiring(engine, NET, net, n_data=32, T=2, batch=4, check_v0=_check_v0)
 
 
 def test_meta_minimize_and_refusals(engine):
     """One first-order training step on the narrow net runs on the recording step path; second derivatives refuse it."""
-    data = _data(32, seed=11)
-    meta.set_random_seed(12)
-    opt = meta.MetaOptimizer(**_net_config(O.DM_LOGSIGN, make_params(O.DM_LOGSIGN, seed=13, trained_like=True)))
-    problem = problems.vgg16_cifar10("cifar10", batch_size=4, data=data, channels=NARROW)
-    ms = opt.meta_minimize(problem, 2, learning_rate=1e-3)
-    w0 = {m: {v: np.array(a) for v, a in d.items()} for m, d in opt._nets["cw"].variables.items()}
-    with Session() as sess:
-        sess.run(ms.reset)
-        c1 = sess.run([ms.fx, ms.update, ms.step])[0]
-    assert np.isfinite(c1) and opt.graph.last_path == "steps"
-    assert "vgg16_fg" in engine.calls
-    w1 = opt._nets["cw"].variables
-    assert any(not np.array_equal(w0[m][v], np.asarray(w1[m][v])) for m in w0 for v in w0[m])
-    opt2 = meta.MetaOptimizer(**_net_config(O.DM_LOGSIGN, make_params(O.DM_LOGSIGN, seed=13, trained_like=True)))
-    with pytest.raises(NotImplementedError, match="second_derivatives"):
-        opt2.meta_minimize(problem, 2, learning_rate=1e-3, second_derivatives=True)
+    H.check_meta_minimize_and_refusals(engine, NET, n_data=32, batch=4, replicas=False)
