@@ -52,6 +52,8 @@ MLP_HVP_SYMBOLS = ("l2o_mlp_hvp", "l2o_mlp_hvp_scratch_floats")
 VGG16_SYMBOLS = ("l2o_vgg16_fg", "l2o_vgg16_scratch_floats")
 # ... and include/l2o_nas_abi.h (problems.NAS); bound when the library has them
 NAS_SYMBOLS = ("l2o_nas_fg", "l2o_nas_scratch_floats")
+# ... and include/l2o_klstm_abi.h (networks.KernelDeepLSTM); bound when the library has them
+KLSTM_SYMBOLS = ("l2o_klstm_supported", "l2o_klstm_state_floats", "l2o_klstm_step", "l2o_klstm_bwd_step")
 
 
 # option ids of include/l2o_abi.h ("options": per call, caller-owned -- the LIBRARY keeps no option state since ABI v9).
@@ -267,6 +269,20 @@ class GenBwdIO(C.Structure):
                [(n, C.c_void_p) for n in ("tc", "h_last", "dd", "feats", "du", "dg")]
 
 
+class KlstmNet(C.Structure):
+    """struct l2o_klstm_net (include/l2o_klstm_abi.h)"""
+    _fields_ = [("kw", C.c_int32), ("kh", C.c_int32), ("n_layers", C.c_int32), ("hidden", C.c_int32 * 2),
+                ("preprocess", C.c_int32), ("tanh_output", C.c_int32), ("flags", C.c_int32), ("logsign_k", C.c_double),
+                ("scale", C.c_double), ("w_gates", C.c_void_p * 2), ("b_gates", C.c_void_p * 2), ("w_lin", C.c_void_p),
+                ("b_lin", C.c_void_p)]
+
+
+class KlstmBwdIO(C.Structure):
+    """struct l2o_klstm_bwd_io"""
+    _fields_ = [(n, C.c_void_p) for n in ("g", "st_prev", "dx_next", "carry_in", "carry_out")] + \
+               [("act", C.c_void_p * 2), ("dz", C.c_void_p * 2)] + [(n, C.c_void_p) for n in ("tc", "h_last", "dd")]
+
+
 class NetWeights(C.Structure):
     """struct l2o_net_weights"""
     _fields_ = [(n, C.c_void_p) for n in ("w_gates1", "b_gates1", "w_gates2", "b_gates2", "w_lin", "b_lin",
@@ -328,7 +344,8 @@ def source_build_id():
     csrc = os.path.join(_HERE, "csrc")
     names = ["l2o_kernels.hip", "l2o_kernels_ilp.hip", "Makefile", "../../include/l2o_abi.h",
              "../../include/l2o_confocal_unroll_abi.h", "../../include/l2o_confocal_multi_abi.h",
-             "../../include/l2o_mlp_hvp_abi.h", "../../include/l2o_vgg16_abi.h", "../../include/l2o_nas_abi.h"] + [
+             "../../include/l2o_mlp_hvp_abi.h", "../../include/l2o_vgg16_abi.h", "../../include/l2o_nas_abi.h",
+             "../../include/l2o_klstm_abi.h"] + [
         os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.h"))]
     h = hashlib.sha256()
     try:
@@ -437,6 +454,15 @@ def lib():
         floats, fg = getattr(L, stem + "_scratch_floats"), getattr(L, stem + "_fg")
         floats.restype, floats.argtypes = C.c_size_t, [C.POINTER(struct)]
         fg.restype, fg.argtypes = C.c_int, [C.POINTER(struct)] + [vp] * 6
+    if all(hasattr(L, name) for name in KLSTM_SYMBOLS):
+        L.l2o_klstm_supported.restype = C.c_int
+        L.l2o_klstm_supported.argtypes = [C.POINTER(KlstmNet)]
+        L.l2o_klstm_state_floats.restype = C.c_size_t
+        L.l2o_klstm_state_floats.argtypes = [C.POINTER(KlstmNet), i64]
+        L.l2o_klstm_step.restype = C.c_int
+        L.l2o_klstm_step.argtypes = [C.POINTER(KlstmNet), vp, vp, vp, vp, i64, vp]
+        L.l2o_klstm_bwd_step.restype = C.c_int
+        L.l2o_klstm_bwd_step.argtypes = [C.POINTER(KlstmNet), C.POINTER(KlstmBwdIO), i64, vp]
     L.l2o_mlp_hvp_scratch_floats.restype = C.c_size_t
     L.l2o_mlp_hvp_scratch_floats.argtypes = [C.POINTER(MlpDeep)]
     L.l2o_mlp_hvp.restype = C.c_int

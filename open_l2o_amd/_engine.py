@@ -787,6 +787,52 @@ class HipEngine(object):
         _abi.check(self.lib.l2o_cwlstm_bwd_step_generic(C.byref(cc), C.byref(gen.c), C.byref(c), float(pow1), float(pow2),
                                                         int(N), self._stream()))
 
+    # -- networks.KernelDeepLSTM (l2o_klstm_step / l2o_klstm_bwd_step, include/l2o_klstm_abi.h) ----------
+    class KlstmNet(object):
+        """Device weights of a KernelDeepLSTM in their Sonnet layouts + the struct l2o_klstm_net that points at them."""
+
+        def __init__(self, engine, net):
+            c = _abi.KlstmNet()
+            c.kw, c.kh = net.kernel_shape
+            c.n_layers = len(net.layers)
+            c.preprocess, c.tanh_output, c.flags = int(net.preprocess), int(bool(net.tanh_output)), 0
+            c.logsign_k, c.scale = float(net.logsign_k), float(net.scale)
+            self.tensors = []
+            params = net.variables
+            for l, H in enumerate(net.layers):
+                c.hidden[l] = H
+                for name, field in (("w_gates", c.w_gates), ("b_gates", c.b_gates)):
+                    t = engine.tensor(params["lstm_%d" % (l + 1)][name])
+                    self.tensors.append(t)
+                    field[l] = t.data_ptr()
+            wl, bl = engine.tensor(params["linear"]["w"]), engine.tensor(params["linear"]["b"])
+            self.tensors += [wl, bl]
+            c.w_lin, c.b_lin = wl.data_ptr(), bl.data_ptr()
+            self.c = c
+
+    def klstm_net(self, net):
+        if not all(hasattr(self.lib, name) for name in _abi.KLSTM_SYMBOLS):
+            raise RuntimeError("libl2o_hip.so has no l2o_klstm_step: rebuild it (make -C open_l2o_amd/csrc)")
+        return HipEngine.KlstmNet(self, net)
+
+    def klstm_step(self, net, g, st_in, st_out, x, N):
+        """One KernelDeepLSTM step on the N filters of a [K, N] variable (l2o_klstm_step): x += delta; st_out may be
+        st_in."""
+        _abi.check(self.lib.l2o_klstm_step(C.byref(net.device_net(self).c), _ptr(g), _ptr(st_in), _ptr(st_out), _ptr(x),
+                                           int(N), self._stream()))
+
+    def klstm_bwd_step(self, net, io: dict, N):
+        """One BPTT step of a KernelDeepLSTM (l2o_klstm_bwd_step).  io: device tensors keyed by the fields of struct
+        l2o_klstm_bwd_io (act / dz: lists, one tensor per layer)."""
+        c = _abi.KlstmBwdIO()
+        for k, _ in _abi.KlstmBwdIO._fields_:
+            if k in ("act", "dz"):
+                for l, t in enumerate(io[k]):
+                    getattr(c, k)[l] = _ptr(t).value
+            else:
+                setattr(c, k, _ptr(io[k]))
+        _abi.check(self.lib.l2o_klstm_bwd_step(C.byref(net.device_net(self).c), C.byref(c), int(N), self._stream()))
+
     def lstm_step(self, spec: NetSpec, wpack, g, m, v, pow1, pow2, st, x, B, D):
         if isinstance(wpack, HipEngine.GenNet):
             return self.lstm_step_generic(spec, wpack, g, None, m, v, pow1, pow2, st, x, B * D)

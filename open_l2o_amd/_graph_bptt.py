@@ -12,6 +12,20 @@ from . import _abi, networks
 from ._graph_core import PackedState, _DevGrad, _LazyHost, _term_vars, _world, _all_reduce, rng  # noqa: F401
 
 
+def _atb_blocks(eng, A, Bmat):
+    """A^T B through l2o_atb, which holds a KA <= 112 x KB <= 192 result in registers: in blocks where it is larger."""
+    ka, kb = A.shape[1], Bmat.shape[1]
+    if ka <= 112 and kb <= 192:
+        return eng.atb(A, Bmat)
+    res = eng.empty(ka, kb)              # (blocks copied into place: buffer plumbing)
+    for r0 in range(0, ka, 96):
+        Ab = A[:, r0:r0 + 96].contiguous()
+        for c0 in range(0, kb, 176):
+            blk = eng.atb(Ab, Bmat[:, c0:c0 + 176].contiguous())
+            res[r0:r0 + blk.shape[0], c0:c0 + blk.shape[1]].copy_(blk)
+    return res
+
+
 class BpttMixin(object):
     def _bptt(self, net, acc, B, D, T, step0, gs, sts, ms, vs, dxs):
         """Back-propagation through T recorded steps of ONE network on one [B, D] panel:
@@ -25,6 +39,8 @@ class BpttMixin(object):
         per step for all of them (l2o_cwlstm_bwd_multi) when every panel is tile-aligned
         (D % 16 == 0 or B == 1), else panel by panel."""
         eng = self.engine
+        if isinstance(net, networks.KernelDeepLSTM):
+            return self._bptt_kernel_net(net, acc, T, panels)
         b1, b2 = float(np.float32(self.beta1)), float(np.float32(self.beta2))
         spec = net.spec
         nl = len(spec.layers)
@@ -130,19 +146,8 @@ class BpttMixin(object):
                               carry_in=carry_in, carry_out=carry_out)
                     eng.bwd_step_generic(spec, gen, io, b1 ** k, b2 ** k, N)
                     carry_in, carry_out = carry_out, carry_in
-                    def atb_blocks(A, Bmat):               # l2o_atb holds a KA <= 112 x KB <= 192 result in registers
-                        ka, kb = A.shape[1], Bmat.shape[1]
-                        if ka <= 112 and kb <= 192:
-                            return eng.atb(A, Bmat)
-                        res = eng.empty(ka, kb)              # (blocks copied into place: buffer plumbing)
-                        for r0 in range(0, ka, 96):
-                            Ab = A[:, r0:r0 + 96].contiguous()
-                            for c0 in range(0, kb, 176):
-                                blk = eng.atb(Ab, Bmat[:, c0:c0 + 176].contiguous())
-                                res[r0:r0 + blk.shape[0], c0:c0 + blk.shape[1]].copy_(blk)
-                        return res
                     for l in range(nl):
-                        add("lstm_%d" % (l + 1), "w_gates", atb_blocks(io["act"][l], io["dz"][l]))
+                        add("lstm_%d" % (l + 1), "w_gates", _atb_blocks(eng, io["act"][l], io["dz"][l]))
                         add("lstm_%d" % (l + 1), "b_gates", eng.colsum(io["dz"][l]))
                     dd = io["dd"].view(N, 1)
                     add("linear", "w", eng.atb(io["h_last"], dd))
@@ -289,13 +294,50 @@ class BpttMixin(object):
             else:
                 srcs.pop(id(acc), None)
 
+    def _bptt_kernel_net(self, net, acc, T, panels):
+        """Back-propagation through the T recorded steps of a networks.KernelDeepLSTM, variable by variable: one
+        l2o_klstm_bwd_step per step, which recomputes the step and emits the operands of the weight gradients; the
+        products act_l^T dz_l, h_last^T dd (l2o_atb) and the column sums are accumulated over the steps here.  The
+        optimizee gradients are constants (first order): dL/d(delta_t) is the suffix sum of the recorded gradients."""
+        eng = self.engine
+        if not hasattr(eng, "klstm_bwd_step"):
+            raise NotImplementedError("this engine has no BPTT for KernelDeepLSTM")
+        Hs, K = list(net.layers), net.output_size
+        ins = [net.in_dim] + Hs[:-1]
+
+        def add(mod, var, val):
+            k = (mod, var)
+            if k not in acc:
+                acc[k] = val
+            else:
+                eng.lincomb(acc[k], acc[k], 1.0, val.reshape(acc[k].shape), 1.0)
+
+        for pn in panels:
+            N, D = pn["N"], pn["B"] * pn["D"]
+            dxs = eng.empty(max(T, 1), D)
+            eng.suffix_sums([pn["gs"][t].reshape(D) for t in range(T)], pn["g_final"].reshape(D), dxs)
+            nst = 2 * N * sum(Hs)
+            io = dict(act=[eng.empty(N, i + h) for i, h in zip(ins, Hs)], dz=[eng.empty(N, 4 * h) for h in Hs],
+                      tc=eng.empty(N * sum(Hs)), h_last=eng.empty(N, Hs[-1]), dd=eng.empty(N, K))
+            carry_in, carry_out = eng.zeros(nst), eng.zeros(nst)
+            for t in reversed(range(T)):
+                io.update(g=pn["gs"][t].reshape(D), st_prev=pn["sts"][t], dx_next=dxs[t], carry_in=carry_in,
+                          carry_out=carry_out)
+                eng.klstm_bwd_step(net, io, N)
+                carry_in, carry_out = carry_out, carry_in
+                for l in range(len(Hs)):
+                    add("lstm_%d" % (l + 1), "w_gates", _atb_blocks(eng, io["act"][l], io["dz"][l]))
+                    add("lstm_%d" % (l + 1), "b_gates", eng.colsum(io["dz"][l]))
+                add("linear", "w", _atb_blocks(eng, io["h_last"], io["dd"]))
+                add("linear", "b", eng.colsum(io["dd"]))
+
     def _bptt_panel_sets(self, rec):
         """The BPTT panels of one recorded unroll, by network: {net key: (net, [panel dicts as _bptt_panels takes])}."""
         by_net = {}                                        # variables that share a network go through ONE launch per step
         mlp_terms = {}                                     # second derivatives: what the panels of one MLP term share
         for si, s in enumerate(self.slots):
             net = s.net
-            if not isinstance(net, networks.StandardDeepLSTM):
+            if not isinstance(net, (networks.StandardDeepLSTM, networks.KernelDeepLSTM)):
                 continue
             j = s.var_index
             B, D = rec["shapes"][j]
@@ -305,6 +347,8 @@ class BpttMixin(object):
             pn = dict(B=B, D=D, gs=[g[j] for g in rec["g"]], sts=[st[si] for st in rec["st"]],
                       ms=[m[si] for m in rec["m"]], vs=[v[si] for v in rec["v"]], dxs=None,
                       g_final=rec["g_final"][j].reshape(N))
+            if isinstance(net, networks.KernelDeepLSTM):
+                pn["N"] = net.rows_of(self.x[j])           # the filters: rows of the net, columns of the [K, N] variable
             if self.second_derivatives:                    # dL/dx_t picks up H(x_t) . dL/dg_t (DM/meta.py:328-329)
                 term = self.term_of[self.x[j].decl.name]
                 pn.update(second=True, desc=rec["descs"][j], xs=[x[j] for x in rec["x"]], weight=term.weight)

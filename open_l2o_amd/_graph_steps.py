@@ -434,6 +434,10 @@ class StepPlanMixin(object):
                         hm, hv = eng.empty(T + 1, ms[si].numel()), eng.empty(T + 1, vs[si].numel())
                         hm[0].copy_(ms[si].reshape(-1)); hv[0].copy_(vs[si].reshape(-1))
                     chain[si] = (hs, hm, hv)
+                elif isinstance(s.net, networks.KernelDeepLSTM):      # the same chain, through l2o_klstm_step's state_in / _out
+                    hs = eng.empty(T + 1, states[si].buf.numel())
+                    hs[0].copy_(states[si].buf)
+                    chain[si] = (hs, None, None)
         for t in range(T):
             if record is not None:
                 grads[:] = [hg[t] for hg in hist_g]
@@ -462,6 +466,12 @@ class StepPlanMixin(object):
                         seg = (grads[j], ms[si], vs[si], None if states[si].packed is None else states[si].packed,
                                panels[j], B, D)
                     groups.setdefault(id(s.net), (s.net, []))[1].append(seg)
+                elif isinstance(s.net, networks.KernelDeepLSTM):
+                    # one l2o_klstm_step per (net, filter variable): the [K, N] matrix the variable is in memory
+                    st_in = st_out = states[si].buf
+                    if chain is not None:
+                        st_in, st_out = chain[si][0][t], chain[si][0][t + 1]
+                    eng.klstm_step(s.net, grads[j].reshape(-1), st_in, st_out, panels[j].view(-1), states[si].N)
                 else:                                    # Sgd / Adam baseline nets
                     delta, states[si] = s.net(grads[j], states[si])
                     panels[j].add_(delta.view(B, D))
@@ -480,7 +490,7 @@ class StepPlanMixin(object):
         if record is not None:
             record["g_final"] = list(grads)
             for si, (hs, hm, hv) in chain.items():         # the variables take the end of the chain
-                states[si].packed.copy_(hs[T])
+                (states[si].packed if isinstance(states[si], PackedState) else states[si].buf).copy_(hs[T])
                 if hm is not None:
                     ms[si].copy_(hm[T].view(ms[si].shape)); vs[si].copy_(hv[T].view(vs[si].shape))
 

@@ -40,6 +40,8 @@
 #include "l2o_confocal.h"
 #include "l2o_confocal_unroll.h"
 #include "l2o_generic.h"
+#include "l2o_klstm.h"
+#include "../../include/l2o_klstm_abi.h"
 #include "l2o_atb.h"
 #include "l2o_bwd.h"
 #include "l2o_bwd_mfma.h"
@@ -1372,6 +1374,87 @@ int l2o_vgg16_fg(const l2o_vgg16* m, const int32_t* indices, const float* const*
       std::swap(dy, other);
     }
   }
+  HIP_TRY(hipGetLastError());
+  return L2O_OK;
+}
+
+// ---- KernelDeepLSTM: one LSTM per convolution filter (csrc/l2o_klstm.h, include/l2o_klstm_abi.h) ----------------------------
+static bool klstm_ok(const l2o_klstm_net* n) {
+  if (!n || n->flags != 0) return false;
+  if (n->kw < 1 || n->kw > L2O_KLSTM_MAX_SIDE || n->kh < 1 || n->kh > L2O_KLSTM_MAX_SIDE) return false;
+  if (n->n_layers < 1 || n->n_layers > L2O_KLSTM_MAX_LAYERS) return false;
+  for (int l = 0; l < n->n_layers; ++l)
+    if (n->hidden[l] < 4 || n->hidden[l] > L2O_KLSTM_MAX_HIDDEN || n->hidden[l] % 4) return false;
+  return n->preprocess == L2O_PRE_IDENTITY || n->preprocess == L2O_PRE_LOGSIGN;
+}
+static int klstm_check(const char* who, const l2o_klstm_net* n, int64_t N) {
+  if (!klstm_ok(n) || N < 1)
+    return fail(L2O_ERR_UNSUPPORTED, "%s: kw, kh in [1, %d], 1 or 2 layers of a width that is a multiple of 4 in [4, %d], "
+                "preprocess identity or LogAndSign, flags 0, N >= 1", who, L2O_KLSTM_MAX_SIDE, L2O_KLSTM_MAX_HIDDEN);
+  for (int l = 0; l < n->n_layers; ++l)
+    if (!n->w_gates[l] || !n->b_gates[l]) return fail(L2O_ERR_ARG, "%s: NULL weights of layer %d", who, l);
+  if (!n->w_lin || !n->b_lin) return fail(L2O_ERR_ARG, "%s: NULL output Linear", who);
+  return L2O_OK;
+}
+int l2o_klstm_supported(const l2o_klstm_net* net) { return klstm_ok(net) ? 1 : 0; }
+size_t l2o_klstm_state_floats(const l2o_klstm_net* net, int64_t N) {
+  if (!klstm_ok(net) || N < 1) return 0;
+  size_t n = 0;
+  for (int l = 0; l < net->n_layers; ++l) n += 2 * (size_t)N * (size_t)net->hidden[l];
+  return n;
+}
+int l2o_klstm_step(const l2o_klstm_net* net, const float* g, const float* state_in, float* state_out, float* x, int64_t N,
+                   void* stream) {
+  int rc = klstm_check("l2o_klstm_step", net, N);
+  if (rc) return rc;
+  if (!g || !state_in || !state_out || !x) return fail(L2O_ERR_ARG, "l2o_klstm_step: NULL argument");
+  KlParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.K = net->kw * net->kh;
+  p.pre = net->preprocess;
+  p.in = p.pre == L2O_PRE_LOGSIGN ? 2 * p.K : p.K;
+  p.in_pad = (p.in + 3) / 4 * 4;
+  p.n_layers = net->n_layers;
+  for (int l = 0; l < net->n_layers; ++l) { p.H[l] = net->hidden[l]; p.wg[l] = net->w_gates[l]; p.bg[l] = net->b_gates[l]; }
+  p.tanh_output = net->tanh_output;
+  p.scale = (float)net->scale;
+  p.k_inv = net->logsign_k != 0.0 ? (float)(1.0 / net->logsign_k) : 0.0f;
+  p.exp_k = (float)std::exp(net->logsign_k);
+  p.wl = net->w_lin; p.bl = net->b_lin;
+  p.g = g; p.st_in = state_in; p.st_out = state_out; p.x = x; p.N = (long)N;
+  const int64_t ntiles = (N + 15) / 16;
+  if (ntiles > 0x7fffffff / 16) return fail(L2O_ERR_UNSUPPORTED, "l2o_klstm_step: N %lld is too large", (long long)N);
+  p.ntiles = (int)ntiles;
+  const int64_t wgs = (ntiles + kKlWaves - 1) / kKlWaves;
+  return launch(k_klstm_step, dim3((unsigned)(wgs < kKlMaxBlocks ? wgs : kKlMaxBlocks)), dim3(kKlThreads),
+                sizeof(float) * (size_t)kl_lds_floats(p), (hipStream_t)stream, p);
+}
+int l2o_klstm_bwd_step(const l2o_klstm_net* net, const l2o_klstm_bwd_io* io, int64_t N, void* stream) {
+  int rc = klstm_check("l2o_klstm_bwd_step", net, N);
+  if (rc) return rc;
+  if (!io || !io->g || !io->st_prev || !io->dx_next || !io->carry_in || !io->carry_out || !io->tc || !io->h_last || !io->dd ||
+      io->carry_in == io->carry_out)
+    return fail(L2O_ERR_ARG, "l2o_klstm_bwd_step: bad argument");
+  KlBwdParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.K = net->kw * net->kh;
+  p.pre = net->preprocess;
+  p.in = p.pre == L2O_PRE_LOGSIGN ? 2 * p.K : p.K;
+  p.n_layers = net->n_layers;
+  for (int l = 0; l < net->n_layers; ++l) {
+    if (!io->act[l] || !io->dz[l]) return fail(L2O_ERR_ARG, "l2o_klstm_bwd_step: NULL act / dz of layer %d", l);
+    p.H[l] = net->hidden[l]; p.wg[l] = net->w_gates[l]; p.bg[l] = net->b_gates[l];
+    p.act[l] = io->act[l]; p.dz[l] = io->dz[l];
+  }
+  p.tanh_output = net->tanh_output;
+  p.scale = (float)net->scale;
+  p.k_inv = net->logsign_k != 0.0 ? (float)(1.0 / net->logsign_k) : 0.0f;
+  p.exp_k = (float)std::exp(net->logsign_k);
+  p.wl = net->w_lin; p.bl = net->b_lin;
+  p.g = io->g; p.st_prev = io->st_prev; p.dx_next = io->dx_next; p.carry_in = io->carry_in; p.carry_out = io->carry_out;
+  p.tc = io->tc; p.h_last = io->h_last; p.dd = io->dd; p.N = (long)N;
+  hipLaunchKernelGGL(k_klstm_bwd_step, dim3((unsigned)((N + kKlBwdThreads - 1) / kKlBwdThreads)), dim3(kKlBwdThreads), 0,
+                     (hipStream_t)stream, p);
   HIP_TRY(hipGetLastError());
   return L2O_OK;
 }

@@ -92,6 +92,7 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
                 if rnnprop != (net.spec.kind == _abi.NET_RNNPROP):
                     raise ValueError("RNNprop networks need the RNNProp MetaOptimizer (meta_rnnprop_eval / "
                                      "meta_rnnprop_train) and vice versa")
+        self._check_kernel_nets()
 
         # placeholders of the train / RNNProp forks (DM/meta_dm_train.py:336-338,
         # DM/meta_rnnprop_eval.py: scale + step)
@@ -117,6 +118,25 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
         self._fx_cache = {}
         self.last_path = None
         self.second_derivatives = False
+
+    def _check_kernel_nets(self):
+        """What a graph with a networks.KernelDeepLSTM is refused for, at graph build and with the reason: the RNNProp
+        optimizers (their nets take the pair (m~, g~)), a sharded graph (the filters of a variable are not split over
+        ranks), and a variable that is not a [kw, kh, c_in, c_out] filter of the net's kernel_shape (ValueError)."""
+        for subset, key in zip(self.subsets, self.net_keys):
+            net = self.nets[key]
+            if not isinstance(net, networks.KernelDeepLSTM):
+                continue
+            if self.rnnprop:
+                raise NotImplementedError("KernelDeepLSTM (net %r) is not implemented for the RNNProp optimizers" % (key,))
+            if self.sharded:
+                raise NotImplementedError("KernelDeepLSTM (net %r) is not implemented for a sharded graph (world size %d): "
+                                          "the filters of a variable are not split over ranks" % (key, self.world))
+            for j in subset:
+                net.rows_of(self.x[j])
+
+    def _has_kernel_net(self):
+        return any(isinstance(net, networks.KernelDeepLSTM) for net in self.nets.values())
 
     def _shard_of(self, decls):
         """(sharded, this rank's contiguous slice of the batch or None): the batched analytic problems under torch.distributed."""
@@ -179,6 +199,8 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
                 s.state = PackedState.zeros(eng, B, D, s.net.spec.layers)
                 if self.rnnprop:
                     s.m, s.v = eng.zeros(B, D), eng.zeros(B, D)
+            elif isinstance(s.net, networks.KernelDeepLSTM):
+                s.state = s.net.initial_state_for_inputs(var, engine=eng)
             else:
                 s.state = s.net.initial_state_for_inputs(var.value)
         self._initialized = True
@@ -498,7 +520,8 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
         xs = [v.value if commit else v.value.clone() for v in self.x]
         states, ms, vs = [], [], []
         for s in self.slots:
-            states.append(s.state.clone() if isinstance(s.state, PackedState) and not commit else s.state)
+            states.append(s.state.clone() if isinstance(s.state, (PackedState, networks.KernelState)) and not commit
+                          else s.state)
             ms.append(s.m if (commit or s.m is None) else s.m.clone())
             vs.append(s.v if (commit or s.v is None) else s.v.clone())
         # (a step-path optimizee has no descriptor: _run_steps evaluates it at x * scale, DM/meta_dm_train.py:384)
@@ -754,6 +777,8 @@ class UnrollGraph(BpttMixin, AdamMixin, StepPlanMixin, object):
         for s in slots:
             if isinstance(s.state, PackedState) and s.state.packed is not None:
                 ts.append(s.state.packed)
+            elif isinstance(s.state, networks.KernelState):
+                ts.append(s.state.buf)
             if s.m is not None:
                 ts += [s.m, s.v]
         return ts
@@ -795,6 +820,9 @@ class MtUnroll(object):
         self.sizes = [int(sum(int(np.prod(graph.x[j].shape)) for j in subset)) for subset in graph.subsets]
         self.total = int(sum(self.sizes))
         for k in self.keys:
+            if isinstance(graph.nets[k], networks.KernelDeepLSTM):
+                raise NotImplementedError("imitation unrolls are not implemented for KernelDeepLSTM (net %r): they feed a "
+                                          "flat [T, P] gradient sequence per subset, not filters" % (k,))
             if not isinstance(graph.nets[k], networks.StandardDeepLSTM):
                 raise NotImplementedError("imitation unrolls are implemented for the LSTM optimizer networks")
         self.labels = [Placeholder("mt%d_label_subset%d" % (mti, j), (T, P)) for j, P in enumerate(self.sizes)]
@@ -970,7 +998,11 @@ class MetaOptimizer(object):
     def _check_second_derivatives(graph):
         """What second_derivatives=True is implemented for, refused here -- at graph build, with the reason -- and not in
         the middle of the first train step: the analytic optimizees (l2o_problem_hvp) under any net the BPTT takes, and
-        problems.mnist (l2o_mlp_hvp) when ALL its variables are stepped by ONE (20, 20) LSTM net."""
+        problems.mnist (l2o_mlp_hvp) when ALL its variables are stepped by ONE (20, 20) LSTM net.  Never with a
+        KernelDeepLSTM: its backward step emits no input adjoint dL/dg_t."""
+        if graph._has_kernel_net():
+            raise NotImplementedError("second_derivatives=True is not implemented for a graph with a KernelDeepLSTM: "
+                                      "l2o_klstm_bwd_step is the first-order step (no dL/dg_t)")
         if any(is_multivar(t.kind) and t.kind != _abi.PROB_MLP for t in graph.terms):
             raise NotImplementedError("second_derivatives=True is implemented for the analytic optimizees and problems.mnist "
                                       "(problems.mnist_conv / problems.cifar10 / problems.LeNet / "

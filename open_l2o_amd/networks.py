@@ -8,7 +8,7 @@ of ``networks.save`` (DM/networks.py:47-62):
 ``{module_name: {variable_name: ndarray}}`` with Sonnet's module / variable names
 (``lstm_1/w_gates`` ...), so weights trained by the TF reference drop in and
 vice-versa.  All arithmetic happens in the HIP kernels; ``net(inputs, state)``
-runs ``l2o_cwlstm_step`` eagerly on device tensors.
+runs ``l2o_cwlstm_step`` (``KernelDeepLSTM``: ``l2o_klstm_step``) eagerly on device tensors.
 """
 from __future__ import annotations
 
@@ -125,7 +125,7 @@ class StandardDeepLSTM(Network):
                  scale=1.0, initializer=None, name="deep_lstm", tanh_output=False):
         if output_size != 1:
             raise NotImplementedError("only coordinate-wise (output_size=1) networks are implemented; "
-                                      "KernelDeepLSTM / StandardDeepLSTM are outside the hot path")
+                                      "conv filters take KernelDeepLSTM")
         self.name = name
         self._output_size = output_size
         self._scale = scale
@@ -332,11 +332,145 @@ class RNNprop(StandardDeepLSTM):
         return delta.reshape(g.shape), nxt
 
 
-class KernelDeepLSTM(StandardDeepLSTM):
-    """`DeepLSTM` for convolutional filters (DM/networks.py:303-351): out of scope."""
+class KernelState(object):
+    """LSTM state of one ``[kw, kh, c_in, c_out]`` variable under a `KernelDeepLSTM`: N = c_in * c_out rows, in the
+    unit-major device layout of ``l2o_klstm_state_floats`` (per layer hidden [H][N] then cell [H][N]); ``unpack()`` gives
+    the reference structure ``((hidden_1, cell_1), ...)`` with [N, H] arrays."""
 
-    def __init__(self, kernel_shape, name="kernel_deep_lstm", **kwargs):
-        raise NotImplementedError("KernelDeepLSTM (conv-filter optimizee nets) is outside the hot path")
+    def __init__(self, engine, buf, N, layers):
+        self.engine, self.buf, self.N, self.layers = engine, buf, int(N), tuple(int(h) for h in layers)
+
+    @classmethod
+    def zeros(cls, engine, N, layers):
+        return cls(engine, engine.zeros(2 * int(N) * sum(int(h) for h in layers)), N, layers)
+
+    def clone(self):
+        return KernelState(self.engine, self.buf.clone(), self.N, self.layers)
+
+    def zero_(self):
+        self.buf.zero_()
+
+    def unpack(self):
+        out, off = [], 0
+        for H in self.layers:
+            out.append((self.buf[off:off + H * self.N].view(H, self.N).t(),
+                        self.buf[off + H * self.N:off + 2 * H * self.N].view(H, self.N).t()))
+            off += 2 * H * self.N
+        return tuple(out)
+
+
+class KernelDeepLSTM(Network):
+    """`DeepLSTM` for convolutional filters.  DM/networks.py:303-351.
+
+    One LSTM per (c_in, c_out) filter of a ``[kw, kh, c_in, c_out]`` variable: it reads the kw * kh gradients of the
+    filter's patch at once and emits the whole patch of updates.  In memory the variable is a [K = kw * kh][N = c_in *
+    c_out] matrix (row j = a * kh + b, column n = ci * c_out + co), which is what the reference's transpose / reshape /
+    transpose-back indexes: no data moves.  The step is ``l2o_klstm_step`` (csrc/l2o_klstm.h), the gate products on the
+    matrix cores.  Not a `StandardDeepLSTM` here: that class means "coordinate-wise, packed state" to the unroll graph.
+
+    Accepted: kw, kh in [1, 7], one or two layers of a width that is a multiple of 4 in [4, 32], preprocess identity or
+    LogAndSign; anything else raises NotImplementedError."""
+
+    MAX_SIDE, MAX_LAYERS, MAX_HIDDEN = 7, 2, 32
+
+    def __init__(self, kernel_shape, layers, preprocess_name="identity", preprocess_options=None, scale=1.0,
+                 initializer=None, tanh_output=False, name="kernel_deep_lstm"):
+        self.name = name
+        self._kernel_shape = tuple(int(k) for k in kernel_shape)
+        self._layers = tuple(int(h) for h in layers)
+        self._scale = float(scale)
+        self._preprocess_name = preprocess_name
+        self.tanh_output = bool(tanh_output)
+        preprocess_options = dict(preprocess_options or {})
+        if len(self._kernel_shape) != 2 or not all(1 <= k <= self.MAX_SIDE for k in self._kernel_shape):
+            raise NotImplementedError("KernelDeepLSTM: kernel_shape (kw, kh) with both in [1, %d] (got %r)"
+                                      % (self.MAX_SIDE, tuple(kernel_shape)))
+        if not 1 <= len(self._layers) <= self.MAX_LAYERS or \
+                not all(4 <= h <= self.MAX_HIDDEN and h % 4 == 0 for h in self._layers):
+            raise NotImplementedError("KernelDeepLSTM: one or two layers, every width a multiple of 4 in [4, %d] (got %r)"
+                                      % (self.MAX_HIDDEN, tuple(layers)))
+        K = self.output_size = self._kernel_shape[0] * self._kernel_shape[1]
+        if preprocess_name == "LogAndSign":
+            self.preprocess, in_dim, self.logsign_k = _abi.PRE_LOGSIGN, 2 * K, float(preprocess_options["k"])
+        elif preprocess_name == "identity":
+            self.preprocess, in_dim, self.logsign_k = _abi.PRE_IDENTITY, K, 0.0
+        elif preprocess_name == "fc":
+            raise NotImplementedError("KernelDeepLSTM with preprocess_name='fc' is not implemented (the reference's Linear "
+                                      "on the [N, kw, kh, 1] input cannot be built either)")
+        else:
+            raise ValueError("preprocess_name %r is not implemented (identity | LogAndSign)" % (preprocess_name,))
+        self.in_dim = in_dim
+        variables = collections.OrderedDict()
+        size_in = in_dim
+        for i, size in enumerate(self._layers, start=1):
+            lname = "lstm_{}".format(i)
+            init = _get_layer_initializers(initializer, lname, ("w_gates", "b_gates"))
+            shape_w = (size_in + size, 4 * size)
+            variables[lname] = {
+                "w_gates": _materialize(init.get("w_gates"), shape_w, lambda s=shape_w: _truncated_normal(s, s[0])),
+                "b_gates": _materialize(init.get("b_gates"), (4 * size,), lambda n=4 * size: np.zeros((n,), np.float32)),
+            }
+            size_in = size
+        init = _get_layer_initializers(initializer, "linear", ("w", "b"))
+        variables["linear"] = {
+            "w": _materialize(init.get("w"), (size_in, K), lambda: _truncated_normal((size_in, K), size_in)),
+            "b": _materialize(init.get("b"), (K,), lambda: np.zeros((K,), np.float32)),
+        }
+        self.variables = variables
+        self._wversion = 0
+        self._wdev = None
+
+    @property
+    def kernel_shape(self):
+        return self._kernel_shape
+
+    @property
+    def layers(self):
+        return self._layers
+
+    @property
+    def scale(self):
+        return self._scale
+
+    def assign(self, module_name, variable_name, value):
+        """Overwrite one weight (MetaOptimizer.restore and the Adam meta-step)."""
+        cur = self.variables[module_name][variable_name]
+        self.variables[module_name][variable_name] = np.asarray(value, np.float32).reshape(cur.shape).copy()
+        self._wversion += 1
+
+    def device_net(self, engine):
+        """The engine's device copy of the weights (HipEngine: behind a struct l2o_klstm_net), rebuilt when the weights'
+        version has moved: assign() mutates the dict in place, so its identity says nothing."""
+        ent = self._wdev
+        if ent is None or ent[0] is not engine or ent[1] != self._wversion:
+            ent = self._wdev = (engine, self._wversion, engine.klstm_net(self))
+        return ent[2]
+
+    def rows_of(self, inputs):
+        """N = c_in * c_out of a [kw, kh, c_in, c_out] variable; ValueError for any other shape (the reference fails in
+        its reshape)."""
+        shape = tuple(int(d) for d in inputs.shape)
+        if len(shape) != 4 or shape[:2] != self._kernel_shape:
+            raise ValueError("KernelDeepLSTM %r with kernel_shape %r cannot step a variable of shape %r"
+                             % (self.name, self._kernel_shape, shape))
+        return shape[2] * shape[3]
+
+    def initial_state_for_inputs(self, inputs, **kwargs):
+        engine = kwargs.pop("engine", None) or _engine.default_engine()
+        return KernelState.zeros(engine, self.rows_of(inputs), self._layers)
+
+    def __call__(self, inputs, prev_state):
+        """``net(g4d, state) -> (delta4d, next_state)``: one launch of l2o_klstm_step on a zeroed update buffer and a new
+        state buffer; the arguments are not modified."""
+        engine = prev_state.engine
+        N = self.rows_of(inputs)
+        if prev_state.N != N or prev_state.layers != self._layers:
+            raise ValueError("KernelDeepLSTM: the state is for %d rows of layers %r, the inputs have %d rows"
+                             % (prev_state.N, prev_state.layers, N))
+        delta = engine.zeros(self.output_size * N)
+        nxt = KernelState(engine, engine.empty(prev_state.buf.numel()), N, self._layers)
+        engine.klstm_step(self, inputs.reshape(-1).contiguous(), prev_state.buf, nxt.buf, delta, N)
+        return delta.reshape(inputs.shape), nxt
 
 
 class Sgd(Network):
