@@ -4,6 +4,11 @@ This is the ONLY way the Python host reaches the compute path: there is no
 PyTorch / NumPy fallback.  If ``libl2o_hip.so`` is missing (not built) every
 entry point raises ``RuntimeError`` -- the product path must fail loudly when
 the HIP extension is absent.
+
+Two tables carry everything that is per symbol: ``PROTOTYPES`` (header ->
+symbol -> restype / argtypes; ``lib()`` declares exactly these and refuses a
+library that lacks one) and ``STEP_FG`` (the (struct, stem) pair of every
+step-path optimizee, from which their two prototypes each are made).
 """
 from __future__ import annotations
 
@@ -26,35 +31,6 @@ PROB_LENET = 8
 PROB_CONFOCAL = 9
 PROB_VGG16 = 10           # include/l2o_vgg16_abi.h (added after ABI v15)
 PROB_NAS = 11             # include/l2o_nas_abi.h (added after ABI v15)
-
-# every symbol include/l2o_abi.h declares (tests check the library exports all of them)
-SYMBOLS = (
-    "l2o_abi_version", "l2o_last_error", "l2o_build_id", "l2o_last_unroll_form", "l2o_last_unroll_variant", "l2o_coresident_workgroups", "l2o_wpack_floats", "l2o_wpack_host",
-    "l2o_state_floats", "l2o_state_pack", "l2o_state_unpack", "l2o_problem_fg", "l2o_problem_hvp", "l2o_mlp_fg",
-    "l2o_mlp_scratch_floats", "l2o_mlp_unroll", "l2o_mlp_unroll_record", "l2o_mlp_unroll_supported", "l2o_mlp_unroll_workspace_bytes",
-    "l2o_mlp_unroll_multi", "l2o_mlp_unroll_multi_record", "l2o_mlp_unroll_multi_supported", "l2o_mlp_unroll_multi_workspace_bytes",
-    "l2o_mlp_deep_fg", "l2o_mlp_deep_scratch_floats", "l2o_mnist_conv_fg", "l2o_mnist_conv_scratch_floats",
-    "l2o_cifar_conv_fg", "l2o_cifar_conv_scratch_floats", "l2o_lenet_fg", "l2o_lenet_scratch_floats",
-    "l2o_confocal_fg", "l2o_confocal_scratch_floats",
-    "l2o_cwlstm_step", "l2o_cwlstm_step_multi", "l2o_cwlstm_step_generic", "l2o_cwlstm_bwd_step_generic", "l2o_gen_state_floats", "l2o_cwlstm_bwd_step", "l2o_cwlstm_bwd_multi", "l2o_cwlstm_bwd_unroll", "l2o_cwlstm_bwd_unroll_compact", "l2o_cwlstm_wgrad_compact", "l2o_unroll", "l2o_unroll_record", "l2o_unroll_reduce", "l2o_unroll_workspace_init", "l2o_unroll_workspace_layout", "l2o_cwlstm_wgrad", "l2o_cwlstm_wgrad_dims", "l2o_unroll_supported", "l2o_unroll_record_supported", "l2o_adam_step", "l2o_adam_step_guarded", "l2o_adam_step_gather", "l2o_wpack_device", "l2o_unroll_workspace_bytes",
-    "l2o_unroll_status", "l2o_reduce_fx", "l2o_atb", "l2o_atb_workspace_bytes",
-    "l2o_suffix_sums", "l2o_colsum", "l2o_colsum_scratch_floats", "l2o_lincomb", "l2o_rnnprop_input_adjoint",
-)
-# ... and every symbol include/l2o_confocal_unroll_abi.h declares (the fused confocal unroll, added after ABI v15)
-CONFOCAL_UNROLL_SYMBOLS = ("l2o_confocal_unroll", "l2o_confocal_unroll_record", "l2o_confocal_unroll_supported",
-                           "l2o_confocal_unroll_scratch_floats")
-# ... and include/l2o_confocal_multi_abi.h (several confocal instances per fused launch); bound when the library has them
-CONFOCAL_MULTI_SYMBOLS = ("l2o_confocal_unroll_multi", "l2o_confocal_unroll_multi_record",
-                          "l2o_confocal_unroll_multi_supported", "l2o_confocal_unroll_multi_scratch_floats")
-# ... and include/l2o_mlp_hvp_abi.h (the Hessian-vector product of the MLP optimizee: second_derivatives=True on problems.mnist)
-MLP_HVP_SYMBOLS = ("l2o_mlp_hvp", "l2o_mlp_hvp_scratch_floats")
-# ... and include/l2o_vgg16_abi.h (problems.vgg16_cifar10); bound when the library has them
-VGG16_SYMBOLS = ("l2o_vgg16_fg", "l2o_vgg16_scratch_floats")
-# ... and include/l2o_nas_abi.h (problems.NAS); bound when the library has them
-NAS_SYMBOLS = ("l2o_nas_fg", "l2o_nas_scratch_floats")
-# ... and include/l2o_klstm_abi.h (networks.KernelDeepLSTM); bound when the library has them
-KLSTM_SYMBOLS = ("l2o_klstm_supported", "l2o_klstm_state_floats", "l2o_klstm_step", "l2o_klstm_bwd_step")
-
 
 # option ids of include/l2o_abi.h ("options": per call, caller-owned -- the LIBRARY keeps no option state since ABI v9).
 # This binding keeps the caller's side of it: one process-wide dict of non-default values (applied from the L2O_*
@@ -244,15 +220,11 @@ class Vgg16(C.Structure):
                 ("images", C.c_void_p), ("labels", C.c_void_p)]
 
 
-# the step-path optimizees: (descriptor struct, symbol stem).  Every one exports <stem>_scratch_floats(const struct *) ->
-# size_t and <stem>_fg(const struct *, 6 pointers) -> int: lib() declares both from this list
+# the step-path optimizees: (descriptor struct, symbol stem), in the order of their problem kinds.  Every one exports
+# <stem>_fg(const struct *, 6 pointers) -> int and <stem>_scratch_floats(const struct *) -> size_t: PROTOTYPES holds both per
+# pair.  A new step-path optimizee appends its pair here and gives it a place in PROTOTYPES.
 STEP_FG = ((MlpDeep, "l2o_mlp_deep"), (MnistConv, "l2o_mnist_conv"), (CifarConv, "l2o_cifar_conv"), (Lenet, "l2o_lenet"),
-           (Confocal, "l2o_confocal"))
-# ... and those added after ABI v15 (the same two exports per stem), declared when the library has them
-STEP_FG_LATER = ((Vgg16, "l2o_vgg16"),)
-# ... and the OPEN list of every (struct, stem) pair declared that way: a new step-path optimizee appends its pair here and
-# nothing else in this module changes
-STEP_FG_OPEN = list(STEP_FG_LATER) + [(Nas, "l2o_nas")]
+           (Confocal, "l2o_confocal"), (Vgg16, "l2o_vgg16"), (Nas, "l2o_nas"))
 
 
 class GenNet(C.Structure):
@@ -321,6 +293,115 @@ class UnrollHist(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("st", "g", "m", "v", "g_final")]
 
 
+def _step_fg(pairs):
+    """The two prototypes of every (struct, stem) pair of STEP_FG in `pairs`, in the headers' order."""
+    out = {}
+    for struct, stem in pairs:
+        out[stem + "_fg"] = (C.c_int, [C.POINTER(struct)] + [C.c_void_p] * 6)
+        out[stem + "_scratch_floats"] = (C.c_size_t, [C.POINTER(struct)])
+    return out
+
+
+def _prototypes():
+    P, vp, i32, i64, dbl, flt, I, Z = C.POINTER, C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float, C.c_int, C.c_size_t
+    cfg, prob, mlp, conf = P(NetCfg), P(Problem), P(Mlp), P(Confocal)
+    bwd_unroll = [cfg, P(NetWeights), P(BwdUnrollSeg), i32, vp, i32, i64, vp, vp, vp, vp, vp]
+    return {
+        "l2o_abi.h": {
+            "l2o_abi_version": (I, []),
+            "l2o_last_error": (C.c_char_p, []),
+            "l2o_build_id": (C.c_char_p, []),
+            "l2o_last_unroll_form": (I, []),
+            "l2o_last_unroll_variant": (I, []),
+            "l2o_coresident_workgroups": (i32, [vp, vp]),
+            "l2o_wpack_floats": (Z, [cfg]),
+            "l2o_wpack_host": (I, [cfg] + [vp] * 9),
+            "l2o_state_floats": (Z, [i64, i64]),
+            "l2o_state_pack": (I, [vp, vp, vp, vp, vp, i64, i64, vp]),
+            "l2o_state_unpack": (I, [vp, vp, vp, vp, vp, i64, i64, vp]),
+            "l2o_problem_fg": (I, [prob, vp, vp, vp, vp]),
+            "l2o_problem_hvp": (I, [prob, vp, vp, vp, vp, vp]),
+            "l2o_mlp_fg": (I, [mlp] + [vp] * 12),
+            "l2o_mlp_scratch_floats": (Z, [mlp]),
+            "l2o_mlp_unroll": (I, [cfg, vp, mlp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+            "l2o_mlp_unroll_record": (I, [cfg, vp, mlp, vp, vp, vp, vp, vp, vp, i32, i32, vp, P(MlpHist), vp, vp]),
+            "l2o_mlp_unroll_supported": (I, [cfg, mlp, vp]),
+            "l2o_mlp_unroll_workspace_bytes": (Z, [mlp]),
+            "l2o_mlp_unroll_multi": (I, [cfg, vp, mlp, P(MlpInstance), i32, i32, i32, vp, vp]),
+            "l2o_mlp_unroll_multi_record": (I, [cfg, vp, mlp, P(MlpInstance), i32, i32, i32, P(MlpHist), vp, vp]),
+            "l2o_mlp_unroll_multi_supported": (I, [cfg, mlp, i32, vp]),
+            "l2o_mlp_unroll_multi_workspace_bytes": (Z, [mlp, i32]),
+            **_step_fg(STEP_FG[:5]),
+            "l2o_cwlstm_step": (I, [cfg, vp, vp, vp, vp, dbl, dbl, vp, vp, i64, i64, vp]),
+            "l2o_cwlstm_step_multi": (I, [cfg, vp, P(StepSeg), i32, dbl, dbl, vp]),
+            "l2o_cwlstm_step_generic": (I, [cfg, P(GenNet), vp, vp, vp, vp, dbl, dbl, vp, vp, i64, vp]),
+            "l2o_cwlstm_bwd_step_generic": (I, [cfg, P(GenNet), P(GenBwdIO), dbl, dbl, i64, vp]),
+            "l2o_gen_state_floats": (Z, [P(GenNet), i64]),
+            "l2o_cwlstm_bwd_step": (I, [cfg, P(NetWeights), P(BwdIO), dbl, dbl, i64, i64, vp]),
+            "l2o_cwlstm_bwd_multi": (I, [cfg, P(NetWeights), P(BwdSeg), i32, vp, vp, vp, vp, dbl, dbl, vp]),
+            "l2o_cwlstm_bwd_unroll": (I, bwd_unroll),
+            "l2o_cwlstm_bwd_unroll_compact": (I, bwd_unroll),
+            "l2o_cwlstm_wgrad_compact": (I, [cfg, vp, vp, i32, i64, vp, vp, vp]),
+            "l2o_unroll": (I, [cfg, vp, prob, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+            "l2o_unroll_record": (I, [cfg, vp, prob, vp, vp, vp, vp, i32, i32, vp, vp, P(UnrollHist), vp]),
+            "l2o_unroll_reduce": (I, [cfg, vp, prob, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, P(UnrollHist), vp]),
+            "l2o_unroll_workspace_init": (I, [vp, Z, vp]),
+            "l2o_unroll_workspace_layout": (i64, [cfg, prob]),
+            "l2o_cwlstm_wgrad": (I, [cfg, vp, vp, i64, vp, vp, vp]),
+            "l2o_cwlstm_wgrad_dims": (i32, [cfg, P(i32), P(i32)]),
+            "l2o_unroll_supported": (I, [cfg, prob]),
+            "l2o_unroll_record_supported": (I, [cfg, prob]),
+            "l2o_adam_step": (I, [vp, vp, vp, vp, i64, flt, dbl, dbl, dbl, vp]),
+            "l2o_adam_step_guarded": (I, [vp, vp, vp, vp, i64, flt, dbl, dbl, dbl, vp, vp]),
+            "l2o_adam_step_gather": (I, [vp, vp, vp, vp, vp, i64, flt, dbl, dbl, dbl, vp, vp]),
+            "l2o_wpack_device": (I, [cfg, P(NetWeights), vp, vp]),
+            "l2o_unroll_workspace_bytes": (Z, [cfg, prob, i32]),
+            "l2o_unroll_status": (I, [vp]),
+            "l2o_reduce_fx": (I, [vp, i32, i32, i32, vp, vp]),
+            "l2o_atb": (I, [vp, vp, i64, i32, i32, vp, vp, vp]),
+            "l2o_atb_workspace_bytes": (Z, [i64, i32, i32]),
+            "l2o_suffix_sums": (I, [vp, vp, vp, i64, i32, vp]),
+            "l2o_colsum": (I, [vp, i64, i64, i32, vp, i32, vp, vp]),
+            "l2o_colsum_scratch_floats": (Z, [i64, i32]),
+            "l2o_lincomb": (I, [vp, vp, flt, vp, flt, vp, flt, i64, vp]),
+            "l2o_rnnprop_input_adjoint": (I, [vp, i64, i32, i32, vp, vp, vp, vp, dbl, dbl, dbl, dbl, vp, vp, vp, i64, vp]),
+        },
+        "l2o_confocal_unroll_abi.h": {       # the fused confocal unroll
+            "l2o_confocal_unroll": (I, [cfg, vp, conf, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+            "l2o_confocal_unroll_record": (I, [cfg, vp, conf, vp, vp, vp, vp, vp, vp, i32, i32, vp, P(ConfocalHist), vp, vp]),
+            "l2o_confocal_unroll_supported": (I, [cfg, conf, vp]),
+            "l2o_confocal_unroll_scratch_floats": (Z, [conf, i32]),
+        },
+        "l2o_confocal_multi_abi.h": {        # several confocal instances per fused launch
+            "l2o_confocal_unroll_multi": (I, [cfg, vp, conf, P(ConfocalInstance), i32, i32, i32, vp, vp]),
+            "l2o_confocal_unroll_multi_record": (I, [cfg, vp, conf, P(ConfocalInstance), i32, i32, i32, P(ConfocalHist), vp, vp]),
+            "l2o_confocal_unroll_multi_supported": (I, [cfg, conf, i32, vp]),
+            "l2o_confocal_unroll_multi_scratch_floats": (Z, [conf, i32, i32]),
+        },
+        "l2o_mlp_hvp_abi.h": {               # the Hessian-vector product of the MLP optimizee (second_derivatives=True)
+            "l2o_mlp_hvp": (I, [P(MlpDeep)] + [vp] * 6),
+            "l2o_mlp_hvp_scratch_floats": (Z, [P(MlpDeep)]),
+        },
+        "l2o_vgg16_abi.h": _step_fg(STEP_FG[5:6]),           # problems.vgg16_cifar10
+        "l2o_nas_abi.h": _step_fg(STEP_FG[6:7]),             # problems.NAS
+        "l2o_klstm_abi.h": {                 # networks.KernelDeepLSTM
+            "l2o_klstm_supported": (I, [P(KlstmNet)]),
+            "l2o_klstm_state_floats": (Z, [P(KlstmNet), i64]),
+            "l2o_klstm_step": (I, [P(KlstmNet), vp, vp, vp, vp, i64, vp]),
+            "l2o_klstm_bwd_step": (I, [P(KlstmNet), P(KlstmBwdIO), i64, vp]),
+        },
+    }
+
+
+# THE prototype table: header of include/ -> {symbol: (restype, argtypes)}, every symbol the header declares, in this
+# binding's order.  declare() gives a loaded library exactly these prototypes and refuses one that lacks any of them; the
+# per-header tuples below are views of it (tests hold each against its header's text).
+PROTOTYPES = _prototypes()
+SYMBOLS, CONFOCAL_UNROLL_SYMBOLS, CONFOCAL_MULTI_SYMBOLS, MLP_HVP_SYMBOLS, VGG16_SYMBOLS, NAS_SYMBOLS, KLSTM_SYMBOLS = (
+    tuple(PROTOTYPES[h]) for h in ("l2o_abi.h", "l2o_confocal_unroll_abi.h", "l2o_confocal_multi_abi.h", "l2o_mlp_hvp_abi.h",
+                                   "l2o_vgg16_abi.h", "l2o_nas_abi.h", "l2o_klstm_abi.h"))
+
+
 class L2OError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libl2o_hip error %d: %s" % (code, msg))
@@ -337,19 +418,18 @@ class L2OPartnerTimeout(L2OError):
 
 
 def source_build_id():
-    """What l2o_build_id() of a library built from the sources in this tree returns (csrc/Makefile: sha256 over
-    the two .hip translation units, the headers and the Makefile in make's $(sort) order), or None without the sources."""
+    """What l2o_build_id() of a library built from the sources in this tree returns (csrc/Makefile: sha256 over the two .hip
+    translation units, every header of csrc/ and include/ and the Makefile in make's $(sort) order), or None without the
+    sources."""
     import glob
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
-    names = ["l2o_kernels.hip", "l2o_kernels_ilp.hip", "Makefile", "../../include/l2o_abi.h",
-             "../../include/l2o_confocal_unroll_abi.h", "../../include/l2o_confocal_multi_abi.h",
-             "../../include/l2o_mlp_hvp_abi.h", "../../include/l2o_vgg16_abi.h", "../../include/l2o_nas_abi.h",
-             "../../include/l2o_klstm_abi.h"] + [
-        os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.h"))]
+    names = ["l2o_kernels.hip", "l2o_kernels_ilp.hip", "Makefile"] + \
+        [os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.h"))] + \
+        ["../../include/" + os.path.basename(p) for p in glob.glob(os.path.join(csrc, "../../include/*.h"))]
     h = hashlib.sha256()
     try:
-        for n in sorted(set(names)):
+        for n in sorted(names):
             with open(os.path.join(csrc, n), "rb") as f:
                 h.update(f.read())
     except OSError:
@@ -380,6 +460,20 @@ def last_unroll_variant():
             "NV": (w >> 12) & 3}
 
 
+def declare(library):
+    """Give every symbol of PROTOTYPES its restype / argtypes on the loaded `library` and return it.  The library is built
+    from this tree, so one that lacks a listed symbol is a stale file: it is refused whole, at load."""
+    missing = [name for protos in PROTOTYPES.values() for name in protos if not hasattr(library, name)]
+    if missing:
+        raise RuntimeError("open_l2o_amd: %s has no %s: the library is stale (built from older sources) -- rebuild it with "
+                           "`make -C open_l2o_amd/csrc`" % (LIB_PATH, ", ".join(missing)))
+    for protos in PROTOTYPES.values():
+        for name, (restype, argtypes) in protos.items():
+            fn = getattr(library, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    return library
+
+
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is not built."""
     global _lib
@@ -389,164 +483,7 @@ def lib():
         raise RuntimeError(
             "open_l2o_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C open_l2o_amd/csrc`.  There is no CPU fallback." % LIB_PATH)
-    L = C.CDLL(LIB_PATH)
-    fp, vp, i32, i64, dbl = C.POINTER(C.c_float), C.c_void_p, C.c_int32, C.c_int64, C.c_double
-    L.l2o_abi_version.restype = C.c_int
-    L.l2o_abi_version.argtypes = []
-    L.l2o_last_error.restype = C.c_char_p
-    L.l2o_last_error.argtypes = []
-    L.l2o_build_id.restype = C.c_char_p
-    L.l2o_build_id.argtypes = []
-    L.l2o_last_unroll_form.restype = C.c_int
-    L.l2o_last_unroll_form.argtypes = []
-    L.l2o_last_unroll_variant.restype = C.c_int
-    L.l2o_last_unroll_variant.argtypes = []
-    L.l2o_coresident_workgroups.restype = C.c_int32
-    L.l2o_coresident_workgroups.argtypes = [C.c_void_p, C.c_void_p]
-    L.l2o_wpack_floats.restype = C.c_size_t
-    L.l2o_wpack_floats.argtypes = [C.POINTER(NetCfg)]
-    L.l2o_wpack_host.restype = C.c_int
-    L.l2o_wpack_host.argtypes = [C.POINTER(NetCfg)] + [vp] * 9
-    L.l2o_state_floats.restype = C.c_size_t
-    L.l2o_state_floats.argtypes = [i64, i64]
-    L.l2o_state_pack.restype = C.c_int
-    L.l2o_state_pack.argtypes = [vp, vp, vp, vp, vp, i64, i64, vp]
-    L.l2o_state_unpack.restype = C.c_int
-    L.l2o_state_unpack.argtypes = [vp, vp, vp, vp, vp, i64, i64, vp]
-    L.l2o_problem_fg.restype = C.c_int
-    L.l2o_problem_fg.argtypes = [C.POINTER(Problem), vp, vp, vp, vp]
-    L.l2o_problem_hvp.restype = C.c_int
-    L.l2o_problem_hvp.argtypes = [C.POINTER(Problem), vp, vp, vp, vp, vp]
-    L.l2o_mlp_fg.restype = C.c_int
-    L.l2o_mlp_fg.argtypes = [C.POINTER(Mlp)] + [vp] * 12
-    L.l2o_mlp_scratch_floats.restype = C.c_size_t
-    L.l2o_mlp_scratch_floats.argtypes = [C.POINTER(Mlp)]
-    L.l2o_confocal_unroll_supported.restype = C.c_int
-    L.l2o_confocal_unroll_supported.argtypes = [C.POINTER(NetCfg), C.POINTER(Confocal), vp]
-    L.l2o_confocal_unroll_scratch_floats.restype = C.c_size_t
-    L.l2o_confocal_unroll_scratch_floats.argtypes = [C.POINTER(Confocal), i32]
-    L.l2o_confocal_unroll.restype = C.c_int
-    L.l2o_confocal_unroll.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Confocal), vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
-    L.l2o_confocal_unroll_record.restype = C.c_int
-    L.l2o_confocal_unroll_record.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Confocal), vp, vp, vp, vp, vp, vp, i32, i32, vp,
-                                             C.POINTER(ConfocalHist), vp, vp]
-    if all(hasattr(L, name) for name in CONFOCAL_MULTI_SYMBOLS):
-        L.l2o_confocal_unroll_multi_supported.restype = C.c_int
-        L.l2o_confocal_unroll_multi_supported.argtypes = [C.POINTER(NetCfg), C.POINTER(Confocal), i32, vp]
-        L.l2o_confocal_unroll_multi_scratch_floats.restype = C.c_size_t
-        L.l2o_confocal_unroll_multi_scratch_floats.argtypes = [C.POINTER(Confocal), i32, i32]
-        L.l2o_confocal_unroll_multi.restype = C.c_int
-        L.l2o_confocal_unroll_multi.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Confocal), C.POINTER(ConfocalInstance), i32,
-                                                i32, i32, vp, vp]
-        L.l2o_confocal_unroll_multi_record.restype = C.c_int
-        L.l2o_confocal_unroll_multi_record.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Confocal),
-                                                       C.POINTER(ConfocalInstance), i32, i32, i32, C.POINTER(ConfocalHist), vp, vp]
-    L.l2o_mlp_unroll_supported.restype = C.c_int
-    L.l2o_mlp_unroll_supported.argtypes = [C.POINTER(NetCfg), C.POINTER(Mlp), vp]
-    L.l2o_mlp_unroll_workspace_bytes.restype = C.c_size_t
-    L.l2o_mlp_unroll_workspace_bytes.argtypes = [C.POINTER(Mlp)]
-    L.l2o_mlp_unroll.restype = C.c_int
-    L.l2o_mlp_unroll.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Mlp), vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
-    L.l2o_mlp_unroll_record.restype = C.c_int
-    L.l2o_mlp_unroll_record.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Mlp), vp, vp, vp, vp, vp, vp, i32, i32, vp,
-                                        C.POINTER(MlpHist), vp, vp]
-    for struct, stem in STEP_FG + tuple(e for e in STEP_FG_OPEN if hasattr(L, e[1] + "_fg")):
-        floats, fg = getattr(L, stem + "_scratch_floats"), getattr(L, stem + "_fg")
-        floats.restype, floats.argtypes = C.c_size_t, [C.POINTER(struct)]
-        fg.restype, fg.argtypes = C.c_int, [C.POINTER(struct)] + [vp] * 6
-    if all(hasattr(L, name) for name in KLSTM_SYMBOLS):
-        L.l2o_klstm_supported.restype = C.c_int
-        L.l2o_klstm_supported.argtypes = [C.POINTER(KlstmNet)]
-        L.l2o_klstm_state_floats.restype = C.c_size_t
-        L.l2o_klstm_state_floats.argtypes = [C.POINTER(KlstmNet), i64]
-        L.l2o_klstm_step.restype = C.c_int
-        L.l2o_klstm_step.argtypes = [C.POINTER(KlstmNet), vp, vp, vp, vp, i64, vp]
-        L.l2o_klstm_bwd_step.restype = C.c_int
-        L.l2o_klstm_bwd_step.argtypes = [C.POINTER(KlstmNet), C.POINTER(KlstmBwdIO), i64, vp]
-    L.l2o_mlp_hvp_scratch_floats.restype = C.c_size_t
-    L.l2o_mlp_hvp_scratch_floats.argtypes = [C.POINTER(MlpDeep)]
-    L.l2o_mlp_hvp.restype = C.c_int
-    L.l2o_mlp_hvp.argtypes = [C.POINTER(MlpDeep)] + [vp] * 6
-    L.l2o_mlp_unroll_multi_supported.restype = C.c_int
-    L.l2o_mlp_unroll_multi_supported.argtypes = [C.POINTER(NetCfg), C.POINTER(Mlp), i32, vp]
-    L.l2o_mlp_unroll_multi_workspace_bytes.restype = C.c_size_t
-    L.l2o_mlp_unroll_multi_workspace_bytes.argtypes = [C.POINTER(Mlp), i32]
-    L.l2o_mlp_unroll_multi.restype = C.c_int
-    L.l2o_mlp_unroll_multi.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Mlp), C.POINTER(MlpInstance), i32, i32, i32, vp, vp]
-    L.l2o_mlp_unroll_multi_record.restype = C.c_int
-    L.l2o_mlp_unroll_multi_record.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Mlp), C.POINTER(MlpInstance), i32, i32, i32,
-                                              C.POINTER(MlpHist), vp, vp]
-    L.l2o_cwlstm_step.restype = C.c_int
-    L.l2o_cwlstm_step.argtypes = [C.POINTER(NetCfg), vp, vp, vp, vp, dbl, dbl, vp, vp, i64, i64, vp]
-    L.l2o_gen_state_floats.restype = C.c_size_t
-    L.l2o_gen_state_floats.argtypes = [C.POINTER(GenNet), i64]
-    L.l2o_cwlstm_step_generic.restype = C.c_int
-    L.l2o_cwlstm_step_generic.argtypes = [C.POINTER(NetCfg), C.POINTER(GenNet), vp, vp, vp, vp, dbl, dbl, vp, vp, i64, vp]
-    L.l2o_cwlstm_bwd_step_generic.restype = C.c_int
-    L.l2o_cwlstm_bwd_step_generic.argtypes = [C.POINTER(NetCfg), C.POINTER(GenNet), C.POINTER(GenBwdIO), dbl, dbl, i64, vp]
-    L.l2o_cwlstm_step_multi.restype = C.c_int
-    L.l2o_cwlstm_step_multi.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(StepSeg), C.c_int32, dbl, dbl, vp]
-    L.l2o_cwlstm_bwd_step.restype = C.c_int
-    L.l2o_cwlstm_bwd_step.argtypes = [C.POINTER(NetCfg), C.POINTER(NetWeights), C.POINTER(BwdIO), dbl, dbl, i64,
-                                      i64, vp]
-    L.l2o_cwlstm_bwd_multi.restype = C.c_int
-    L.l2o_cwlstm_bwd_multi.argtypes = [C.POINTER(NetCfg), C.POINTER(NetWeights), C.POINTER(BwdSeg), C.c_int32, vp, vp,
-                                       vp, vp, dbl, dbl, vp]
-    L.l2o_cwlstm_bwd_unroll.restype = C.c_int
-    L.l2o_cwlstm_bwd_unroll.argtypes = [C.POINTER(NetCfg), C.POINTER(NetWeights), C.POINTER(BwdUnrollSeg), C.c_int32, vp,
-                                        C.c_int32, i64, vp, vp, vp, vp, vp]
-    L.l2o_cwlstm_bwd_unroll_compact.restype = C.c_int
-    L.l2o_cwlstm_bwd_unroll_compact.argtypes = L.l2o_cwlstm_bwd_unroll.argtypes
-    L.l2o_adam_step.restype = C.c_int
-    L.l2o_adam_step.argtypes = [vp, vp, vp, vp, i64, C.c_float, dbl, dbl, dbl, vp]
-    L.l2o_adam_step_guarded.restype = C.c_int
-    L.l2o_adam_step_guarded.argtypes = [vp, vp, vp, vp, i64, C.c_float, dbl, dbl, dbl, vp, vp]
-    L.l2o_adam_step_gather.restype = C.c_int
-    L.l2o_adam_step_gather.argtypes = [vp, vp, vp, vp, vp, i64, C.c_float, dbl, dbl, dbl, vp, vp]
-    L.l2o_wpack_device.restype = C.c_int
-    L.l2o_wpack_device.argtypes = [C.POINTER(NetCfg), C.POINTER(NetWeights), vp, vp]
-    L.l2o_unroll.restype = C.c_int
-    L.l2o_unroll.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Problem), vp, vp, vp, vp, i32, i32, vp, vp, vp]
-    L.l2o_unroll_record.restype = C.c_int
-    L.l2o_unroll_record.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Problem), vp, vp, vp, vp, i32, i32, vp, vp,
-                                    C.POINTER(UnrollHist), vp]
-    L.l2o_unroll_reduce.restype = C.c_int
-    L.l2o_unroll_reduce.argtypes = [C.POINTER(NetCfg), vp, C.POINTER(Problem), vp, vp, vp, vp, vp, i32, i32, i32, vp, vp,
-                                    vp, C.POINTER(UnrollHist), vp]
-    L.l2o_unroll_workspace_init.restype = C.c_int
-    L.l2o_unroll_workspace_init.argtypes = [vp, C.c_size_t, vp]
-    L.l2o_cwlstm_wgrad_dims.restype = C.c_int32
-    L.l2o_cwlstm_wgrad_dims.argtypes = [C.POINTER(NetCfg), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.l2o_cwlstm_wgrad.restype = C.c_int
-    L.l2o_cwlstm_wgrad.argtypes = [C.POINTER(NetCfg), vp, vp, C.c_int64, vp, vp, vp]
-    L.l2o_cwlstm_wgrad_compact.restype = C.c_int
-    L.l2o_cwlstm_wgrad_compact.argtypes = [C.POINTER(NetCfg), vp, vp, C.c_int32, C.c_int64, vp, vp, vp]
-    L.l2o_unroll_workspace_layout.restype = C.c_int64
-    L.l2o_unroll_workspace_layout.argtypes = [C.POINTER(NetCfg), C.POINTER(Problem)]
-    L.l2o_unroll_workspace_bytes.restype = C.c_size_t
-    L.l2o_unroll_workspace_bytes.argtypes = [C.POINTER(NetCfg), C.POINTER(Problem), i32]
-    L.l2o_unroll_status.restype = C.c_int
-    L.l2o_unroll_status.argtypes = [vp]
-    L.l2o_unroll_supported.restype = C.c_int
-    L.l2o_unroll_supported.argtypes = [C.POINTER(NetCfg), C.POINTER(Problem)]
-    L.l2o_unroll_record_supported.restype = C.c_int
-    L.l2o_unroll_record_supported.argtypes = [C.POINTER(NetCfg), C.POINTER(Problem)]
-    L.l2o_atb_workspace_bytes.restype = C.c_size_t
-    L.l2o_atb_workspace_bytes.argtypes = [i64, i32, i32]
-    L.l2o_atb.restype = C.c_int
-    L.l2o_atb.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
-    L.l2o_reduce_fx.restype = C.c_int
-    L.l2o_reduce_fx.argtypes = [vp, i32, i32, i32, vp, vp]
-    L.l2o_suffix_sums.restype = C.c_int
-    L.l2o_suffix_sums.argtypes = [vp, vp, vp, i64, i32, vp]
-    L.l2o_colsum_scratch_floats.restype = C.c_size_t
-    L.l2o_colsum_scratch_floats.argtypes = [i64, i32]
-    L.l2o_colsum.restype = C.c_int
-    L.l2o_colsum.argtypes = [vp, i64, i64, i32, vp, i32, vp, vp]
-    L.l2o_lincomb.restype = C.c_int
-    L.l2o_lincomb.argtypes = [vp, vp, C.c_float, vp, C.c_float, vp, C.c_float, i64, vp]
-    L.l2o_rnnprop_input_adjoint.restype = C.c_int
-    L.l2o_rnnprop_input_adjoint.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, dbl, dbl, dbl, dbl, vp, vp, vp, i64, vp]
+    L = declare(C.CDLL(LIB_PATH))
     if L.l2o_abi_version() != L2O_ABI_VERSION:
         raise RuntimeError("libl2o_hip.so ABI version %d != binding version %d"
                            % (L.l2o_abi_version(), L2O_ABI_VERSION))

@@ -138,11 +138,12 @@ class ConfocalDesc:
     img: torch.Tensor = None  # inference: [batch, Rx Ry Rz] fp32, flat voxel index (iy Rx + ix) Rz + iz
 
 
-# The step-path optimizees: ONE term over several variables, evaluated per step by an entry point of its own.  Per problem
-# kind: the engine method the graph calls, the descriptor the graph builds for it, the C struct and the stem of its two
-# symbols (<stem>_scratch_floats, <stem>_fg), the engine attribute that caches its scratch, how many variables a descriptor
-# takes, and whether every evaluation draws a minibatch.  (PROB_MLP is here with SEVERAL hidden layers; one hidden layer has
-# mlp_fg and the fused unrolls.)
+# The step-path optimizees: ONE term over several variables, evaluated per step by an entry point of its own.  ONE table, per
+# problem kind: the engine method the graph calls, the descriptor the graph builds for it, the C struct and the stem of its
+# two symbols (<stem>_scratch_floats, <stem>_fg: the pair is in _abi.STEP_FG), the engine attribute that caches its scratch,
+# how many variables a descriptor takes, and whether every evaluation draws a minibatch.  A new kind adds ONE entry here; the
+# graph and meta.py ask step_optimizee(kind) and never a literal table.  (PROB_MLP is here with SEVERAL hidden layers; one
+# hidden layer has mlp_fg and the fused unrolls.)
 StepOptimizee = collections.namedtuple("StepOptimizee", "method desc struct stem scratch nvars sampled")
 STEP_OPTIMIZEES = {
     _abi.PROB_MLP: StepOptimizee("mlp_deep_fg", MlpDeepDesc, _abi.MlpDeep, "l2o_mlp_deep", "_mlp_deep_scratch",
@@ -155,24 +156,16 @@ STEP_OPTIMIZEES = {
                                    lambda d: 14 if d.batch_norm else 10, True),
     _abi.PROB_CONFOCAL: StepOptimizee("confocal_fg", ConfocalDesc, _abi.Confocal, "l2o_confocal", "_confocal_scratch",
                                       lambda d: 6 * d.num_points + 1, False),
-}
-# ... and the kinds added since that table's keys were pinned (tests/test_step_optimizees_cpu.py): the same entry type.
-# ALL_STEP_OPTIMIZEES is the union; both are values that tests pin (tests/test_vgg16_cpu.py) and get no new entries.
-LATER_STEP_OPTIMIZEES = {
     _abi.PROB_VGG16: StepOptimizee("vgg16_fg", Vgg16Desc, _abi.Vgg16, "l2o_vgg16", "_vgg16_scratch", lambda d: 28, True),
+    _abi.PROB_NAS: StepOptimizee("nas_fg", NasDesc, _abi.Nas, "l2o_nas", "_nas_scratch",
+                                 lambda d: 18 if d.batch_norm else 10, True),
 }
-ALL_STEP_OPTIMIZEES = {**STEP_OPTIMIZEES, **LATER_STEP_OPTIMIZEES}
-# The OPEN table: every step-path kind, the pinned ones and whatever came after them.  A new kind adds ONE entry here (and
-# its (struct, stem) pair to _abi.STEP_FG_OPEN); the graph and meta.py ask step_optimizee(kind) and never a literal table.
-STEP_REGISTRY = dict(ALL_STEP_OPTIMIZEES)
-STEP_REGISTRY[_abi.PROB_NAS] = StepOptimizee("nas_fg", NasDesc, _abi.Nas, "l2o_nas", "_nas_scratch",
-                                             lambda d: 18 if d.batch_norm else 10, True)
-_ENTRY_OF_METHOD = {entry.method: entry for entry in STEP_REGISTRY.values()}
+_ENTRY_OF_METHOD = {entry.method: entry for entry in STEP_OPTIMIZEES.values()}
 
 
 def step_optimizee(kind):
     """The registry entry of a problem kind, or None where the kind is not a step-path optimizee."""
-    return STEP_REGISTRY.get(kind)
+    return STEP_OPTIMIZEES.get(kind)
 
 
 def _ptr(t):
@@ -186,26 +179,37 @@ def _addr(t):
     return 0 if t is None else t.data_ptr()
 
 
-def _ptr_array(ts, optional=False, size=None):
-    """void *[size or len(ts)] of contiguous fp32 device tensors, a None entry NULL (ts None, or `optional` and every entry
-    None: a NULL array)."""
+def _ptr_array(ts, optional=False):
+    """void *[len(ts)] of contiguous fp32 device tensors, a None entry NULL (ts None, or `optional` and every entry None: a
+    NULL array)."""
     if ts is None or (optional and all(t is None for t in ts)):
         return None
-    return (C.c_void_p * (size or len(ts)))(*[None if t is None else _ptr(t).value for t in ts])
+    return (C.c_void_p * len(ts))(*[None if t is None else _ptr(t).value for t in ts])
 
 
-def _set_ptrs(s, **lists):
-    """Fill the void *[N] fields of the ctypes struct `s` from lists of device tensors (a None list: the field stays NULL)."""
-    for field, ts in lists.items():
-        if ts is not None:
-            setattr(s, field, _ptr_array(ts, size=len(getattr(s, field))))
+def _fill(s, values, checked=False):
+    """Fill the fields of the ctypes struct `s` from the dict `values` and return s: a pointer field takes a device tensor's
+    address, a void *[N] field a list of tensors element by element, an integer field an int; a missing or None value (or
+    list entry) stays NULL / 0.  checked: every tensor goes through _ptr (contiguous fp32)."""
+    for name, ctype in s._fields_:
+        v = values.get(name)
+        if v is None:
+            continue
+        if ctype is C.c_void_p:
+            setattr(s, name, _ptr(v).value if checked else v.data_ptr())
+        elif issubclass(ctype, C.Array):
+            field = getattr(s, name)
+            for k, t in enumerate(v):
+                if t is not None:
+                    field[k] = _ptr(t).value if checked else t.data_ptr()
+        else:
+            setattr(s, name, int(v))
+    return s
 
 
-def _fill_hist(h, hist):
-    """struct l2o_mlp_hist / l2o_confocal_hist from dict(st=, g=, m=, v=) of per-variable lists (m / v, or entries of them,
-    None for the DM nets).  Returns h."""
-    _set_ptrs(h, st=hist["st"], g=hist["g"], m=hist.get("m"), v=hist.get("v"))
-    return h
+def _net_weights(weights):
+    """struct l2o_net_weights from a dict of device tensors keyed by its field names (missing = NULL)."""
+    return _fill(_abi.NetWeights(), weights)
 
 
 def _check_confocal(name, d, lists, sim, img):
@@ -217,6 +221,23 @@ def _check_confocal(name, d, lists, sim, img):
     if any(t.numel() != d.batch for t in lists[0]) \
             or (inference and (img is None or img.numel() != d.batch * int(np.prod(d.roi)))):
         raise ValueError("%s: every variable holds [batch] floats, img [batch, V]" % name)
+
+
+def _upload_lstm_stack(engine, c, params, layers):
+    """Upload the Sonnet-layout weights of an LSTM stack and its output Linear (params: the .l2l dict) and point the struct
+    `c` (l2o_gen_net / l2o_klstm_net: n_layers, hidden, w_gates, b_gates, w_lin, b_lin) at them.  Returns the device tensors,
+    which the caller keeps alive."""
+    c.n_layers = len(layers)
+    tensors = []
+    for l, H in enumerate(layers):
+        c.hidden[l] = H
+        for name, field in (("w_gates", c.w_gates), ("b_gates", c.b_gates)):
+            t = engine.tensor(params["lstm_%d" % (l + 1)][name])
+            tensors.append(t)
+            field[l] = t.data_ptr()
+    wl, bl = engine.tensor(params["linear"]["w"]), engine.tensor(params["linear"]["b"])
+    c.w_lin, c.b_lin = wl.data_ptr(), bl.data_ptr()
+    return tensors + [wl, bl]
 
 
 class HipEngine(object):
@@ -295,9 +316,8 @@ class HipEngine(object):
         """Device Sonnet-layout weights (dict keyed like struct l2o_net_weights) -> `out` (device wpack),
         without leaving the device (l2o_wpack_device; bit-equal to pack_weights)."""
         cc = spec.to_c()
-        w = _abi.NetWeights()
-        for k, _ in _abi.NetWeights._fields_:
-            setattr(w, k, None if (k == "wpack" or weights.get(k) is None) else weights[k].data_ptr())
+        w = _net_weights(weights)
+        w.wpack = None                                       # (the output, not an input)
         # a buffer this engine has packed before for the same configuration: its padding words are zero already
         # (L2O_OPT_WPACK_NO_CLEAR: no memset in front of the pack kernel on the meta-step's critical path)
         sig = (spec.preprocess, tuple(spec.layers), spec.kind)
@@ -383,9 +403,7 @@ class HipEngine(object):
     def problem_hvp(self, p: ProblemDesc, x, u, out):
         """out = (d g / d x) u of the analytic optimizee at x (l2o_problem_hvp), g as problem_fg returns it."""
         cp = self._cprob(p)
-        scr = self.__dict__.get("_hvp_scratch")
-        if scr is None or scr.numel() < p.B_local:
-            scr = self._hvp_scratch = self.empty(max(p.B_local, 1))
+        scr = self._cached_buffer("_hvp_scratch", max(p.B_local, 1))
         _abi.check(self.lib.l2o_problem_hvp(C.byref(cp), _ptr(x), _ptr(u), _ptr(out), _ptr(scr), self._stream()))
 
     def int_tensor(self, a):
@@ -416,21 +434,26 @@ class HipEngine(object):
             setattr(self, attr, buf)
         return buf
 
-    def _step_scratch(self, entry, c):
-        """The cached scratch of one step-path optimizee, grown to what <stem>_scratch_floats asks for the struct `c`; None
-        where the library refuses the shape (a size of 0)."""
-        n = int(getattr(self.lib, entry.stem + "_scratch_floats")(C.byref(c)))
-        return self._cached_buffer(entry.scratch, n) if n else None
+    def _step_fg(self, entry, c, d, indices, ws, loss, grads, unsupported, miscount=None):
+        """<stem>_fg of the table entry `entry` on ONE minibatch: `c` its struct filled from the descriptor `d` (None: a shape
+        the caller itself refuses), ws / grads lists of device tensors in the graph's variable order (grads may be None:
+        forward only).  The scratch is the entry's cached buffer, grown to what <stem>_scratch_floats asks for; a size of 0
+        is the library refusing the shape (the text `unsupported`), then comes the variable count (the text `miscount`;
+        None: left to the library)."""
+        n = int(getattr(self.lib, entry.stem + "_scratch_floats")(C.byref(c))) if c is not None else 0
+        if not n:
+            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, unsupported)
+        scr = self._cached_buffer(entry.scratch, n)
+        if miscount is not None and (len(ws) != entry.nvars(d) or (grads is not None and len(grads) != len(ws))):
+            raise ValueError(miscount)
+        _abi.check(getattr(self.lib, entry.stem + "_fg")(C.byref(c), C.c_void_p(indices.data_ptr()), _ptr_array(ws),
+                                                         _ptr(loss), _ptr_array(grads), _ptr(scr), self._stream()))
 
     def mlp_deep_fg(self, d: MlpDeepDesc, indices, ws, loss, grads):
         """Loss and gradients of the MLP optimizee with SEVERAL hidden layers on ONE minibatch (l2o_mlp_deep_fg).  ws / grads:
         lists [w0, b0, w1, b1, ..., wL, bL] of device tensors (grads may be None: forward only)."""
-        c = self._cmlp_deep(d, d.hidden)
-        scr = self._step_scratch(STEP_OPTIMIZEES[_abi.PROB_MLP], c)
-        if scr is None:
-            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_mlp_deep_fg: unsupported MLP shape %r" % (d.hidden,))
-        _abi.check(self.lib.l2o_mlp_deep_fg(C.byref(c), C.c_void_p(indices.data_ptr()), _ptr_array(ws), _ptr(loss),
-                                            _ptr_array(grads), _ptr(scr), self._stream()))
+        self._step_fg(STEP_OPTIMIZEES[_abi.PROB_MLP], self._cmlp_deep(d, d.hidden), d, indices, ws, loss, grads,
+                      "l2o_mlp_deep_fg: unsupported MLP shape %r" % (d.hidden,))
 
     @staticmethod
     def _cmlp_deep(d, hidden):
@@ -460,20 +483,14 @@ class HipEngine(object):
                                         _ptr_array(outs), _ptr(scr), self._stream()))
 
     def _image_net_fg(self, method, d, indices, ws, loss, grads):
-        """Loss and gradients of an image-net optimizee on ONE minibatch: <stem>_fg of the table entry of the public method
-        that delegates here.  ws / grads: lists of device tensors in the graph's variable order (grads may be None: forward
-        only)."""
+        """Loss and gradients of an image-net optimizee on ONE minibatch (_step_fg): the struct of _abi.ImageNet."""
         entry = _ENTRY_OF_METHOD[method]
         c = entry.struct()
         c.batch, c.n_data, c.batch_norm, c.flags = d.batch, int(d.images.shape[0]), 1 if d.batch_norm else 0, 0
         c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
-        scr = self._step_scratch(entry, c)
-        if scr is None:
-            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "%s_fg: unsupported minibatch %d" % (entry.stem, d.batch))
-        if len(ws) != entry.nvars(d) or (grads is not None and len(grads) != len(ws)):
-            raise ValueError("%s_fg: %d variables for batch_norm=%r" % (entry.stem, len(ws), d.batch_norm))
-        _abi.check(getattr(self.lib, entry.stem + "_fg")(C.byref(c), C.c_void_p(indices.data_ptr()), _ptr_array(ws),
-                                                         _ptr(loss), _ptr_array(grads), _ptr(scr), self._stream()))
+        self._step_fg(entry, c, d, indices, ws, loss, grads,
+                      "%s_fg: unsupported minibatch %d" % (entry.stem, d.batch),
+                      "%s_fg: %d variables for batch_norm=%r" % (entry.stem, len(ws), d.batch_norm))
 
     def mnist_conv_fg(self, d: MnistConvDesc, indices, ws, loss, grads):
         """problems.mnist_conv (l2o_mnist_conv_fg): 10 variables with batch norm, 6 without."""
@@ -494,34 +511,27 @@ class HipEngine(object):
     def vgg16_fg(self, d: Vgg16Desc, indices, ws, loss, grads):
         """problems.vgg16_cifar10 (l2o_vgg16_fg): 28 variables -- weights and biases of the 13 conv layers, then of fc.  ws /
         grads: lists of device tensors in the graph's variable order (grads may be None: forward only)."""
-        entry = _ENTRY_OF_METHOD["vgg16_fg"]
-        if not hasattr(self.lib, "l2o_vgg16_fg"):
-            raise RuntimeError("libl2o_hip.so has no l2o_vgg16_fg: rebuild it (make -C open_l2o_amd/csrc)")
-        c = entry.struct()
-        c.batch, c.n_data, c.flags = d.batch, int(d.images.shape[0]), 0
         channels = tuple(int(n) for n in d.channels)
-        for k, n in enumerate(channels[:5]):
-            c.channels[k] = n
-        c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
-        scr = self._step_scratch(entry, c) if len(channels) == 5 else None
-        if scr is None:
-            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_vgg16_fg: unsupported minibatch %d or channels %r"
-                                      % (d.batch, channels))
-        if len(ws) != entry.nvars(d) or (grads is not None and len(grads) != len(ws)):
-            raise ValueError("l2o_vgg16_fg: %d variables (it takes %d)" % (len(ws), entry.nvars(d)))
-        _abi.check(self.lib.l2o_vgg16_fg(C.byref(c), C.c_void_p(indices.data_ptr()), _ptr_array(ws), _ptr(loss),
-                                         _ptr_array(grads), _ptr(scr), self._stream()))
+        c = None
+        if len(channels) == 5:
+            c = _abi.Vgg16()
+            c.batch, c.n_data, c.flags = d.batch, int(d.images.shape[0]), 0
+            c.channels[:] = channels
+            c.images, c.labels = C.c_void_p(d.images.data_ptr()), C.c_void_p(d.labels.data_ptr())
+        self._step_fg(STEP_OPTIMIZEES[_abi.PROB_VGG16], c, d, indices, ws, loss, grads,
+                      "l2o_vgg16_fg: unsupported minibatch %d or channels %r" % (d.batch, channels),
+                      "l2o_vgg16_fg: %d variables (it takes 28)" % len(ws))
 
     def confocal_fg(self, d: ConfocalDesc, theta, sim, loss, grads):
         """Loss and gradients of the confocal optimizee (l2o_confocal_fg).  theta / sim / grads: lists of 6 num_points + 1
         device tensors of [batch] floats in the graph's variable order (per point I, x, y, z, sigmaxy, sigmaz; then bg);
         sim is None in inference mode (d.img is the target); grads may be None: forward only."""
-        entry = STEP_OPTIMIZEES[_abi.PROB_CONFOCAL]
         c = self._cconfocal(d)
-        scr = self._step_scratch(entry, c)
-        if scr is None:
+        n = int(self.lib.l2o_confocal_scratch_floats(C.byref(c)))
+        if not n:
             raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "l2o_confocal_fg: batch in [1, 1024], num_points in [1, 8], "
                                       "ROI edges in [2, 32] (got %d, %d, %r)" % (d.batch, d.num_points, tuple(d.roi)))
+        scr = self._cached_buffer("_confocal_scratch", n)
         _check_confocal("l2o_confocal_fg", d, (theta,) if grads is None else (theta, grads), sim, d.img)
         _abi.check(self.lib.l2o_confocal_fg(C.byref(c), _ptr_array(theta), _ptr_array(sim), _ptr(loss), _ptr_array(grads),
                                             _ptr(scr), self._stream()))
@@ -556,13 +566,11 @@ class HipEngine(object):
         if hist is None:
             _abi.check(self.lib.l2o_confocal_unroll(*args, _ptr(scr), self._stream()))
             return
-        h = _fill_hist(_abi.ConfocalHist(), hist)
+        h = _fill(_abi.ConfocalHist(), hist, checked=True)
         _abi.check(self.lib.l2o_confocal_unroll_record(*args, C.byref(h), _ptr(scr), self._stream()))
 
     def confocal_unroll_multi_supported(self, spec: NetSpec, d: ConfocalDesc, n_inst):
         """l2o_confocal_unroll_multi applies: up to CONFOCAL_MAX_INSTANCES confocal instances of one shape in one launch."""
-        if not hasattr(self.lib, "l2o_confocal_unroll_multi"):
-            return False
         cc, cm = spec.to_c(), self._cconfocal(d)
         return bool(self.lib.l2o_confocal_unroll_multi_supported(C.byref(cc), C.byref(cm), int(n_inst), self._stream()))
 
@@ -572,8 +580,6 @@ class HipEngine(object):
         scales=, sim=, img=, fx=) as the arguments of confocal_unroll (sim None in inference mode, where img is THAT
         instance's target; d.img is ignored); all instances share the network, the shape d and T / step0.  hists: None, or
         one history dict per instance as confocal_unroll's `hist` (l2o_confocal_unroll_multi_record)."""
-        if not hasattr(self.lib, "l2o_confocal_unroll_multi"):
-            raise _abi.L2OUnsupported(_abi.L2O_ERR_UNSUPPORTED, "libl2o_hip.so has no l2o_confocal_unroll_multi")
         for i in insts:
             _check_confocal("l2o_confocal_unroll_multi", d, [i[k] for k in ("xs", "sts", "ms", "vs", "scales")], i.get("sim"),
                             i.get("img"))
@@ -589,14 +595,14 @@ class HipEngine(object):
         arr = (_abi.ConfocalInstance * len(insts))()
         for a, i in zip(arr, insts):
             a.fx, a.img = _ptr(i["fx"]), _ptr(i.get("img")) if d.img is not None else None
-            _set_ptrs(a, x=i["xs"], st=i["sts"], m=i["ms"], v=i["vs"], x_scale=i["scales"], sim=i.get("sim"))
+            _fill(a, dict(x=i["xs"], st=i["sts"], m=i["ms"], v=i["vs"], x_scale=i["scales"], sim=i.get("sim")), checked=True)
         args = (C.byref(cc), _ptr(wpack), C.byref(cm), arr, len(insts), int(T), int(step0))
         if hists is None:
             _abi.check(self.lib.l2o_confocal_unroll_multi(*args, _ptr(scr), self._stream()))
             return
         harr = (_abi.ConfocalHist * len(hists))()
         for h, hist in zip(harr, hists):
-            _fill_hist(h, hist)
+            _fill(h, hist, checked=True)
         _abi.check(self.lib.l2o_confocal_unroll_multi_record(*args, harr, _ptr(scr), self._stream()))
 
     def mlp_unroll_supported(self, spec: NetSpec, d: MlpDesc):
@@ -632,7 +638,7 @@ class HipEngine(object):
         self._last_ws = ws
         ax, ast, am, av, asc = ent["arrs"]
         if hist is not None:
-            h = _fill_hist(_abi.MlpHist(), hist)
+            h = _fill(_abi.MlpHist(), hist, checked=True)
             _abi.check(self.lib.l2o_mlp_unroll_record(C.byref(cc), _ptr(wpack), C.byref(cm), C.c_void_p(indices.data_ptr()),
                                                       ax, ast, am, av, asc, int(T), int(step0), _ptr(fx), C.byref(h),
                                                       C.c_void_p(ws.data_ptr()), self._stream()))
@@ -669,14 +675,14 @@ class HipEngine(object):
             arr = (_abi.MlpInstance * len(instances))()
             for a, i in zip(arr, instances):
                 a.indices, a.fx = i["indices"].data_ptr(), i["fx"].data_ptr()
-                _set_ptrs(a, x=i["xs"], st=i["sts"], m=i["ms"], v=i["vs"], x_scale=i["scales"])
+                _fill(a, dict(x=i["xs"], st=i["sts"], m=i["ms"], v=i["vs"], x_scale=i["scales"]), checked=True)
             harr = None
             if hists is not None:
                 if len(hists) != len(instances):
                     raise ValueError("mlp_unroll_multi: one history per instance")
                 harr = (_abi.MlpHist * len(hists))()
                 for h, hist in zip(harr, hists):
-                    _fill_hist(h, hist)
+                    _fill(h, hist, checked=True)
             ent = dict(cc=cc, cm=cm, ws=ws, arr=arr, harr=harr,
                        keep=(d, wpack, [dict(i) for i in instances], None if hists is None else [dict(h) for h in hists]))
             if len(memo) >= 8:
@@ -740,18 +746,8 @@ class HipEngine(object):
 
         def __init__(self, engine, spec, params, direct=False):
             layers = tuple(int(h) for h in spec.layers)
-            self.tensors = []
             c = _abi.GenNet()
-            c.n_layers = len(layers)
-            for l, H in enumerate(layers):
-                c.hidden[l] = H
-                for name, field in (("w_gates", c.w_gates), ("b_gates", c.b_gates)):
-                    t = engine.tensor(params["lstm_%d" % (l + 1)][name])
-                    self.tensors.append(t)
-                    field[l] = t.data_ptr()
-            wl, bl = engine.tensor(params["linear"]["w"]), engine.tensor(params["linear"]["b"])
-            self.tensors += [wl, bl]
-            c.w_lin, c.b_lin = wl.data_ptr(), bl.data_ptr()
+            self.tensors = _upload_lstm_stack(engine, c, params, layers)
             c.in_dim = 2 if spec.preprocess == _abi.PRE_LOGSIGN else 1
             if spec.preprocess == _abi.PRE_FC_ELU:
                 wf, bf = engine.tensor(params["input_projection"]["w"]), engine.tensor(params["input_projection"]["b"])
@@ -775,15 +771,7 @@ class HipEngine(object):
     def bwd_step_generic(self, spec: NetSpec, gen, io: dict, pow1, pow2, N):
         """One BPTT step of an ANY-`layers` stack (l2o_cwlstm_bwd_step_generic).  io: device tensors keyed by the fields
         of struct l2o_gen_bwd_io (act / dz: lists, one tensor per layer; missing = NULL)."""
-        c = _abi.GenBwdIO()
-        for k, _ in _abi.GenBwdIO._fields_:
-            if k in ("act", "dz"):
-                for l, t in enumerate(io[k]):
-                    getattr(c, k)[l] = t.data_ptr()
-            else:
-                t = io.get(k)
-                setattr(c, k, None if t is None else t.data_ptr())
-        cc = spec.to_c()
+        c, cc = _fill(_abi.GenBwdIO(), io), spec.to_c()
         _abi.check(self.lib.l2o_cwlstm_bwd_step_generic(C.byref(cc), C.byref(gen.c), C.byref(c), float(pow1), float(pow2),
                                                         int(N), self._stream()))
 
@@ -794,25 +782,12 @@ class HipEngine(object):
         def __init__(self, engine, net):
             c = _abi.KlstmNet()
             c.kw, c.kh = net.kernel_shape
-            c.n_layers = len(net.layers)
             c.preprocess, c.tanh_output, c.flags = int(net.preprocess), int(bool(net.tanh_output)), 0
             c.logsign_k, c.scale = float(net.logsign_k), float(net.scale)
-            self.tensors = []
-            params = net.variables
-            for l, H in enumerate(net.layers):
-                c.hidden[l] = H
-                for name, field in (("w_gates", c.w_gates), ("b_gates", c.b_gates)):
-                    t = engine.tensor(params["lstm_%d" % (l + 1)][name])
-                    self.tensors.append(t)
-                    field[l] = t.data_ptr()
-            wl, bl = engine.tensor(params["linear"]["w"]), engine.tensor(params["linear"]["b"])
-            self.tensors += [wl, bl]
-            c.w_lin, c.b_lin = wl.data_ptr(), bl.data_ptr()
+            self.tensors = _upload_lstm_stack(engine, c, net.variables, net.layers)
             self.c = c
 
     def klstm_net(self, net):
-        if not all(hasattr(self.lib, name) for name in _abi.KLSTM_SYMBOLS):
-            raise RuntimeError("libl2o_hip.so has no l2o_klstm_step: rebuild it (make -C open_l2o_amd/csrc)")
         return HipEngine.KlstmNet(self, net)
 
     def klstm_step(self, net, g, st_in, st_out, x, N):
@@ -824,13 +799,7 @@ class HipEngine(object):
     def klstm_bwd_step(self, net, io: dict, N):
         """One BPTT step of a KernelDeepLSTM (l2o_klstm_bwd_step).  io: device tensors keyed by the fields of struct
         l2o_klstm_bwd_io (act / dz: lists, one tensor per layer)."""
-        c = _abi.KlstmBwdIO()
-        for k, _ in _abi.KlstmBwdIO._fields_:
-            if k in ("act", "dz"):
-                for l, t in enumerate(io[k]):
-                    getattr(c, k)[l] = _ptr(t).value
-            else:
-                setattr(c, k, _ptr(io[k]))
+        c = _fill(_abi.KlstmBwdIO(), io, checked=True)
         _abi.check(self.lib.l2o_klstm_bwd_step(C.byref(net.device_net(self).c), C.byref(c), int(N), self._stream()))
 
     def lstm_step(self, spec: NetSpec, wpack, g, m, v, pow1, pow2, st, x, B, D):
@@ -874,17 +843,8 @@ class HipEngine(object):
         """One BPTT step (l2o_cwlstm_bwd_step).  weights / io: dicts of device tensors keyed by the
         field names of struct l2o_net_weights / l2o_bwd_io (missing = NULL)."""
         cc = spec.to_c()
-        w = _abi.NetWeights()
-        for k, _ in _abi.NetWeights._fields_:
-            setattr(w, k, None if weights.get(k) is None else weights[k].data_ptr())
-        b = _abi.BwdIO()
-        for k, _ in _abi.BwdIO._fields_:
-            if k in ("a_stride", "b_stride"):
-                setattr(b, k, int(io.get(k) or 0))
-            elif k == "dg":
-                b.dg = None if io.get("dg") is None else io["dg"].data_ptr()
-            else:
-                setattr(b, k, None if io.get(k) is None else io[k].data_ptr())
+        w = _net_weights(weights)
+        b = _fill(_abi.BwdIO(), io)
         _abi.check(self.lib.l2o_cwlstm_bwd_step(C.byref(cc), C.byref(w), C.byref(b), float(pow1), float(pow2),
                                                 B, D, self._stream()))
 
@@ -893,14 +853,10 @@ class HipEngine(object):
         segs: list of dict(g=, m=, v=, st_prev=, dx_next=, B=, D=); A [rows, KA], Bm [rows, KB] and the
         carries [4, rows, 20] are shared, rows = 16 * (total tiles)."""
         cc = spec.to_c()
-        w = _abi.NetWeights()
-        for k, _ in _abi.NetWeights._fields_:
-            setattr(w, k, None if weights.get(k) is None else weights[k].data_ptr())
+        w = _net_weights(weights)
         arr = (_abi.BwdSeg * len(segs))()
         for a, sg in zip(arr, segs):
-            for k in ("g", "m", "v", "st_prev", "dx_next"):
-                setattr(a, k, None if sg.get(k) is None else sg[k].data_ptr())
-            a.B, a.D = int(sg["B"]), int(sg["D"])
+            _fill(a, sg)
         _abi.check(self.lib.l2o_cwlstm_bwd_multi(C.byref(cc), C.byref(w), arr, len(segs), _ptr(carry_in),
                                                  _ptr(carry_out), _ptr(A), _ptr(Bm), float(pow1), float(pow2),
                                                  self._stream()))
@@ -917,9 +873,7 @@ class HipEngine(object):
         compact: A is [T + 1, rows, KA - 40] -- the rows without their duplicated h1(t-1) / h2(t-1) columns
         (l2o_cwlstm_bwd_unroll_compact; read by wgrad_compact)."""
         cc = spec.to_c()
-        w = _abi.NetWeights()
-        for k, _ in _abi.NetWeights._fields_:
-            setattr(w, k, None if weights.get(k) is None else weights[k].data_ptr())
+        w = _net_weights(weights)
         if table is None:
             table = self.bwd_table(panels, T)
         arr = (_abi.BwdUnrollSeg * len(panels))()
@@ -959,22 +913,17 @@ class HipEngine(object):
         nbytes = int(self.lib.l2o_unroll_workspace_bytes(C.byref(cc), C.byref(cp), int(T)))
         ws = None
         if nbytes:
-            ws = self._workspace
+            old = self._workspace
             layout = int(self.lib.l2o_unroll_workspace_layout(C.byref(cc), C.byref(cp)))
-            if ws is None or ws.numel() < nbytes:
-                ws = self._workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-            elif layout != self.__dict__.get("_ws_layout"):
+            ws = self._cached_buffer("_workspace", nbytes, torch.uint8)
+            if ws is old and layout != self.__dict__.get("_ws_layout"):
                 # the granule area moved: zero the workspace once (the library keeps it clean between launches)
                 _abi.check(self.lib.l2o_unroll_workspace_init(C.c_void_p(ws.data_ptr()), ws.numel(), self._stream()))
             self._ws_layout = layout
         self._last_ws = ws
         wsp = None if ws is None else C.c_void_p(ws.data_ptr())
         flags = _abi.UNROLL_ZERO_STATE if zero_state else 0
-        h = None
-        if hist is not None:
-            h = _abi.UnrollHist()
-            for k, _ in _abi.UnrollHist._fields_:
-                setattr(h, k, None if hist.get(k) is None else hist[k].data_ptr())
+        h = None if hist is None else _fill(_abi.UnrollHist(), hist)
         if fx is not None:
             _abi.check(self.lib.l2o_unroll_reduce(C.byref(cc), _ptr(wpack), C.byref(cp), _ptr(x0), _ptr(x), _ptr(st), _ptr(m),
                                                   _ptr(v), int(T), int(step0), flags, _ptr(fx_part), _ptr(fx),
@@ -1093,15 +1042,18 @@ class HipEngine(object):
                 ws.zero_()
             _abi.check(self.lib.l2o_unroll_status(hdr))
 
+    def _atb_workspace(self, R, KA, KB):
+        """The split-K workspace atb, wgrad and wgrad_compact share: l2o_atb_workspace_bytes answers in bytes, the buffer is
+        held as floats."""
+        n = int(self.lib.l2o_atb_workspace_bytes(int(R), int(KA), int(KB)))
+        return self._cached_buffer("_atb_ws", (n + 3) // 4)
+
     def atb(self, A, B):
         """A^T B for tall-skinny fp32 device matrices A [R, KA], B [R, KB] (l2o_atb: split-K over the rows on the
         matrix cores, fixed-order reduction) -> new [KA, KB] device tensor."""
         R, KA = A.shape
         KB = B.shape[1]
-        n = int(self.lib.l2o_atb_workspace_bytes(int(R), int(KA), int(KB)))
-        ws = self.__dict__.get("_atb_ws")
-        if ws is None or ws.numel() * 4 < n:
-            ws = self._atb_ws = self.empty((n + 3) // 4)
+        ws = self._atb_workspace(R, KA, KB)
         out = self.empty(KA, KB)
         _abi.check(self.lib.l2o_atb(_ptr(A), _ptr(B), int(R), int(KA), int(KB), _ptr(out), _ptr(ws), self._stream()))
         return out
@@ -1115,10 +1067,7 @@ class HipEngine(object):
         ka, kb = C.c_int32(0), C.c_int32(0)
         _abi.check(self.lib.l2o_cwlstm_wgrad_dims(C.byref(cc), C.byref(ka), C.byref(kb)))
         assert (ka.value, kb.value) == (KA, KB), ((ka.value, kb.value), (KA, KB))
-        n = int(self.lib.l2o_atb_workspace_bytes(int(R), int(KA), int(KB)))
-        ws = self.__dict__.get("_atb_ws")
-        if ws is None or ws.numel() * 4 < n:
-            ws = self._atb_ws = self.empty((n + 3) // 4)
+        ws = self._atb_workspace(R, KA, KB)
         out = self.empty(KA, KB)
         _abi.check(self.lib.l2o_cwlstm_wgrad(C.byref(cc), _ptr(A), _ptr(B), int(R), _ptr(out), _ptr(ws), self._stream()))
         return out
@@ -1132,10 +1081,7 @@ class HipEngine(object):
         _abi.check(self.lib.l2o_cwlstm_wgrad_dims(C.byref(cc), C.byref(ka), C.byref(kb)))
         KA = ka.value
         assert kb.value == KB and tuple(Ac.shape) == (T + 1, R, KA - 40), (tuple(Ac.shape), (T + 1, R, KA - 40), KB)
-        n = int(self.lib.l2o_atb_workspace_bytes(int(T * R), int(KA), int(KB)))
-        ws = self.__dict__.get("_atb_ws")
-        if ws is None or ws.numel() * 4 < n:
-            ws = self._atb_ws = self.empty((n + 3) // 4)
+        ws = self._atb_workspace(T * R, KA, KB)
         out = self.empty(KA, KB)
         _abi.check(self.lib.l2o_cwlstm_wgrad_compact(C.byref(cc), _ptr(Ac), _ptr(Bm), int(T), int(R), _ptr(out), _ptr(ws),
                                                      self._stream()))
@@ -1171,10 +1117,7 @@ class HipEngine(object):
         b, rows, cols = A3.shape
         if out is None:
             out = self.empty(b, cols) if A.dim() == 3 else self.empty(cols)
-        n = int(self.lib.l2o_colsum_scratch_floats(b, cols))
-        scr = self.__dict__.get("_colsum_scratch")
-        if scr is None or scr.numel() < n:
-            scr = self._colsum_scratch = self.empty(n)
+        scr = self._cached_buffer("_colsum_scratch", int(self.lib.l2o_colsum_scratch_floats(b, cols)))
         _abi.check(self.lib.l2o_colsum(_ptr(A3), b, rows, cols, _ptr(out), 1 if accumulate else 0, _ptr(scr), self._stream()))
         return out
 

@@ -10,22 +10,12 @@ import numpy as np
 import torch
 
 from . import _abi, networks
-from ._engine import ALL_STEP_OPTIMIZEES, STEP_OPTIMIZEES, MlpDesc, step_optimizee
+from ._engine import MlpDesc, step_optimizee
 from ._graph_core import PackedState, _DevGrad, _LazyHost, _term_vars, _world, rng  # noqa: F401
 
 # the optimizees that are ONE term over several variables, evaluated by an entry point of their own with the random x-scaling
-# applied around it (_engine.STEP_OPTIMIZEES: problems.mnist, mnist_conv, cifar10, LeNet, confocal_microscopy_3d), and those
-# of them that draw a minibatch per evaluation (all but the last)
-_MULTIVAR = tuple(sorted(STEP_OPTIMIZEES))
-_SAMPLED = tuple(k for k in _MULTIVAR if STEP_OPTIMIZEES[k].sampled)
-# ... and the same two tuples over every kind, the later additions (problems.vgg16_cifar10) included: what the graph and
-# meta.py test a term's kind against (the two above keep the values tests/test_step_optimizees_cpu.py pins)
-MULTIVAR_KINDS = tuple(sorted(ALL_STEP_OPTIMIZEES))
-SAMPLED_KINDS = tuple(k for k in MULTIVAR_KINDS if ALL_STEP_OPTIMIZEES[k].sampled)
-
-
-# The four tuples above are values that tests pin; the graph and meta.py ask these two instead, which go over the open
-# registry (_engine.STEP_REGISTRY): a kind added there is a step-path optimizee everywhere, with no table to extend.
+# applied around it, and those of them that draw a minibatch per evaluation (all but confocal_microscopy_3d): the graph and
+# meta.py ask these two, which read the one table (_engine.STEP_OPTIMIZEES)
 def is_multivar(kind):
     """True for a step-path optimizee: ONE term over several variables, evaluated by an entry point of its own."""
     return step_optimizee(kind) is not None
@@ -35,6 +25,7 @@ def is_sampled(kind):
     """True for a step-path optimizee that draws a minibatch per evaluation."""
     entry = step_optimizee(kind)
     return entry is not None and entry.sampled
+
 
 # the optimizees that also have a fused unroll -- the T steps in ONE launch: the term's problem kind, the engine's
 # single-launch method (<method>_supported answers for a (net, descriptor) pair) and the kind's own conditions on the graph

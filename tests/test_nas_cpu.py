@@ -101,32 +101,31 @@ def test_missing_data_error_and_cifar_multi(tmp_path, monkeypatch):
     assert "conv_channels" in str(ei.value) and not isinstance(ei.value, FileNotFoundError)
 
 
-# 3. the open registry
+# 3. the registry
 def test_registry_membership():
     """Membership, never equality: the kind after this one changes no line here."""
     e = _engine.step_optimizee(_abi.PROB_NAS)
-    assert type(e) is _engine.StepOptimizee and _engine.STEP_REGISTRY[11] is e
+    assert type(e) is _engine.StepOptimizee and _engine.STEP_OPTIMIZEES[11] is e
     assert (e.method, e.stem, e.scratch, e.sampled) == ("nas_fg", "l2o_nas", "_nas_scratch", True)
     assert e.desc is _engine.NasDesc and issubclass(_engine.NasDesc, _engine.ImageNetDesc)
-    assert e.struct is _abi.Nas and issubclass(_abi.Nas, _abi.ImageNet) and (e.struct, e.stem) in _abi.STEP_FG_OPEN
+    assert e.struct is _abi.Nas and issubclass(_abi.Nas, _abi.ImageNet) and (e.struct, e.stem) in _abi.STEP_FG
     assert e.nvars(_engine.NasDesc(2, True, None, None)) == 18 and e.nvars(_engine.NasDesc(2, False, None, None)) == 10
     assert _engine._ENTRY_OF_METHOD["nas_fg"] is e and callable(_engine.HipEngine.nas_fg)
     assert _graph_steps.is_multivar(11) and _graph_steps.is_sampled(11)
-    # every earlier kind answers through the same functions as its pinned table says
-    for kind, entry in _engine.ALL_STEP_OPTIMIZEES.items():
-        assert _engine.step_optimizee(kind) is entry and _engine.STEP_REGISTRY[kind] is entry
+    # every kind answers through the same functions as the table says
+    for kind, entry in _engine.STEP_OPTIMIZEES.items():
+        assert _engine.step_optimizee(kind) is entry
         assert _graph_steps.is_multivar(kind) and _graph_steps.is_sampled(kind) == entry.sampled
         assert _engine._ENTRY_OF_METHOD[entry.method] is entry
-        assert (kind in _graph_steps.MULTIVAR_KINDS) and ((kind in _graph_steps.SAMPLED_KINDS) == entry.sampled)
-    assert set(range(5, 11)) <= set(_engine.STEP_REGISTRY)
+    assert set(range(5, 12)) <= set(_engine.STEP_OPTIMIZEES)
+    kinds = tuple(range(12)) + (99,)
+    assert tuple(k for k in kinds if _graph_steps.is_multivar(k)) == (5, 6, 7, 8, 9, 10, 11)
+    assert tuple(k for k in kinds if _graph_steps.is_sampled(k)) == (5, 6, 7, 8, 10, 11)
     assert _graph_steps.is_sampled(_abi.PROB_CONFOCAL) is False and _graph_steps.is_multivar(_abi.PROB_CONFOCAL)
     for kind in (0, 1, 2, 3, 4, 99):
         assert _engine.step_optimizee(kind) is None
         assert not _graph_steps.is_multivar(kind) and not _graph_steps.is_sampled(kind)
-    assert _engine._ENTRY_OF_METHOD["vgg16_fg"] is _engine.LATER_STEP_OPTIMIZEES[_abi.PROB_VGG16]
-    # the pinned names keep no trace of kind 11
-    assert 11 not in _engine.ALL_STEP_OPTIMIZEES and 11 not in _graph_steps.MULTIVAR_KINDS
-    assert all(stem != "l2o_nas" for _, stem in _abi.STEP_FG + _abi.STEP_FG_LATER)
+    assert _engine._ENTRY_OF_METHOD["vgg16_fg"] is _engine.STEP_OPTIMIZEES[_abi.PROB_VGG16]
 
 
 # 4. the library

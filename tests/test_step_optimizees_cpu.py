@@ -1,10 +1,12 @@
 """The Python host layer of the step-path optimizees (problems.mnist with several hidden layers, mnist_conv, cifar10, LeNet,
-confocal_microscopy_3d) is one table, _engine.STEP_OPTIMIZEES, and what reads it.  Pinned here, as literals: the table's
-kinds and the tuples derived from it, the symbols and structs of the binding, the public names and signatures that tests,
+confocal_microscopy_3d, vgg16_cifar10, NAS) is one table, _engine.STEP_OPTIMIZEES, and what reads it.  Pinned here, as
+literals: every kind's entry and the predicates that read the table, the symbols and structs of the binding (one prototype
+table, _abi.PROTOTYPES, which a library must export whole), the public names and signatures that tests,
 scripts and oracle engines use, and the texts of the refusals -- in the factories (no GPU) and in the engine (GPU)."""
 import ctypes as C
 import hashlib
 import inspect
+import os
 
 import numpy as np
 import pytest
@@ -19,6 +21,8 @@ TABLE = {
     7: ("cifar_conv_fg", "l2o_cifar_conv", "_cifar_conv_scratch", True),
     8: ("lenet_fg", "l2o_lenet", "_lenet_scratch", True),
     9: ("confocal_fg", "l2o_confocal", "_confocal_scratch", False),
+    10: ("vgg16_fg", "l2o_vgg16", "_vgg16_scratch", True),
+    11: ("nas_fg", "l2o_nas", "_nas_scratch", True),
 }
 IMAGE_NETS = {
     "mnist_conv": (6, problems.synthetic_mnist, problems.mnist_conv, "28x28x1"),
@@ -29,16 +33,21 @@ IMAGE_NETS = {
 
 
 def test_table_has_each_kind_once():
-    assert (_abi.PROB_MLP, _abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV, _abi.PROB_LENET, _abi.PROB_CONFOCAL) == (5, 6, 7, 8, 9)
-    assert sorted(STEP_OPTIMIZEES) == [5, 6, 7, 8, 9]
-    assert {k: (e.method, e.stem, e.scratch, e.sampled) for k, e in STEP_OPTIMIZEES.items()} == TABLE
-    assert [STEP_OPTIMIZEES[k].desc for k in (5, 6, 7, 8, 9)] == [
-        _engine.MlpDeepDesc, _engine.MnistConvDesc, _engine.CifarConvDesc, _engine.LenetDesc, _engine.ConfocalDesc]
-    assert [STEP_OPTIMIZEES[k].struct for k in (5, 6, 7, 8, 9)] == [
-        _abi.MlpDeep, _abi.MnistConv, _abi.CifarConv, _abi.Lenet, _abi.Confocal]
-    for e in STEP_OPTIMIZEES.values():
+    """Membership, never equality, for the set of kinds: the kind after these changes no line here."""
+    assert (_abi.PROB_MLP, _abi.PROB_MNIST_CONV, _abi.PROB_CIFAR_CONV, _abi.PROB_LENET, _abi.PROB_CONFOCAL, _abi.PROB_VGG16,
+            _abi.PROB_NAS) == (5, 6, 7, 8, 9, 10, 11)
+    assert set(range(5, 12)) <= set(STEP_OPTIMIZEES)
+    assert {k: (e.method, e.stem, e.scratch, e.sampled) for k, e in STEP_OPTIMIZEES.items() if k in TABLE} == TABLE
+    assert [STEP_OPTIMIZEES[k].desc for k in (5, 6, 7, 8, 9, 10, 11)] == [
+        _engine.MlpDeepDesc, _engine.MnistConvDesc, _engine.CifarConvDesc, _engine.LenetDesc, _engine.ConfocalDesc,
+        _engine.Vgg16Desc, _engine.NasDesc]
+    assert [STEP_OPTIMIZEES[k].struct for k in (5, 6, 7, 8, 9, 10, 11)] == [
+        _abi.MlpDeep, _abi.MnistConv, _abi.CifarConv, _abi.Lenet, _abi.Confocal, _abi.Vgg16, _abi.Nas]
+    for k, e in STEP_OPTIMIZEES.items():
+        assert type(e) is _engine.StepOptimizee and _engine.step_optimizee(k) is e
         assert (e.struct, e.stem) in _abi.STEP_FG and callable(getattr(_engine.HipEngine, e.method))
-    assert len(_abi.STEP_FG) == 5
+    for k in (0, 1, 2, 3, 4, 99):
+        assert _engine.step_optimizee(k) is None
 
 
 def test_variable_counts():
@@ -48,19 +57,27 @@ def test_variable_counts():
     assert STEP_OPTIMIZEES[5].nvars(_engine.MlpDeepDesc(784, (20, 20), 10, 128, 0, None, None)) == 6
     assert STEP_OPTIMIZEES[5].nvars(_engine.MlpDeepDesc(784, (20, 20, 20), 10, 128, 0, None, None)) == 8
     assert STEP_OPTIMIZEES[9].nvars(_engine.ConfocalDesc(32, 5, (28, 28, 28))) == 31
+    assert STEP_OPTIMIZEES[10].nvars(_engine.Vgg16Desc(2, (8, 8, 8, 8, 8), None, None)) == 28
+    e = STEP_OPTIMIZEES[11]
+    assert e.nvars(e.desc(2, True, None, None)) == 18 and e.nvars(e.desc(2, False, None, None)) == 10
 
 
 def test_derived_kind_tuples():
-    assert _graph_steps._SAMPLED == (5, 6, 7, 8)
-    assert _graph_steps._MULTIVAR == (5, 6, 7, 8, 9)
+    """What used to be tuples derived from the table are the two predicates the graph and meta.py ask."""
+    kinds = tuple(range(12)) + (99,)
+    assert tuple(k for k in kinds if _graph_steps.is_multivar(k)) == (5, 6, 7, 8, 9, 10, 11)
+    assert tuple(k for k in kinds if _graph_steps.is_sampled(k)) == (5, 6, 7, 8, 10, 11)
+    assert all(type(f(k)) is bool for f in (_graph_steps.is_multivar, _graph_steps.is_sampled) for k in kinds)
 
 
 def test_symbols_are_declared():
     import __graft_entry__  # noqa: F401
     lib = _abi.lib()
-    for e in STEP_OPTIMIZEES.values():
+    home = {5: _abi.SYMBOLS, 6: _abi.SYMBOLS, 7: _abi.SYMBOLS, 8: _abi.SYMBOLS, 9: _abi.SYMBOLS, 10: _abi.VGG16_SYMBOLS,
+            11: _abi.NAS_SYMBOLS}                              # (the header that declares the kind's two symbols)
+    for k, e in STEP_OPTIMIZEES.items():
         floats, fg = e.stem + "_scratch_floats", e.stem + "_fg"
-        assert floats in _abi.SYMBOLS and fg in _abi.SYMBOLS
+        assert k not in home or (floats in home[k] and fg in home[k])
         assert getattr(lib, floats).restype is C.c_size_t and getattr(lib, floats).argtypes == [C.POINTER(e.struct)]
         assert getattr(lib, fg).restype is C.c_int and getattr(lib, fg).argtypes == [C.POINTER(e.struct)] + [C.c_void_p] * 6
     # the list and its order, as before the table existed (sha256 of the names joined by blanks)
@@ -70,6 +87,56 @@ def test_symbols_are_declared():
         "l2o_mlp_deep_fg", "l2o_mlp_deep_scratch_floats", "l2o_mnist_conv_fg", "l2o_mnist_conv_scratch_floats",
         "l2o_cifar_conv_fg", "l2o_cifar_conv_scratch_floats", "l2o_lenet_fg", "l2o_lenet_scratch_floats",
         "l2o_confocal_fg", "l2o_confocal_scratch_floats")
+
+
+SYMBOL_TUPLES = ("SYMBOLS", "CONFOCAL_UNROLL_SYMBOLS", "CONFOCAL_MULTI_SYMBOLS", "MLP_HVP_SYMBOLS", "VGG16_SYMBOLS",
+                 "NAS_SYMBOLS", "KLSTM_SYMBOLS")
+
+
+def test_every_listed_symbol_has_a_prototype():
+    listed = [name for t in SYMBOL_TUPLES for name in getattr(_abi, t)]
+    table = {name: proto for protos in _abi.PROTOTYPES.values() for name, proto in protos.items()}
+    assert len(listed) == len(set(listed)) == 84 and set(listed) == set(table)
+    assert sum(len(protos) for protos in _abi.PROTOTYPES.values()) == 84         # (no symbol under two headers)
+    for name in listed:
+        restype, argtypes = table[name]
+        assert restype in (C.c_int, C.c_int32, C.c_int64, C.c_size_t, C.c_char_p) and type(argtypes) is list, name
+        if name.endswith(("_scratch_floats", "_workspace_bytes", "_state_floats", "l2o_wpack_floats")):
+            assert restype is C.c_size_t, name                                    # (ctypes' default int would truncate it)
+    for struct, stem in _abi.STEP_FG:
+        assert table[stem + "_fg"] == (C.c_int, [C.POINTER(struct)] + [C.c_void_p] * 6)
+        assert table[stem + "_scratch_floats"] == (C.c_size_t, [C.POINTER(struct)])
+    assert [stem for _, stem in _abi.STEP_FG] == ["l2o_mlp_deep", "l2o_mnist_conv", "l2o_cifar_conv", "l2o_lenet",
+                                                  "l2o_confocal", "l2o_vgg16", "l2o_nas"]
+    # the headers of include/ are the table's keys, and the loaded library carries exactly the table's prototypes
+    import __graft_entry__
+    assert sorted(_abi.PROTOTYPES) == sorted(os.listdir(os.path.join(__graft_entry__.ROOT, "include")))
+    lib = _abi.lib()
+    for name, (restype, argtypes) in table.items():
+        assert getattr(lib, name).restype is restype and getattr(lib, name).argtypes == argtypes, name
+
+
+class _Without(object):
+    """Stands in for a loaded library that exports every listed symbol but `missing`."""
+
+    def __init__(self, *missing):
+        for protos in _abi.PROTOTYPES.values():
+            for name in protos:
+                if name not in missing:
+                    setattr(self, name, type("fn", (), {})())
+
+
+def test_a_library_that_lacks_a_listed_symbol_is_refused_at_load():
+    whole = _Without()
+    assert _abi.declare(whole) is whole
+    assert whole.l2o_nas_scratch_floats.restype is C.c_size_t and whole.l2o_klstm_step.argtypes[0] is C.POINTER(_abi.KlstmNet)
+    for missing in (("l2o_klstm_bwd_step",), ("l2o_abi_version",), ("l2o_confocal_unroll_multi", "l2o_vgg16_fg")):
+        stale = _Without(*missing)
+        with pytest.raises(RuntimeError) as ei:
+            _abi.declare(stale)
+        assert str(ei.value) == ("open_l2o_amd: %s has no %s: the library is stale (built from older sources) -- rebuild it "
+                                 "with `make -C open_l2o_amd/csrc`" % (_abi.LIB_PATH, ", ".join(missing)))
+        assert not hasattr(stale.l2o_build_id, "restype")                         # (refused whole: nothing was declared)
 
 
 def test_image_net_structs():

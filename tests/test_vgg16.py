@@ -192,7 +192,7 @@ def test_bit_contracts(eng):
 def test_engine_wiring(eng):
     """Minibatches 4, 2, 8: forward only gives the bits of the call with gradients, the scratch is kept while it is large
     enough and replaced by a larger one when not; then the variable-count, minibatch and width refusals."""
-    entry = _engine.ALL_STEP_OPTIMIZEES[_abi.PROB_VGG16]
+    entry = _engine.STEP_OPTIMIZEES[_abi.PROB_VGG16]
     data = _data(8, seed=1)
     images, labels = eng.tensor(data["images"].reshape(8, -1)), eng.int_tensor(data["labels"])
     w = _weights(NARROW, "sample", seed=2)

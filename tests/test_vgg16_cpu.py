@@ -100,20 +100,20 @@ def test_get_config():
     assert [tuple(v.shape) for v in problem().variables] == R.shapes(NARROW)
 
 
-# 3. the companion table
+# 3. the table entry
 def test_later_kinds_table():
-    """The pinned table keeps its five kinds; vgg16 lives in the companion table, with the same entry type, and everything
-    that looks a kind up reads the union."""
-    assert sorted(_engine.STEP_OPTIMIZEES) == [5, 6, 7, 8, 9] and sorted(_engine.LATER_STEP_OPTIMIZEES) == [10]
-    assert sorted(_engine.ALL_STEP_OPTIMIZEES) == [5, 6, 7, 8, 9, 10]
-    e = _engine.LATER_STEP_OPTIMIZEES[_abi.PROB_VGG16]
-    assert type(e) is _engine.StepOptimizee
+    """vgg16 is kind 10 of the one table, with the entry type of the kinds before it; everything that looks a kind up reads
+    that table."""
+    assert set(range(5, 11)) <= set(_engine.STEP_OPTIMIZEES)
+    e = _engine.STEP_OPTIMIZEES[_abi.PROB_VGG16]
+    assert type(e) is _engine.StepOptimizee and _engine.step_optimizee(10) is e
     assert (e.method, e.stem, e.scratch, e.sampled) == ("vgg16_fg", "l2o_vgg16", "_vgg16_scratch", True)
-    assert e.desc is _engine.Vgg16Desc and e.struct is _abi.Vgg16 and (e.struct, e.stem) in _abi.STEP_FG_LATER
+    assert e.desc is _engine.Vgg16Desc and e.struct is _abi.Vgg16 and (e.struct, e.stem) in _abi.STEP_FG
     assert e.nvars(_engine.Vgg16Desc(2, NARROW, None, None)) == 28
     assert _engine._ENTRY_OF_METHOD["vgg16_fg"] is e and callable(_engine.HipEngine.vgg16_fg)
-    assert _graph_steps._MULTIVAR == (5, 6, 7, 8, 9) and _graph_steps._SAMPLED == (5, 6, 7, 8)
-    assert _graph_steps.MULTIVAR_KINDS == (5, 6, 7, 8, 9, 10) and _graph_steps.SAMPLED_KINDS == (5, 6, 7, 8, 10)
+    kinds = tuple(range(11)) + (99,)
+    assert tuple(k for k in kinds if _graph_steps.is_multivar(k)) == (5, 6, 7, 8, 9, 10)
+    assert tuple(k for k in kinds if _graph_steps.is_sampled(k)) == (5, 6, 7, 8, 10)
     assert C.sizeof(_abi.Vgg16) == 48 and _abi.Vgg16.__doc__.startswith("struct l2o_vgg16")
 
 
