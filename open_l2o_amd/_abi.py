@@ -418,14 +418,14 @@ class L2OPartnerTimeout(L2OError):
 
 
 def source_build_id():
-    """What l2o_build_id() of a library built from the sources in this tree returns (csrc/Makefile: sha256 over the two .hip
+    """What l2o_build_id() of a library built from the sources in this tree returns (csrc/Makefile: sha256 over the .hip
     translation units, every header of csrc/ and include/ and the Makefile in make's $(sort) order), or None without the
     sources."""
     import glob
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
-    names = ["l2o_kernels.hip", "l2o_kernels_ilp.hip", "Makefile"] + \
-        [os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.h"))] + \
+    names = ["Makefile"] + \
+        [os.path.basename(p) for ext in ("*.hip", "*.h") for p in glob.glob(os.path.join(csrc, ext))] + \
         ["../../include/" + os.path.basename(p) for p in glob.glob(os.path.join(csrc, "../../include/*.h"))]
     h = hashlib.sha256()
     try:

@@ -2,7 +2,7 @@
 // KA <= 112, KB <= 192.  Every weight gradient of a recorded unroll is a block of this one product
 // (meta_minimize, DM/meta.py:398-414: A = [act1 | act2 | h2 | feats | 1], B = [dz1 | dz2 | dd | du] as emitted by
 // l2o_cwlstm_bwd_unroll; KA x KB = 82 x 161 (L2O-DM), 83 x 161 (LogAndSign), 103 x 181 (RNNProp)).
-// Included by l2o_kernels.hip.
+// Included by l2o_core.hip (alone: g_atb_phase below is a __device__ global).
 //
 // Split-K over the rows: a persistent workgroup walks row blocks of 32, keeps the WHOLE KA x KB result in its
 // accumulators (MT x NT tiles of 16 x 16 over 4 waves, v_mfma_f32_16x16x4_f32: exact fp32 products and sums, like

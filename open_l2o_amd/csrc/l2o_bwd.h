@@ -1,7 +1,7 @@
 // l2o_bwd.h -- one step of back-propagation-through-time of the coordinate-wise optimizer
 // network (the meta-gradient of MetaOptimizer.meta_minimize, DM/meta.py:398-414, with the
 // optimizee gradient treated as a constant: tf.stop_gradient, DM/meta.py:328-329).
-// Included by l2o_kernels.hip.
+// Included by l2o_bwd.hip (and, for l2o_bwd_mfma.h's weight layout, by l2o_core.hip: templates only, no code there).
 //
 // Kernel of the TRAINING path: one thread per coordinate, weights (Sonnet layouts) read as
 // scalar loads (wave-uniform addresses -> SGPR operands), the step's forward recomputed from the

@@ -1,7 +1,7 @@
 // l2o_bwd_mfma.h -- one back-propagation-through-time step of the optimizer network on the bf16
 // matrix cores (the meta-gradient of MetaOptimizer.meta_minimize, DM/meta.py:398-414; optimizee
 // gradient held constant, DM/meta.py:328-329).  Same contract, same A / Bm / carry layouts as
-// k_cwlstm_bwd_tile (l2o_bwd.h); launched by l2o_kernels.hip (launch_bwd_tile).
+// k_cwlstm_bwd_tile (l2o_bwd.h); launched by l2o_bwd.hip (launch_bwd_tile).
 //
 // Why: k_cwlstm_bwd_tile spends 33 us per step on 16 384 coordinates (79 000 cycles per 16-coordinate
 // tile) reading fp32 weight rows from LDS for scalar FMAs; the forward step of the same network

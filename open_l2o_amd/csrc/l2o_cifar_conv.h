@@ -2,8 +2,8 @@
 // conv 3x3x3x16 stride 2 VALID (32x32 -> 15x15) -> [BN] -> ReLU -> max-pool 2x2 (15x15 -> 7x7: row / column 14 dropped)
 // -> conv 5x5x16x32 stride 2 VALID (7x7 -> 2x2) -> [BN] -> ReLU -> max-pool 2x2 (-> 1x1x32) -> fc 32x10 -> ReLU -> mean
 // sparse softmax cross-entropy.  BN = tf.layers.batch_normalization(training=True): batch statistics over (N, H, W),
-// biased variance, eps 1e-3.  NHWC activations, HWIO weights.  The step-granular evaluation l2o_cifar_conv_fg; it builds on
-// l2o_mnist_conv.h, whose cv_* reductions (256 threads, templated on the channel count) it calls;
+// biased variance, eps 1e-3.  NHWC activations, HWIO weights.  The step-granular evaluation l2o_cifar_conv_fg; it calls
+// the cv_* reductions of l2o_conv_bn.h (256 threads, templated on the channel count); included by l2o_nets.hip;
 // written for gfx950 only.
 //
 // Six launches per evaluation, fp32 VALU, every reduction in a fixed order (no atomics: bit-reproducible):
@@ -23,7 +23,7 @@
 //                 thread 0 the mean loss
 // Forward only (g == NULL): the first three (up to the loss) and the loss sum.
 #pragma once
-#include "l2o_mnist_conv.h"
+#include "l2o_conv_bn.h"
 
 namespace l2o {
 

@@ -5,7 +5,7 @@
 //   E[k] = erf((k + 0.5 - c) / (sqrt2 sigma)) - erf((k - 0.5 - c) / (sqrt2 sigma)),
 // with (I0, x0, y0, z0, sigma_xy, sigma_z) affine in the raw trainable values (the quantiles of uniform priors, not
 // clipped).  The target is the same sum over the simulation parameters, or a supplied volume (inference) whose flat voxel
-// index is (iy Rx + ix) Rz + iz.  The step-granular evaluation l2o_confocal_fg; included by l2o_kernels.hip; written for
+// index is (iy Rx + ix) Rz + iz.  The step-granular evaluation l2o_confocal_fg; included by l2o_confocal.hip; written for
 // gfx950 only.
 //
 // The image of a point is separable, so everything is computed from per-point, per-axis tables of at most 32 entries

@@ -8,7 +8,7 @@
 // Also serves RNNprop.__call__(m, g, state): `direct_inputs` feeds (m~, g~) as given (no moment update).
 // State layout (l2o_gen_state_floats): per layer l, hidden [N][H_l] then cell [N][H_l] -- the reference's
 // ((hidden_1, cell_1), (hidden_2, cell_2), ...) tuples stored back to back.
-// Included by l2o_kernels.hip.
+// Included by l2o_bwd.hip.
 #pragma once
 #include "l2o_params.h"
 

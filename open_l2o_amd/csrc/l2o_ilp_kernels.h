@@ -1,5 +1,5 @@
-// l2o_ilp_kernels.h -- the kernels that are compiled in a SECOND translation unit (l2o_kernels_ilp.hip) under hipcc's
-// max-ILP scheduling strategy (-mllvm -amdgpu-sched-strategy=max-ilp, a per-TU switch).  Included by both: in the main TU as
+// l2o_ilp_kernels.h -- the kernels that are compiled in a translation unit of their own (l2o_kernels_ilp.hip) under hipcc's
+// max-ILP scheduling strategy (-mllvm -amdgpu-sched-strategy=max-ilp, a per-TU switch).  Included by both: in l2o_unroll.hip as
 // `extern template` declarations (no code there; the launchers bind to the host stubs of the other object), in the ILP TU
 // (which defines L2O_TU_ILP) as explicit instantiations.
 //

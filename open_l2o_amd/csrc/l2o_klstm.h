@@ -23,7 +23,7 @@
 // (l2o_generic.h) with a K-wide dd and the unit-major state / carry layout.  It recomputes the step from the state before
 // it and emits act_l [N][in_l + H_l], dz_l [N][4 H_l], h_last [N][H_L], dd [N][K]; the host contracts them (l2o_atb /
 // l2o_colsum).  Until the backward sweep overwrites them, dz_l holds the gate activations and tc [sum H][N] tanh(c').
-// Included by l2o_kernels.hip.
+// Included by l2o_bwd.hip.
 #pragma once
 #include "l2o_common.h"
 

@@ -3,8 +3,8 @@
 // sigmoid -> max-pool 2x2 (5x5x16) -> flatten NHWC (400) -> linear 400x120 -> [BN over the minibatch] -> sigmoid -> linear
 // 120x84 -> [BN] -> sigmoid -> linear 84x10 -> mean sparse softmax cross-entropy.  BN = snt.BatchNorm in training mode:
 // batch statistics, biased variance, eps 1e-3, an offset beta and NO scale.  NHWC activations, HWIO / [in, out] weights.
-// The step-granular evaluation l2o_lenet_fg; it builds on l2o_mnist_conv.h, whose cv_* reductions
-// (256 threads) the conv half calls; written for gfx950 only.
+// The step-granular evaluation l2o_lenet_fg; the conv half calls the cv_* reductions of l2o_conv_bn.h
+// (256 threads); included by l2o_nets.hip; written for gfx950 only.
 //
 // sigmoid is strictly increasing, so the pools take the maximum of the normalised pre-activation (first maximum of the
 // window in row-major order) and one sigmoid is applied per pooled output.
@@ -34,7 +34,7 @@
 //                 conv betas, the last linear layer; thread 0 the mean loss
 // Forward only (g == NULL): the first six and the loss sum.
 #pragma once
-#include "l2o_mnist_conv.h"
+#include "l2o_conv_bn.h"
 
 namespace l2o {
 

@@ -2,7 +2,7 @@
 // (DM/problems.py:246-288), a [n_in -> n_hidden -> n_out] MLP with mean sparse-softmax
 // cross-entropy on a gathered minibatch: forward + gradient in two small multi-workgroup
 // launches (8 MFLOP per evaluation: latency-, not throughput-bound; the LSTM step on its
-// 15 910 coordinates runs in k_cwlstm_step).  Included by l2o_kernels.hip.
+// 15 910 coordinates runs in k_cwlstm_step).  Included by l2o_mlp.hip.
 //   k_mlp_fwd : 4 samples per workgroup, 64 threads per sample over the 784 inputs (w1 rows
 //               straight from L2 for the common hidden width 20)
 //               -> H, dZ = (softmax - onehot)/batch, dH, per-sample loss (scratch in HBM)

@@ -1,6 +1,6 @@
 // l2o_mlp_deep.h -- forward + gradient of problems.mnist with MORE THAN ONE hidden layer (DM/problems.py:254-288 builds
 // snt.nets.MLP(list(layers) + [10]); DM/util.py:157-163 "mnist_deeper" = layers (20, 20)): the step-granular evaluation
-// l2o_mlp_deep_fg.  Included by l2o_kernels.hip; written for gfx950 only.
+// l2o_mlp_deep_fg.  Included by l2o_mlp.hip; written for gfx950 only.
 //
 // Not a fast path (the fused unrolls serve the one-hidden-layer optimizee of BASELINE config 5): two launches per
 // evaluation, correctness-first.

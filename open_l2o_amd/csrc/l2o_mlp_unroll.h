@@ -2,7 +2,7 @@
 // (DM/problems.py:246-288: a [n_in -> H -> O] MLP, mean sparse-softmax cross-entropy on a fresh
 // minibatch per evaluation, DM/problems.py:282-286) stepped by ONE coordinate-wise LSTM optimizer shared by
 // its four variables (DM/meta.py:338-359; RNNProp DM/meta_rnnprop_train.py:371-423): T steps in ONE launch.
-// Included by l2o_kernels.hip.
+// Included by l2o_mlp.hip.
 //
 // Why: the step-granular path spends 22 us per step in three latency-bound launches (forward, backward,
 // LSTM step) and re-reads the 5 MB of LSTM state and the weight fragments every step.  Here every

@@ -2,7 +2,7 @@
 // conv 3x3x1x16 VALID -> [BN] -> ReLU -> max-pool 2x2 -> conv 5x5x16x32 VALID -> [BN] -> ReLU -> max-pool 2x2 (9x9 -> 4x4:
 // row / column 8 dropped) -> fc 512x10 -> ReLU -> mean sparse softmax cross-entropy.  BN = tf.layers.batch_normalization(
 // training=True): batch statistics over (N, H, W), biased variance, eps 1e-3.  NHWC activations, HWIO weights.
-// The step-granular evaluation l2o_mnist_conv_fg; included by l2o_kernels.hip; written for gfx950 only.
+// The step-granular evaluation l2o_mnist_conv_fg; included by l2o_nets.hip; written for gfx950 only.
 //
 // Six launches per evaluation, fp32 VALU, every reduction in a fixed order (no atomics: bit-reproducible):
 //   k_cv_conv1    one workgroup per sample: conv1 (+ bias); the sample's per-channel (mean, M2) of z1
@@ -17,18 +17,17 @@
 //                 gamma / beta, the fc weights, the conv biases (under batch norm in a factored form, cv_bn_bias_grad);
 //                 thread 0 the mean loss
 // Forward only (g == NULL): the first three (up to the loss) and the loss sum.
-// BN variance: per-sample (mean, M2) merged as M2 = sum M2_s + n sum (mean_s - mean)^2 (never E[z^2] - E[z]^2).
+// BN variance: per-sample (mean, M2) merged as M2 = sum M2_s + n sum (mean_s - mean)^2 (never E[z^2] - E[z]^2): the
+// reductions of l2o_conv_bn.h (kCvThreads, kCvEps and the cv_* functions).
 #pragma once
-#include "l2o_params.h"
+#include "l2o_conv_bn.h"
 
 namespace l2o {
 
-constexpr int kCvThreads = 256;
 constexpr int kCvMaxBatch = 1024;
 constexpr int kCvC1 = 16, kCvC2 = 32, kCvOut = 10;
 constexpr int kCvP1 = 26 * 26, kCvQ1 = 13 * 13, kCvP2 = 9 * 9, kCvQ2 = 4 * 4;
 constexpr int kCvNW1 = 3 * 3 * kCvC1, kCvNW2 = 5 * 5 * kCvC1 * kCvC2, kCvNF = kCvQ2 * kCvC2;   // 144, 12800, 512
-constexpr float kCvEps = 1e-3f;
 
 // per-sample scratch, in floats (offsets of one sample's slice inside each region)
 constexpr int kCvZ1 = kCvP1 * kCvC1;      // 10816: z1, and dL/dy1
@@ -63,131 +62,6 @@ struct MnistConvArgs {
   float* pw1;     // [batch][160]
   float* loss;    // [1]
 };
-
-// Per-channel sums of v[pos * C + c] over npos positions: lane l of channel c takes pos = l, l + L, ... (L = 256 / C) in
-// order, then the L lane sums in lane order.  Returns the sum to threads tid < C (others: 0).
-template <int C>
-__device__ float cv_chan_sum(const float* v, int npos, float* red) {
-  constexpr int L = kCvThreads / C;
-  const int tid = threadIdx.x, c = tid % C, l = tid / C;
-  float s = 0.0f;
-  for (int p = l; p < npos; p += L) s += v[p * C + c];
-  red[tid] = s;
-  __syncthreads();
-  float t = 0.0f;
-  if (tid < C)
-    for (int k = 0; k < L; ++k) t += red[k * C + c];
-  __syncthreads();
-  return t;
-}
-
-// (mean, M2) of one sample's channels, two passes over the LDS-resident values; written to part[c][2].
-template <int C>
-__device__ void cv_sample_stats(const float* v, int npos, float* red, float* mean_sh, float* part) {
-  const int tid = threadIdx.x;
-  const float s = cv_chan_sum<C>(v, npos, red);
-  if (tid < C) mean_sh[tid] = s / (float)npos;
-  __syncthreads();
-  constexpr int L = kCvThreads / C;
-  const int c = tid % C, l = tid / C;
-  const float m = mean_sh[c];
-  float q = 0.0f;
-  for (int p = l; p < npos; p += L) {
-    const float d = v[p * C + c] - m;
-    q = __builtin_fmaf(d, d, q);
-  }
-  red[tid] = q;
-  __syncthreads();
-  if (tid < C) {
-    float t = 0.0f;
-    for (int k = 0; k < L; ++k) t += red[k * C + c];
-    part[2 * tid] = mean_sh[tid];
-    part[2 * tid + 1] = t;
-  }
-  __syncthreads();
-}
-
-// BN statistics of the minibatch from the per-sample (mean, M2) partials part[s][C][2] (n positions per sample), the same
-// fixed order in every workgroup: mean -> mean_sh[C], 1 / sqrt(var + eps) -> rstd_sh[C].
-template <int C>
-__device__ void cv_merge_stats(const float* part, int B, float n, float* red, float* mean_sh, float* rstd_sh) {
-  constexpr int L = kCvThreads / C;
-  const int tid = threadIdx.x, c = tid % C, l = tid / C;
-  float s = 0.0f;
-  for (int b = l; b < B; b += L) s += part[(b * C + c) * 2];
-  red[tid] = s;
-  __syncthreads();
-  if (tid < C) {
-    float t = 0.0f;
-    for (int k = 0; k < L; ++k) t += red[k * C + c];
-    mean_sh[tid] = t / (float)B;
-  }
-  __syncthreads();
-  const float m = mean_sh[c];
-  float q = 0.0f;
-  for (int b = l; b < B; b += L) {
-    const float d = part[(b * C + c) * 2] - m;
-    q += __builtin_fmaf(n * d, d, part[(b * C + c) * 2 + 1]);
-  }
-  red[tid] = q;
-  __syncthreads();
-  if (tid < C) {
-    float t = 0.0f;
-    for (int k = 0; k < L; ++k) t += red[k * C + c];
-    rstd_sh[tid] = 1.0f / sqrtf(t / (n * (float)B) + kCvEps);
-  }
-  __syncthreads();
-}
-
-// Means over the minibatch of the per-sample sums part[s][C][2] (n positions per sample): -> a_sh[C], b_sh[C].
-template <int C>
-__device__ void cv_merge_means(const float* part, int B, float n, float* red, float* a_sh, float* b_sh) {
-  constexpr int L = kCvThreads / C;
-  const int tid = threadIdx.x, c = tid % C, l = tid / C;
-  for (int j = 0; j < 2; ++j) {
-    float s = 0.0f;
-    for (int b = l; b < B; b += L) s += part[(b * C + c) * 2 + j];
-    red[tid] = s;
-    __syncthreads();
-    if (tid < C) {
-      float t = 0.0f;
-      for (int k = 0; k < L; ++k) t += red[k * C + c];
-      (j == 0 ? a_sh : b_sh)[tid] = t / (n * (float)B);
-    }
-    __syncthreads();
-  }
-}
-
-// Per-sample (sum dy, sum dy * xhat) of one layer: dy[pos * C + c] in LDS, z from `z` (same layout), BN stats in LDS.
-template <int C>
-__device__ void cv_sample_bwd_sums(const float* dy, const float* z, int npos, const float* mean_sh, const float* rstd_sh,
-                                   float* red, float* part) {
-  constexpr int L = kCvThreads / C;
-  const int tid = threadIdx.x, c = tid % C, l = tid / C;
-  const float m = mean_sh[c], r = rstd_sh[c];
-  float s0 = 0.0f, s1 = 0.0f;
-  for (int p = l; p < npos; p += L) {
-    const float d = dy[p * C + c];
-    s0 += d;
-    s1 = __builtin_fmaf(d, (z[p * C + c] - m) * r, s1);
-  }
-  red[tid] = s0;
-  __syncthreads();
-  if (tid < C) {
-    float t = 0.0f;
-    for (int k = 0; k < L; ++k) t += red[k * C + c];
-    part[2 * tid] = t;
-  }
-  __syncthreads();
-  red[tid] = s1;
-  __syncthreads();
-  if (tid < C) {
-    float t = 0.0f;
-    for (int k = 0; k < L; ++k) t += red[k * C + c];
-    part[2 * tid + 1] = t;
-  }
-  __syncthreads();
-}
 
 __global__ __launch_bounds__(kCvThreads) void k_cv_conv1(MnistConvArgs a) {
   __shared__ float img[784];
@@ -500,21 +374,6 @@ __global__ __launch_bounds__(kCvThreads) void k_cv_first(MnistConvArgs a) {
     for (int p = 0; p < kCvP1; ++p) acc += dz[p * kCvC1 + c];
     pw[tid] = acc;
   }
-}
-
-// A conv bias followed by batch norm: sum_i dz_i = gamma rstd (sum dy - N mean(dy) - mean(dy xhat) sum xhat) with
-// sum xhat = n rstd sum_s (mean_s - mean) -- zero in exact arithmetic (batch norm removes any per-channel shift).  Summing
-// the N = n B values dz_i themselves leaves O(sqrt(N) eps |dz|) of noise; this factored form leaves O(eps |sum dy|).
-__device__ float cv_bn_bias_grad(const float* st, const float* bw, const float* mean, const float* rstd, const float* gamma,
-                                 int C, int c, int B, float n) {
-  float sdy = 0.0f, sdx = 0.0f, sx = 0.0f;
-  for (int s = 0; s < B; ++s) {
-    sdy += bw[(s * C + c) * 2];
-    sdx += bw[(s * C + c) * 2 + 1];
-    sx += st[(s * C + c) * 2] - mean[c];
-  }
-  const float N = n * (float)B, r = rstd[c];
-  return gamma[c] * r * ((sdy - N * (sdy / N)) - (sdx / N) * (n * r * sx));
 }
 
 // the minibatch sums, one thread per coordinate, in sample order

@@ -1,5 +1,5 @@
 // l2o_nas.h -- problems.NAS (DM/problems.py:540-634): the NAS-cell conv net on CIFAR-10, loss and gradients of one
-// minibatch.  Included by l2o_kernels.hip (host side: l2o_nas_fg there).
+// minibatch.  Included by l2o_nets.hip (host side: l2o_nas_fg there).
 //
 // Four layers L = relu([batch norm](conv 3x3 SAME + bias)) of 16 channels at 32x32 -- node0 (from the 3-channel image),
 // n02 and node1 (both from node0) and n13 (from node1) -- then node3 = avg_pool3x3(node1) + n02 + n13 + node0, its mean
@@ -25,13 +25,13 @@
 //   k_ns_wgrad<CIN, NOUT>      rows = (tap, c_in), reduction = pixels, columns = NOUT; a workgroup walks the strips
 //        blockIdx.x, + gridDim.x, ..., its four waves a quarter of each strip; the waves' accumulators are added in wave
 //        order, every workgroup writes its partial, and k_ns_wsum adds the partials in a fixed order
-// Batch-norm statistics: per-sample (mean, M2) partials (cv_sample_stats) merged in a fixed order (cv_merge_stats), as in
-// l2o_mnist_conv.h; the backward sums (sum dy, sum dy xhat) likewise per sample, then in sample order.  Under batch norm
+// Batch-norm statistics: per-sample (mean, M2) partials (cv_sample_stats) merged in a fixed order (cv_merge_stats), both of
+// l2o_conv_bn.h; the backward sums (sum dy, sum dy xhat) likewise per sample, then in sample order.  Under batch norm
 // the gradient of a conv bias is 0 in exact arithmetic; it is written as that analytic 0 (not in cv_bn_bias_grad's
 // factored form).  No atomics anywhere.
 #pragma once
 #include "l2o_common.h"
-#include "l2o_mnist_conv.h"
+#include "l2o_conv_bn.h"
 #include "../../include/l2o_nas_abi.h"
 
 constexpr int kNsThreads = 256;

@@ -1,6 +1,6 @@
 // l2o_unroll_cu.h -- the fused persistent unroll for optimizees that do NOT fit a CU's LDS
 // (D <= 512 with D % 4 == 0, any M: BASELINE config 3 = Lasso 256 x 512 per problem).  Launched by
-// l2o_kernels.hip (launch_unroll_cu); written for gfx950 only.
+// l2o_unroll.hip (launch_unroll_cu); written for gfx950 only.
 //
 // Replaces, for these sizes, the step-granular pair {l2o_problem_fg, l2o_cwlstm_step} x T
 // (DM/meta.py:338-359 time_step; RNNProp fork DM/meta_rnnprop_train.py:397-423) with ONE

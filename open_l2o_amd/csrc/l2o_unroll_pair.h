@@ -1,5 +1,5 @@
 // l2o_unroll_pair.h -- the fused persistent unroll with every problem split over TWO
-// workgroups (two CUs).  Launched by l2o_kernels.hip (launch_unroll_ch).
+// workgroups (two CUs).  Launched by l2o_unroll.hip (launch_unroll_ch).
 //
 // Why: a batch of B <= #CU/2 problems (BASELINE config 2: B = 128 on 256 CUs) leaves half
 // the chip idle with one problem per CU, and the per-step critical path of a problem is

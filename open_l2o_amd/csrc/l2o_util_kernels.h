@@ -1,5 +1,6 @@
 // l2o_util_kernels.h -- the small kernels that are no templates (emitted by the one translation unit that includes this:
-// the main one): state repack, loss reductions, the co-residency probe, the weight packer, Adam.
+// l2o_core.hip): state repack, loss reductions, the co-residency probe, the weight packer, Adam.  l2o_unroll.hip launches
+// k_combine_halves and k_coresident_probe, l2o_confocal.hip k_reduce_fx, each through a declaration of its own.
 #pragma once
 #include "l2o_bwd_mfma.h"
 #include "l2o_unroll_pair.h"

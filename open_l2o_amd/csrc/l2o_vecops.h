@@ -2,7 +2,7 @@
 // Until round 4 these ran as torch tensor arithmetic in open_l2o_amd/meta.py (.sum, torch.sqrt, torch.where, chains of
 // adds): generic `layers` BPTT, the Linear-only net, second derivatives.  Not hot -- a T-step training unroll calls each
 // of them once or T times on a few thousand to a few hundred thousand floats -- but the training path now runs on l2o_*
-// entry points only.  Included by l2o_kernels.hip.
+// entry points only.  Included by l2o_core.hip.
 #pragma once
 #include "l2o_params.h"
 

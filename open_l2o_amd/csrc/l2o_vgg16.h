@@ -1,5 +1,5 @@
 // l2o_vgg16.h -- problems.vgg16_cifar10 (DM/problems.py:637-694, DM/vgg16.py): VGG-16 on CIFAR-10 without batch norm,
-// loss and gradients of one minibatch.  Included by l2o_kernels.hip (host side: l2o_vgg16_fg there).
+// loss and gradients of one minibatch.  Included by l2o_nets.hip (host side: l2o_vgg16_fg there).
 //
 // Thirteen 3x3 SAME convolutions in five blocks of (2, 2, 3, 3, 3) layers, ReLU after each, max-pool 2x2 after each block,
 // then linear x10, softmax, and a softmax cross-entropy that takes the probabilities as logits.  Activations NHWC, weights

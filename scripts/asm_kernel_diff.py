@@ -1,5 +1,5 @@
-"""Per-symbol comparison of two device assembly files (hipcc --cuda-device-only -S of one translation unit, before and after
-a change that must not touch device code): the same functions, each with the same instructions, the same .amdhsa_ descriptor
+"""Per-symbol comparison of two device assembly files (hipcc --cuda-device-only -S of one translation unit -- or the .s files of
+make -C open_l2o_amd/csrc asm, concatenated -- before and after a change that must not touch device code): the same functions, each with the same instructions, the same .amdhsa_ descriptor
 and the same metadata entry.  Function ORDER may differ, so the numbers in local labels are normalised.
   python scripts/asm_kernel_diff.py before.s after.s"""
 import re, sys
@@ -13,7 +13,7 @@ def symbols(path):
     for m in re.finditer(r'^\t\.amdhsa_kernel (\S+)\n(.*?)^\t\.end_amdhsa_kernel', s, re.M | re.S):
         out['desc ' + m.group(1)] = m.group(2)
     for b in s.split('  - .agpr_count:')[1:]:
-        out['meta ' + re.search(r'\.name:\s+(\S+)', b).group(1)] = b.split('\namdhsa.target')[0]
+        out['meta ' + re.search(r'\.name:\s+(\S+)', b).group(1)] = b.split('\namdhsa.target')[0].rstrip()   # (the last entry of a file has no newline)
     return out
 
 a, b = symbols(sys.argv[1]), symbols(sys.argv[2])

@@ -1,5 +1,5 @@
 // What does a process see of a CU mask?  Prints the device's CU count, the stream's CU mask (hipExtStreamGetCUMask) and the
-// MEASURED number of co-resident one-per-CU workgroups (the probe kernel of l2o_kernels.hip: every workgroup bumps a
+// MEASURED number of co-resident one-per-CU workgroups (the probe kernel of l2o_util_kernels.h: every workgroup bumps a
 // counter and waits -- bounded -- until all have arrived).
 //   hipcc --offload-arch=gfx950 -O2 cu_mask_probe.hip -o cu_mask_probe && ./cu_mask_probe
 //   ROC_GLOBAL_CU_MASK=0xffffffffffffffffffffffffffffffff ./cu_mask_probe ;  HSA_CU_MASK=0:0-127 ./cu_mask_probe

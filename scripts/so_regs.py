@@ -7,7 +7,7 @@ pat = sys.argv[2] if len(sys.argv) > 2 else ''
 data = open(lib, 'rb').read()
 MAGIC = b'__CLANG_OFFLOAD_BUNDLE__'
 start = 0
-while True:                                     # one bundle per translation unit (csrc/Makefile links two)
+while True:                                     # one bundle per translation unit (csrc/Makefile: SRCS)
     i = data.find(MAGIC, start)
     if i < 0:
         break

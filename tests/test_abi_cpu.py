@@ -132,6 +132,64 @@ def test_bad_arguments_return_error_codes(lib):
         assert lib.l2o_unroll_supported(C.byref(cc), C.byref(p)) == 0
 
 
+def _simple_problem():
+    from open_l2o_amd import _abi
+    p = _abi.Problem()
+    p.kind, p.B_local, p.B_global, p.D = _abi.PROB_SIMPLE, 1, 1, 1
+    return p
+
+
+# One call per host translation unit of csrc/ that validation refuses before any HIP call: (symbol, arguments).  Every
+# descriptor is NULL (l2o_unroll: a valid problem and a NULL net, so that the message is the entry point's own).
+REFUSED_CALLS = (
+    ("l2o_atb", lambda: (None, None, 0, 0, 0, None, None, None)),                                      # l2o_core.hip
+    ("l2o_unroll", lambda: (None, None, C.byref(_simple_problem())) + (None,) * 4 + (0, 0) + (None,) * 3),  # l2o_unroll.hip
+    ("l2o_cwlstm_bwd_step", lambda: (None, None, None, 0.0, 0.0, 0, 0, None)),                        # l2o_bwd.hip
+    ("l2o_klstm_step", lambda: (None, None, None, None, None, 1, None)),                              # l2o_bwd.hip
+    ("l2o_mlp_deep_fg", lambda: (None,) * 7),                                                          # l2o_mlp.hip
+    ("l2o_mnist_conv_fg", lambda: (None,) * 7),                                                        # l2o_nets.hip
+    ("l2o_nas_fg", lambda: (None,) * 7),                                                               # l2o_nets.hip
+    ("l2o_confocal_fg", lambda: (None,) * 7),                                                          # l2o_confocal.hip
+)
+
+
+def _refuse(lib, name, args):
+    """Make the refused call and return this thread's l2o_last_error() after it, which must be that call's own."""
+    rc = getattr(lib, name)(*args())
+    assert rc != 0, name
+    msg = lib.l2o_last_error()
+    assert msg.startswith(name.encode() + b":"), (name, msg)
+    return msg
+
+
+@pytest.mark.parametrize("name,args", REFUSED_CALLS, ids=[c[0] for c in REFUSED_CALLS])
+def test_every_host_unit_reports_through_one_last_error(lib, name, args):
+    """The error text is ONE thread-local of the library, whichever translation unit the refusing entry point lives in:
+    l2o_last_error() returns the message of the call just made, not an earlier one's."""
+    other = next(c for c in REFUSED_CALLS if c[0] != name)
+    before = _refuse(lib, *other)
+    assert _refuse(lib, name, args) != before
+
+
+def test_last_error_is_per_thread(lib):
+    import threading
+    mine = _refuse(lib, *REFUSED_CALLS[0])
+    seen = []
+
+    def worker():
+        try:
+            seen.extend(_refuse(lib, n, a) for n, a in REFUSED_CALLS[1:])
+        except Exception as e:                      # (an assertion in a thread would otherwise only be printed)
+            seen.append(e)
+
+    t = threading.Thread(target=worker)
+    t.start()
+    t.join()
+    assert len(seen) == len(REFUSED_CALLS) - 1 and all(isinstance(m, bytes) for m in seen), seen
+    assert len(set(seen)) == len(seen)
+    assert lib.l2o_last_error() == mine
+
+
 @pytest.mark.parametrize("name", ["dm", "dm_logsign", "rnnprop"])
 def test_packed_weights_reproduce_oracle_under_mfma_layout(lib, name):
     from open_l2o_amd._engine import pack_weights_host

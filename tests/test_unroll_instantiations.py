@@ -1,7 +1,7 @@
 """Every instantiation of the fused unroll that the launchers can select, run once against a float64 reference.
 
 The fused unroll (l2o_unroll / l2o_unroll_record / l2o_unroll_reduce) is five kernel templates; launch_unroll_ch and
-launch_unroll_cu (csrc/l2o_kernels.hip) pick one instantiation per call.  The cell table below is BUILT from those
+launch_unroll_cu (csrc/l2o_unroll.hip) pick one instantiation per call.  The cell table below is BUILT from those
 dispatch rules (``_enumerate``), steered with the per-call options, and every cell asserts the template
 (``last_unroll_form``) and the template arguments (``last_unroll_variant``) that ran.
 
@@ -120,7 +120,7 @@ Cell = collections.namedtuple("Cell", "template net kind D variant options secon
 VARIANT0 = dict(CH=0, HIST=0, EXACT=0, FAST=0, KR=0, NV=0)
 
 
-# ---- the dispatch rules, restated (csrc/l2o_kernels.hip: unroll_geom, launch_unroll_ch, launch_unroll_cu) -------------
+# ---- the dispatch rules, restated (csrc/l2o_unroll.hip: unroll_geom, launch_unroll_ch, launch_unroll_cu) -------------
 def geom_ch(D, M):
     """CH of the LDS-resident forms, or None: the streaming form takes the shape."""
     nw = (D + 15) // 16
