@@ -802,6 +802,27 @@ class HipEngine(object):
         c = _fill(_abi.KlstmBwdIO(), io, checked=True)
         _abi.check(self.lib.l2o_klstm_bwd_step(C.byref(net.device_net(self).c), C.byref(c), int(N), self._stream()))
 
+    # -- twin.unroll (l2o_twin_unroll of libl2o_twin.so, csrc_twin/l2o_twin_abi.h) ------------------------
+    def twin_unroll(self, nets, problem, run, theta, states, record=()):
+        """The Twin-L2O evaluation unroll of every instance in one launch.  Host arrays in, host arrays out:
+        nets ((hidden, n_in, {torch parameter name: array}) for min and max), problem (kind, dim, data), run (dict: iter0,
+        n_iter, n_sign, rescale, out_mul, sign_lr), theta [n_inst, 2, dim], states ([4, H, rows] for min and max), record
+        (any of "curve", "f", "delta").  Returns a dict: theta, states and the recorded arrays in the library's layouts
+        (curve [n_iter, n_inst, 2 dim], f [n_iter, n_inst], delta [n_iter, n_inst, dim])."""
+        from . import _twin_abi as T
+        kind, dim, data = problem
+        theta_d, st = self.tensor(theta), [self.tensor(s) for s in states]
+        n_inst, n_iter = int(theta_d.shape[0]), int(run["n_iter"])
+        dev = T.Device(self, nets, (kind, n_inst, dim, data), run)
+        shapes = {"curve": (n_iter, n_inst, 2 * int(dim)), "f": (n_iter, n_inst), "delta": (n_iter, n_inst, int(dim))}
+        out = {k: (self.empty(*shapes[k]) if k in record else None) for k in shapes}
+        with torch.cuda.device(self.device):
+            T.check(dev.unroll(theta_d, st[0], st[1], out["curve"], out["f"], out["delta"], self._stream()))
+        res = {k: (None if t is None else self.to_numpy(t)) for k, t in out.items()}
+        res["theta"] = self.to_numpy(theta_d)
+        res["states"] = tuple(self.to_numpy(s) for s in st)
+        return res
+
     def lstm_step(self, spec: NetSpec, wpack, g, m, v, pow1, pow2, st, x, B, D):
         if isinstance(wpack, HipEngine.GenNet):
             return self.lstm_step_generic(spec, wpack, g, None, m, v, pow1, pow2, st, x, B * D)

@@ -1,0 +1,212 @@
+"""open_l2o_amd.twin on the CPU: the host logic of the Twin-L2O evaluation unroll on TorchTwinEngine (twin_reference.py: the
+float32 torch restatement behind the engine seam) -- gradients, parameter names, the step schedule, curve_info and the
+distances, the reference's config files, the refusals, and the driver end to end."""
+import contextlib
+import importlib.util
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import twin_reference as TR
+from open_l2o_amd import _engine, twin
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden", "twin")
+CONFIGS = ("saddle_test.json", "rotatedsaddle_test.json", "seesaw_test.json", "matrix_game_dim5_test.json")
+
+
+@contextlib.contextmanager
+def as_default(engine):
+    old = _engine._default_engine
+    _engine.set_default_engine(engine)
+    try:
+        yield engine
+    finally:
+        _engine.set_default_engine(old)
+
+
+def load_driver():
+    spec = importlib.util.spec_from_file_location("evaluate_twin", os.path.join(HERE, "..", "scripts", "evaluate_twin.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def make_data(kind, n, dim, seed):
+    rng = np.random.default_rng(seed)
+    if kind == 4:
+        return (rng.uniform(0.5, 1.0, (n, dim, dim)) * (rng.uniform(size=(n, dim, dim)) < 0.5)).astype(np.float32)
+    return rng.uniform(0.5, 3.0, (n, 2)).astype(np.float32)
+
+
+@pytest.mark.parametrize("kind,dim", [(1, 1), (2, 1), (3, 1), (4, 5)])
+def test_gradients_are_autograd_of_objective(kind, dim):
+    data = torch.tensor(make_data(kind, 6, dim, 1), dtype=torch.float64)
+    g = torch.Generator().manual_seed(2)
+    u = torch.rand((6, dim), generator=g, dtype=torch.float64, requires_grad=True)
+    v = torch.rand((6, dim), generator=g, dtype=torch.float64, requires_grad=True)
+    au, av = torch.autograd.grad(TR.objective(kind, data, u, v).sum(), (u, v))
+    gu, gv = TR.gradients(kind, data, u, v)
+    assert torch.allclose(gu, au, rtol=1e-12, atol=1e-14) and torch.allclose(gv, av, rtol=1e-12, atol=1e-14)
+
+
+class RefOptimizer(torch.nn.Module):
+    """A plain torch module with the reference's attribute (hence parameter) names."""
+
+    def __init__(self, H, n_in):
+        super().__init__()
+        self.recurs = torch.nn.LSTMCell(n_in, H)
+        self.recurs2 = torch.nn.LSTMCell(H, H)
+        self.output = torch.nn.Linear(H, 1)
+
+
+def test_state_dict_round_trip_and_reference_pth(tmp_path):
+    opt = twin.Optimizer(hidden_size=7, seed=3)
+    sd = opt.state_dict()
+    assert tuple(sd.keys()) == twin.PARAM_NAMES
+    bound = 1 / math.sqrt(7)
+    assert all(float(t.abs().max()) <= bound for t in sd.values()) and float(sd["recurs2.weight_hh"].abs().max()) > 0.8 * bound
+    other = twin.Optimizer(hidden_size=7, seed=4).load_state_dict(sd)
+    assert all(np.array_equal(other.params[k], opt.params[k]) for k in twin.PARAM_NAMES)
+    torch.manual_seed(5)
+    ref = RefOptimizer(7, 2)
+    torch.save(ref.state_dict(), tmp_path / "bestmin.pth")
+    got = twin.Optimizer(hidden_size=7).load_state_dict(torch.load(tmp_path / "bestmin.pth"))
+    for k, t in ref.state_dict().items():
+        assert np.array_equal(got.params[k], t.numpy()), k
+    with pytest.raises(ValueError):
+        twin.Optimizer(hidden_size=8).load_state_dict(ref.state_dict())
+    one = twin.Optimizer(hidden_size=7, use_second=False)
+    assert one.n_in == 1 and one.params["recurs.weight_ih"].shape == (28, 1)
+
+
+@pytest.mark.parametrize("optim_it", [5, 20, 40, 2000])
+def test_schedule(optim_it):
+    n_sign, lr = twin.schedule(optim_it)
+    sche_lr = list(np.arange(1e-4, 1e-1, (1e-1 - 1e-4) / int(0.2 * optim_it)))
+    assert n_sign == sum(1 for it in range(1, optim_it + 1) if it < 0.2 * optim_it)
+    assert n_sign == {5: 0, 20: 3, 40: 7, 2000: 399}[optim_it]
+    assert lr.dtype == np.float32 and len(lr) >= n_sign
+    assert np.array_equal(lr[:n_sign], np.asarray(sche_lr[:n_sign]).astype(np.float32))
+    assert TR.schedule(optim_it)[0] == n_sign
+
+
+def test_curve_info_and_distances_on_a_hand_made_curve():
+    # one seesaw instance, a = 2: 4 iterations; |u| = 0.8 is 0.2 from 1/a = 0.5 ... nearest k/a is 1.0 (0.2) vs 0.5 (0.3)
+    prob = twin.seesaw(np.array([[2.0, 1.0], [0.5, 1.0]], np.float32))
+    curve = np.zeros((2, 5, 2), np.float32)
+    curve[0, :, 0] = [0.3, 0.8, 0.8, -0.55, -0.55]
+    curve[0, :, 1] = [0.1, 0.1, -0.2, -0.2, 0.4]
+    curve[1, :, 0] = [0.0, 0.9, 0.9, 5.1, 5.1]
+    curve[1, :, 1] = [1.0, 1.0, 2.0, 2.0, 3.0]
+    res = twin.Result(curve=curve, iter0=1, n_iter=4, optim_it=4, dim=1)
+    info = twin.curve_info(res)
+    assert info.shape == (2, 3, 2)
+    assert np.array_equal(info[0], np.array([[0.3, 0.1], [0.8, -0.2], [-0.55, 0.4]], np.float32))
+    assert np.array_equal(info, TR.curve_info(curve, 4, 1).astype(np.float32))
+    du, dv = twin.distances(prob, res)
+    np.testing.assert_allclose(du[0], [0.2, 0.2, 0.05, 0.05], rtol=1e-6)
+    np.testing.assert_allclose(du[1], [0.9, 0.9, 0.9, 0.9], rtol=1e-6)        # k / a = 0, 2, 4, 6
+    np.testing.assert_array_equal(dv[0], np.float32([0.1, 0.2, 0.2, 0.4]))
+    ru, rv = TR.distances(3, prob.data, curve, 1)
+    assert np.array_equal(du, ru) and np.array_equal(dv, rv)
+    # the matrix game: sums over the dim coordinates, 2 dim columns
+    mg = twin.matrix_game(np.ones((1, 4), np.float32), 2)
+    c4 = np.arange(12, dtype=np.float32).reshape(1, 3, 4) - 5
+    r4 = twin.Result(curve=c4, iter0=1, n_iter=2, optim_it=2, dim=2)
+    du, dv = twin.distances(mg, r4)
+    assert np.array_equal(du, [[1.0, 7.0]]) and np.array_equal(dv, [[3.0, 11.0]])
+    assert np.array_equal(twin.curve_info(r4)[0], [[-5, -4, -3, -2], [-1, 0, 5, 6]])
+    with pytest.raises(ValueError):
+        twin.curve_info(twin.Result(curve=curve, iter0=2, n_iter=3, optim_it=4, dim=1))
+
+
+@pytest.mark.parametrize("name", CONFIGS)
+def test_config_parsing(name):
+    drv = load_driver()
+    params = drv.load_config(os.path.join(GOLDEN, name))
+    assert set(params) <= set(drv.KEYS)
+    assert params["mode"] == "test" and params["test_optim_iter"] == 2000 and params["rescale"] == 1e-4
+    assert params["dim"] == (5 if "matrix" in name else 1)
+    assert params["hidden_size"] == (80 if "matrix" in name else 50)
+    params.update(n_test=8, test_epochs=2)
+    prob, mn, mx, theta0, states = drv.setup(params, GOLDEN, random_weights=True)
+    assert prob.kind == params["loss"] and prob.n_inst == 16 and prob.dim == params["dim"]
+    assert np.array_equal(prob.data[0], prob.data[1]) and not np.array_equal(prob.data[1], prob.data[2])
+    assert mn.hidden_size == params["hidden_size"] and not np.array_equal(mn.params["output.weight"], mx.params["output.weight"])
+    assert theta0.shape == (16, 2, prob.dim) and np.abs(theta0).max() < 0.5
+    assert states[0].shape == (4, params["hidden_size"], 16 * prob.dim) and 0.005 < states[0].std() < 0.02
+
+
+def test_refusals(tmp_path):
+    with pytest.raises(NotImplementedError, match="preproc"):
+        twin.Optimizer(preproc=True)
+    with pytest.raises(ValueError, match="optim_it"):
+        twin.schedule(4)
+    opt = twin.Optimizer(hidden_size=5, seed=0)
+    with as_default(TR.TorchTwinEngine()):
+        with pytest.raises(ValueError, match="optim_it"):
+            twin.unroll(twin.saddle(make_data(1, 2, 1, 0)), opt, opt, 4, seed=0)
+    for loss in (1, 2, 3):
+        with pytest.raises(ValueError, match="dim"):
+            twin.problem(loss, make_data(1, 4, 1, 0), dim=2)
+    with pytest.raises(ValueError):
+        twin.problem(5, make_data(1, 4, 1, 0))
+    cfg = json.load(open(os.path.join(GOLDEN, "seesaw_test.json")))
+    cfg["mode"] = "train"
+    (tmp_path / "train.json").write_text(json.dumps(cfg))
+    with pytest.raises(NotImplementedError, match="meta-training"):
+        load_driver().load_config(str(tmp_path / "train.json"))
+    with pytest.raises(FileNotFoundError, match="random-weights"):
+        load_driver().setup(dict(cfg, mode="test", dim=1, n_test=8), GOLDEN, random_weights=False)
+
+
+def test_unroll_on_the_torch_engine_continues_and_matches_float64():
+    prob = twin.matrix_game(make_data(4, 3, 5, 7), 5)
+    mn, mx = twin.Optimizer(hidden_size=6, seed=1), twin.Optimizer(hidden_size=9, seed=2)
+    with as_default(TR.TorchTwinEngine()):
+        whole = twin.unroll(prob, mn, mx, 20, seed=11, record=("curve", "f", "delta"))
+        theta0, states = twin.draw_start(prob, mn, mx, seed=11)
+        a = twin.unroll(prob, mn, mx, 20, theta0=theta0, states=states, n_iter=7, record=("curve",))
+        b = twin.unroll(prob, mn, mx, 20, theta0=a.theta, states=a.states, iter0=8, record=("curve",))
+    assert whole.curve.shape == (3, 21, 10) and whole.f.shape == (3, 20) and whole.delta.shape == (3, 20, 5)
+    assert np.array_equal(whole.curve[:, 0], theta0.reshape(3, 10))
+    assert np.array_equal(np.concatenate([a.curve, b.curve[:, 1:]], axis=1), whole.curve)
+    assert np.array_equal(whole.theta.reshape(3, 10), whole.curve[:, -1])
+    # odd iterations move u alone, even ones v alone; the first 3 by exactly the schedule
+    step = np.diff(whole.curve.astype(np.float64), axis=1)
+    assert not step[:, 0::2, 5:].any() and not step[:, 1::2, :5].any()
+    n_sign, lr = twin.schedule(20)
+    for k in range(1, n_sign + 1):
+        moved = step[:, k - 1, :5] if k % 2 else step[:, k - 1, 5:]
+        np.testing.assert_allclose(np.abs(moved), lr[k - 1], rtol=0, atol=1e-7)     # (float32 points below 0.6: ulp 6e-8)
+    r64 = TR.run(torch.float64, 4, 5, prob.data, mn.params, mx.params, lr, n_sign, theta0, states, 1, 20, 1e-4, 1.0)
+    assert np.abs(whole.curve - r64["curve"]).max() < 1e-5 and np.abs(whole.f - r64["f"]).max() < 1e-5
+
+
+def test_evaluate_twin_end_to_end(tmp_path):
+    drv = load_driver()
+    cfg = json.load(open(os.path.join(GOLDEN, "seesaw_test.json")))
+    cfg.update(n_test=3, test_epochs=1, test_optim_iter=20)
+    (tmp_path / "cfg.json").write_text(json.dumps(cfg))
+    with as_default(TR.TorchTwinEngine()):
+        drv.main(["--config", str(tmp_path / "cfg.json"), "--root", GOLDEN, "--out", str(tmp_path / "out"), "--random-weights"])
+    summary = json.load(open(tmp_path / "out" / "twin_eval.json"))
+    assert summary["runs"] == 3 and summary["burn_in"] == 10
+    curves = sorted(os.listdir(tmp_path / "out" / "curve_info" / "test_example" / "best"))
+    assert len(curves) == 3 and curves[0].startswith("sample_index_0_epoch_0_u_0.929_v_0.966")
+    info = np.loadtxt(tmp_path / "out" / "curve_info" / "test_example" / "best" / curves[0])
+    assert info.shape == (11, 2)
+    # the same figures from the restatement on the same draws
+    params = drv.load_config(str(tmp_path / "cfg.json"))
+    prob, mn, mx, theta0, states = drv.setup(params, GOLDEN, random_weights=True)
+    n_sign, lr = twin.schedule(20)
+    r = TR.run(torch.float32, 3, 1, prob.data, mn.params, mx.params, lr, n_sign, theta0, states, 1, 20, 1e-4, 1.0)
+    du, dv = TR.distances(3, prob.data, r["curve"], 1)
+    want = drv.summarize(params, du, dv)
+    assert summary == pytest.approx(want, rel=1e-6)
+    assert np.allclose(info, TR.curve_info(r["curve"], 20, 1)[0], rtol=1e-6, atol=1e-7)
