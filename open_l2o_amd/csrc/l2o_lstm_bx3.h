@@ -394,15 +394,13 @@ __device__ __forceinline__ void issue(const W& w, const BOp<PK>& b, f32x4 (&acc)
 }
 
 // acc = [-log2e*i, 2log2e*j, -log2e*(f+1), -log2e*o] of the unit pair (T0, T0+1)
+// (the part of gates_pair behind the four first-stage exponentials of each unit, which the caller supplies)
 template <int T0>
-__device__ __forceinline__ void gates_pair(const f32x4 (&acc)[kNT], float (&c)[kNT], float (&h)[kNT]) {
+__device__ __forceinline__ void gates_pair_e(const f32x4 (&acc)[kNT], float (&c)[kNT], float (&h)[kNT], const f32x2 e_i,
+                                             const f32x2 E_j, const f32x2 e_f, const f32x2 e_o) {
   constexpr int T1 = T0 + 1;
   constexpr float k2 = 2.0f * 1.4426950408889634f;
   const f32x2 one = mk2(1.0f, 1.0f);
-  const f32x2 e_i = mk2(fast_exp2(acc[T0][0]), fast_exp2(acc[T1][0]));
-  const f32x2 E_j = mk2(fast_exp2(-__builtin_fabsf(acc[T0][1])), fast_exp2(-__builtin_fabsf(acc[T1][1])));
-  const f32x2 e_f = mk2(fast_exp2(acc[T0][2]), fast_exp2(acc[T1][2]));
-  const f32x2 e_o = mk2(fast_exp2(acc[T0][3]), fast_exp2(acc[T1][3]));
   const f32x2 dij = (one + e_i) * (one + E_j);
   const f32x2 df = one + e_f;
   const f32x2 ij = mk2(fast_rcp(dij.x), fast_rcp(dij.y));
@@ -418,6 +416,15 @@ __device__ __forceinline__ void gates_pair(const f32x4 (&acc)[kNT], float (&c)[k
   c[T0] = cn.x; c[T1] = cn.y;
   h[T0] = __builtin_copysignf(hh.x, cn.x);
   h[T1] = __builtin_copysignf(hh.y, cn.y);
+}
+template <int T0>
+__device__ __forceinline__ void gates_pair(const f32x4 (&acc)[kNT], float (&c)[kNT], float (&h)[kNT]) {
+  constexpr int T1 = T0 + 1;
+  const f32x2 e_i = mk2(fast_exp2(acc[T0][0]), fast_exp2(acc[T1][0]));
+  const f32x2 E_j = mk2(fast_exp2(-__builtin_fabsf(acc[T0][1])), fast_exp2(-__builtin_fabsf(acc[T1][1])));
+  const f32x2 e_f = mk2(fast_exp2(acc[T0][2]), fast_exp2(acc[T1][2]));
+  const f32x2 e_o = mk2(fast_exp2(acc[T0][3]), fast_exp2(acc[T1][3]));
+  gates_pair_e<T0>(acc, c, h, e_i, E_j, e_f, e_o);
 }
 
 // Sonnet LSTM nonlinearities (gates i, j, f, o; forget_bias folded into the weights) for the
@@ -481,6 +488,30 @@ __device__ __forceinline__ void gates5_scalar(const f32x4 (&acc)[kNT], float (&c
   }
 }
 
+// gates5 in two stages, for a caller that issues MFMAs beside the first: stage one is the twenty exponentials that read the
+// accumulators and nothing else (gates5_exps), stage two everything behind them (gates5_rest: the packed adds and multiplies,
+// the reciprocals, the exponential of the new cell state).  The caller fences the two apart, so no packed instruction
+// stands beside an MFMA.  The same operations on the same operands as gates5: bit-identical.
+struct GateExps { f32x4 e[kNT]; };
+__device__ __forceinline__ void gates5_exps(const f32x4 (&acc)[kNT], GateExps& g) {
+  static_for<0, 4 * kNT>([&](auto nc) {                       // gate-major: i of the five units, then j, f, o
+    constexpr int k = decltype(nc)::value / kNT, t = decltype(nc)::value % kNT;
+    g.e[t][k] = fast_exp2(k == 1 ? -__builtin_fabsf(acc[t][1]) : acc[t][k]);
+  });
+}
+__device__ __forceinline__ void gates5_rest(const f32x4 (&acc)[kNT], const GateExps& g, float (&c)[kNT], float (&h)[kNT]) {
+  gates_pair_e<0>(acc, c, h, mk2(g.e[0][0], g.e[1][0]), mk2(g.e[0][1], g.e[1][1]), mk2(g.e[0][2], g.e[1][2]), mk2(g.e[0][3], g.e[1][3]));
+  gates_pair_e<2>(acc, c, h, mk2(g.e[2][0], g.e[3][0]), mk2(g.e[2][1], g.e[3][1]), mk2(g.e[2][2], g.e[3][2]), mk2(g.e[2][3], g.e[3][3]));
+  constexpr float k2 = 2.0f * 1.4426950408889634f;
+  const float e_i = g.e[4][0], E_j = g.e[4][1], e_f = g.e[4][2], e_o = g.e[4][3];
+  const float ij = fast_rcp((1.0f + e_i) * (1.0f + E_j)), rf = fast_rcp(1.0f + e_f);
+  const float cn = __builtin_fmaf(rf, c[4], __builtin_copysignf((1.0f - E_j) * ij, acc[4][1]));
+  const float E_c = fast_exp2(-__builtin_fabsf(cn * k2));
+  const float ro = fast_rcp((1.0f + E_c) * (1.0f + e_o));
+  c[4] = cn;
+  h[4] = __builtin_copysignf((1.0f - E_c) * ro, cn);
+}
+
 // Everything that needs this step's gradient (see l2o::lstm_finish for the contract):
 // acc1 must hold chunk L1H (h1(t-1), bias), acc2 chunk L2B (h2(t-1)).  On return s holds the
 // new state, b1 / b2 the split h1(t) / h2(t) (the next step's L1H / L2B operands) and, with
@@ -491,12 +522,16 @@ struct NoShadow { __device__ __forceinline__ void operator()() const {} };
 // REARM: leave acc1 / acc2 re-initialised with the biases for the NEXT step (the persistent unroll kernels); tile_step
 // (a fresh pair of accumulators per call) switches it off -- the pinned loads would be 10 dead ds_read_b128 per tile
 // SR: the split of h1 in front of chunk L2A in its scalar-residual form (split5; k_unroll_pair)
-template <int PRE, bool NEXT, bool PK, class Shadow = NoShadow, bool REARM = true, class W = NetWB<PRE, PK>, bool SR = false>
+// L2B_LATE (k_unroll_pair, kPairL2bLate): the LAST L2B_LATE MFMAs of chunk L2B are issued here, beside the layer-1 gate
+// exponentials, instead of by the caller in front of finish() -- b2 must still hold the split of h2(t-1)
+template <int PRE, bool NEXT, bool PK, class Shadow = NoShadow, bool REARM = true, class W = NetWB<PRE, PK>, bool SR = false,
+          int L2B_LATE = 0>
 __device__ __forceinline__ float finish(const W& w, TileState& s, BOp<PK>& b1, BOp<PK>& b2,
                                         f32x4 (&acc1)[kNT], f32x4 (&acc2)[kNT], float in0, float in1, unsigned one,
                                         int q, PhaseClock& pc, Shadow&& shadow = Shadow()) {
   constexpr int kN = chunk_mfmas(PK);
   static_assert(!SR || (PK && !NEXT && !W::kLdsFrags), "finish: the scalar-residual split is k_unroll_pair's");
+  static_assert(L2B_LATE == 0 || (PK && !NEXT && !W::kLdsFrags && L2B_LATE <= kN), "finish: the late part of chunk L2B is k_unroll_pair's");
   if constexpr (PRE == L2O_PRE_FC_ELU) {   // (constexpr: chunk L1X does not exist for the DM nets)
     float fc[kNT];
 #pragma unroll
@@ -522,7 +557,25 @@ __device__ __forceinline__ float finish(const W& w, TileState& s, BOp<PK>& b1, B
   }
   pc.drain(acc1);
   pc.mark(5);
-  gates5(acc1, s.c1, s.h1);
+  if constexpr (L2B_LATE > 0) {
+    // The tail of chunk L2B rides on the matrix pipe under the twenty exponentials that open the layer-1 gates: one MFMA,
+    // one v_exp_f32 -- 8 + 8 cycles of vector issue in the 16 cycles the MFMA holds the matrix pipe (MI355X_MICROARCH.md,
+    // "vector-instruction ISSUE cost") -- where the same MFMA in the exchange window costs the wave all 16.  The fences keep
+    // everything else out: the packed adds and multiplies of the gates cost ~10-20 cycles each beside a busy matrix pipe
+    // and stand behind the second fence, in the stage-major order of gates5 (profiles/pair_l2b_under_gates.txt).
+    __builtin_amdgcn_sched_barrier(0);
+    issue<PRE, kChL2B, kN - L2B_LATE, kN, true>(w, b2, acc2);
+    GateExps ge;
+    gates5_exps(acc1, ge);
+#pragma unroll
+    for (int i = 0; i < L2B_LATE; ++i) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // one MFMA
+      __builtin_amdgcn_sched_group_barrier(0x400, 1, 0);    // one transcendental
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    gates5_rest(acc1, ge, s.c1, s.h1);
+  } else
+    gates5(acc1, s.c1, s.h1);
 #ifndef L2O_FINISH_PINNED_LDSFRAGS
 #define L2O_FINISH_PINNED_LDSFRAGS 0
 #endif
@@ -845,13 +898,18 @@ struct LstmCoreRegs {
   // REARM = false: the caller re-arms the accumulators itself -- arm() from the registers, or preload_unpinned() in front
   // of its barrier -- finish<.., true> issues the reads right behind the gate blocks and the pinning asm WAITS for them
   // there, i.e. in front of the split of h1 and in front of the output Linear / the x update (round 4, k_unroll_pair)
-  template <bool NEXT, class Shadow = bx::NoShadow, bool REARM = true>
+  template <bool NEXT, class Shadow = bx::NoShadow, bool REARM = true, int L2B_LATE = 0>
   __device__ __forceinline__ float finish(TileState& s, f32x4 (&acc1)[kNT], f32x4 (&acc2)[kNT], float in0, float in1,
                                           int q, PhaseClock& pc, Shadow&& shadow = Shadow()) {
-    return bx::finish<PRE, NEXT, PK, Shadow, REARM, WT, SR>(w, s, b1, b2, acc1, acc2, in0, in1, one, q, pc, static_cast<Shadow&&>(shadow));
+    return bx::finish<PRE, NEXT, PK, Shadow, REARM, WT, SR, L2B_LATE>(w, s, b1, b2, acc1, acc2, in0, in1, one, q, pc, static_cast<Shadow&&>(shadow));
   }
   // after finish<false>: b1 already holds split h1(t) (finish builds it for chunk L2A); split h2(t) for chunk L2B
   __device__ __forceinline__ void refresh(const TileState& s) { bx::split5<PK, SR>(s.h2, one, b2); }
+  // a use of the split h2: what refresh() computes is complete where this stands
+  __device__ __forceinline__ void hold_b2() {
+#pragma unroll
+    for (int j = 0; j < bx::kPack; ++j) asm volatile("" : "+v"(b2.m[j]));
+  }
 };
 template <int PRE, bool PK>
 struct LstmCore<PRE, true, PK> : LstmCoreRegs<PRE, PK, bx::NetWB<PRE, PK>> {};
@@ -877,6 +935,23 @@ template <int PRE, int KIND, int CH, bool HIST, bool EXACT, bool FAST>
 constexpr bool kPairBiasRegs =
     !HIST && !EXACT &&
     (FAST || !(PRE == L2O_PRE_LOGSIGN && (KIND == L2O_PROB_RASTRIGIN || KIND == L2O_PROB_SQUARE_COS) && CH == 8));
+// Where the plain FAST kernels of k_unroll_pair issue chunk L2B (h2(t-1) -> layer 2: kTotal = 20 MFMAs that depend on nothing
+// of the current step).  Until round 15 all twenty stood in the exchange window, in front of chunk L1H, where a lone MFMA costs
+// the wave its full 16 cycles of matrix pipe.  kPairL2bLate of them leave the window: the first kPairL2bB2 of those go out
+// behind barrier B2, in the gaps of the loss reduction's DPP chain and under the LDS latency of the g pass's residual reads;
+// the rest are issued by bx::finish beside the layer-1 exponentials.  The accumulation chain keeps its order -- bias quad as C
+// of the first MFMA, L2B products 0..3, L2A products 0..3 -- so every result keeps its bits.  The window keeps 5 + 20 MFMAs: it
+// still has to cover the partner's publish and the poll's round trip (with fewer the wave that measures itself gets faster
+// and the launch slower), and the first poll load goes out behind 10 of them (kPairPollAtLate).  Measured on config 2
+// against 20 / 0 / 0 (the parent): 10 / 7 / 3 +1.5 %, 5 / 7 / 8 +2.0 %, 0 / 7 / 13 +0.5 %, 0 / 0 / 20 +-0.2 %
+// (profiles/pair_l2b_under_gates.txt).  The bias quads of layer 2 now live until the layer-1 gates: the LogAndSign net at
+// CH = 8, at 505-509 registers before, reaches 512 with 4-31 spills and keeps the old placement, as do the recording,
+// exact-gates and gather kernels and the 6-product core -- text and ISA (scripts/so_regs.py, scripts/so_isa_diff.py).
+template <int PRE, int KIND, int CH, bool HIST, bool EXACT, bool FAST>
+constexpr int kPairL2bLate =
+    (FAST && !HIST && !EXACT && bx::packed_default(PRE) && !(PRE == L2O_PRE_LOGSIGN && CH == 8)) ? 15 : 0;
+constexpr int kPairL2bB2 = 7;
+constexpr int kPairPollAtLate = 10;
 // the 6-product form with chunk LDSCH in LDS (bx::NetWBH); stage_chunk: every thread copies its share, a barrier follows
 template <int PRE, int LDSCH>
 struct LstmCoreHyb : LstmCoreRegs<PRE, false, bx::NetWBH<PRE, LDSCH>> {

@@ -16,7 +16,8 @@
       Acc4pk r0p = {{0.f, 0.f}, {0.f, 0.f}}, r1p = {{0.f, 0.f}, {0.f, 0.f}};
       l2o::f32x4 x4v[NWH];
       lds_load_f4<NWH>(x4v, xsq);
-      core.refresh(s);                     // split h2(t-1) -> chunk L2B operand, under the LDS latency (t = 0: repeats core.init)
+      // split h2(t-1) -> chunk L2B operand, under the LDS latency (t = 0: repeats core.init); with a late chunk L2B: in the window
+      if constexpr (kL2bLate == 0) core.refresh(s);
       __builtin_amdgcn_sched_group_barrier(0x100, NWH, 0);     // the DS reads first ...
       __builtin_amdgcn_sched_group_barrier(0x002, 48, 0);      // ... then the split's VALU block, then the FMAs
 #pragma unroll
@@ -58,10 +59,26 @@
 #ifndef L2O_PAIR_POLL_AT
 #define L2O_PAIR_POLL_AT 20   // = after chunk L2B.  Packed chunks (20 MFMAs): 5 -> 7.72, 10 -> 7.86, 15 -> 7.95, 20 -> 8.02, 30 -> 7.98 G (config 2)
 #endif
-    constexpr int kPollAt = L2O_PAIR_POLL_AT < Core::kTotal ? L2O_PAIR_POLL_AT : Core::kTotal;   // MFMAs before the first poll load
-    constexpr int kPollAt1 = L2O_PAIR_POLL_AT > Core::kTotal ? L2O_PAIR_POLL_AT - Core::kTotal : 0;
-    core.template issue_l2_prev<0, kPollAt>(s, acc2);
-    if (kPollAt1 > 0) core.template issue_l1_prev<0, kPollAt1>(s, acc1);
+    // (kL2bLate MFMAs of chunk L2B are issued later -- kL2bB2 behind barrier B2, the rest by finish() under the layer-1 gates,
+    //  see kPairL2bLate: the window holds the first kWinL2)
+    constexpr int kL2bB2 = kL2bLate > 0 ? kPairL2bB2 : 0;
+    constexpr int kWinL2 = Core::kTotal - kL2bLate;
+    constexpr int kPollN = kL2bLate > 0 ? kPairPollAtLate : L2O_PAIR_POLL_AT;
+    constexpr int kPollAt = kPollN < kWinL2 ? kPollN : kWinL2;   // MFMAs before the first poll load
+    constexpr int kPollAt1 = kPollN > kWinL2 ? (kPollN - kWinL2 < Core::kTotal ? kPollN - kWinL2 : Core::kTotal) : 0;
+    // Late chunk L2B: the window is its first kWinL2 MFMAs, chunk L1H and, in their gaps, the split of h2 -- two plain
+    // instructions per gap (8 + 2 x 4 cycles of issue in the MFMA's 16); nothing of the window reads the split any more, so
+    // left alone it sinks onto the dependent chain behind barrier B2.  One scheduling region: the poll load is issued by every
+    // lane (lanes gq >= 2 read row 0's granule and drop it), so no exec-masked block cuts the window, and the group
+    // barriers place it behind kPollN MFMAs.
+    if constexpr (kL2bLate > 0) {
+      core.refresh(s);
+      core.template issue_l2_prev<0, kWinL2>(s, acc2);
+      core.template issue_l1_prev<0, Core::kTotal>(s, acc1);
+    } else {
+      core.template issue_l2_prev<0, kPollAt>(s, acc2);
+      if (kPollAt1 > 0) core.template issue_l1_prev<0, kPollAt1>(s, acc1);
+    }
     const unsigned long long* src = theirs + par * SQ + (gq < 2 ? myrow : 0);
     unsigned long long g = 0;
     // "partner timed out" costs the straight-line step nothing: a wave that has given up (poll_salt carries bit 31, which no
@@ -69,13 +86,26 @@
     // below, which is there for the spin anyway, and drops what the load returned there.  Wave-uniform and sticky: once a
     // lane of the wave has timed out, the whole wave stops waiting (its results are garbage from then on, the host reports it).
     const unsigned poll_tag = poll_salt | ((unsigned)t + 1u);
-    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (kL2bLate > 0) {
 #ifndef L2O_ABLATE_EXCHANGE
-    if (gq < 2) g = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      g = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
-    __builtin_amdgcn_sched_barrier(0);
-    if (kPollAt < Core::kTotal) core.template issue_l2_prev<kPollAt, Core::kTotal>(s, acc2);
-    core.template issue_l1_prev<kPollAt1, Core::kTotal>(s, acc1);
+      core.hold_b2();
+#pragma unroll
+      for (int i = 0; i < kWinL2 + Core::kTotal; ++i) {
+        if (i == kPollN) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+      }
+    } else {
+      __builtin_amdgcn_sched_barrier(0);
+#ifndef L2O_ABLATE_EXCHANGE
+      if (gq < 2) g = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+      __builtin_amdgcn_sched_barrier(0);
+      if (kPollAt < kWinL2) core.template issue_l2_prev<kPollAt, kWinL2>(s, acc2);
+      core.template issue_l1_prev<kPollAt1, Core::kTotal>(s, acc1);
+    }
     float contrib = 0.0f;
     if (gq < 2) {
       int spins = 0;
@@ -131,8 +161,18 @@
     l2o::f32x4 rv4v[CH];
     lds_load_f4<CH>(rv4v, rsq);
     {
+      // (late chunk L2B: kL2bB2 of its MFMAs here, one per two instructions of the reduction's DPP chain, while the wave
+      //  waits for the residual reads anyway)
+      if constexpr (kL2bB2 > 0) core.template issue_l2_prev<kWinL2, kWinL2 + kL2bB2>(s, acc2);
       const float fw = wave_sum64(contrib);
       __builtin_amdgcn_sched_group_barrier(0x100, CH, 0);      // the DS reads, then the reduction's DPP chain
+      if constexpr (kL2bB2 > 0) {
+#pragma unroll
+        for (int i = 0; i < kL2bB2; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+        }
+      } else
       __builtin_amdgcn_sched_group_barrier(0x002, 24, 0);
       // (every lane stores: wave_sum64 leaves the same bits on all 64 lanes, so the one address gets one value and the
       //  store needs no exec-masked region -- 3 857 -> 3 813 cycles per step on config 2)
@@ -142,4 +182,5 @@
 #else
       pa.fx_half[((size_t)t * pa.nb + bl) * (2 * NWH) + half * NWH + wv] = fw;
 #endif
+      if constexpr (kL2bB2 > 0) __builtin_amdgcn_sched_barrier(0);    // (the groups above end here: the g pass is scheduled on its own)
     }
