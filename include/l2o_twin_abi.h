@@ -1,7 +1,7 @@
 /* l2o_twin_abi.h -- Twin-L2O (Model_Free_L2O/L2O-Minimax/Twin-L2O.py): two per-coordinate two-layer LSTM optimizers that
- * alternate over an analytic saddle objective, the whole evaluation unroll in one launch.  The C ABI of libl2o_twin.so, a
- * library of its own beside libl2o_hip.so (whose list of exports is closed).  Error codes: those of l2o_abi.h; the text of
- * the last error of the calling thread: l2o_twin_last_error().
+ * alternate over an analytic saddle objective, the whole evaluation unroll in one launch: the part of the C ABI of
+ * libl2o_hip.so that was added after ABI v15.  Conventions (error codes, l2o_last_error): l2o_abi.h, which this header
+ * includes.  (A header of its own: l2o_abi.h's list of exports is the v15 list.)
  *
  * Objectives (l2o_twin_problem.kind; u = theta_min, v = theta_max):
  *   1 saddle          a u^2 - b v^2              2 rotated saddle   a u^2 - b v^2 + 2 u v
@@ -22,10 +22,7 @@
 #ifndef L2O_TWIN_ABI_H
 #define L2O_TWIN_ABI_H
 
-#include <stddef.h>
-#include <stdint.h>
-
-#include "../../include/l2o_abi.h" /* L2O_OK, L2O_ERR_* */
+#include "l2o_abi.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -56,9 +53,6 @@ typedef struct l2o_twin_run {
   float rescale, out_mul;
   const float* sign_lr;            /* device, indexed k-1 (may be NULL when n_sign is 0) */
 } l2o_twin_run;
-
-const char* l2o_twin_last_error(void);
-const char* l2o_twin_build_id(void);   /* sha256 over the sources, 16 hex digits (open_l2o_amd/_twin_abi.py) */
 
 int    l2o_twin_supported(const l2o_twin_net* mn, const l2o_twin_net* mx, const l2o_twin_problem* p);
 size_t l2o_twin_state_floats(const l2o_twin_net* net, int64_t rows);

@@ -255,6 +255,28 @@ class KlstmBwdIO(C.Structure):
                [("act", C.c_void_p * 2), ("dz", C.c_void_p * 2)] + [(n, C.c_void_p) for n in ("tc", "h_last", "dd")]
 
 
+TWIN_MAX_HIDDEN, TWIN_MAX_DIM = 96, 16                                          # L2O_TWIN_MAX_* (include/l2o_twin_abi.h)
+TWIN_SADDLE, TWIN_ROTATED_SADDLE, TWIN_SEESAW, TWIN_MATRIX_GAME = 1, 2, 3, 4    # l2o_twin_problem.kind
+
+
+class TwinNet(C.Structure):
+    """struct l2o_twin_net"""
+    _fields_ = [("hidden", C.c_int32), ("n_in", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("w_ih1", "w_hh1", "b_ih1", "b_hh1", "w_ih2", "w_hh2", "b_ih2", "b_hh2",
+                                          "w_out", "b_out")]
+
+
+class TwinProblem(C.Structure):
+    """struct l2o_twin_problem"""
+    _fields_ = [("kind", C.c_int32), ("n_inst", C.c_int32), ("dim", C.c_int32), ("flags", C.c_int32), ("data", C.c_void_p)]
+
+
+class TwinRun(C.Structure):
+    """struct l2o_twin_run"""
+    _fields_ = [("iter0", C.c_int32), ("n_iter", C.c_int32), ("n_sign", C.c_int32), ("rescale", C.c_float),
+                ("out_mul", C.c_float), ("sign_lr", C.c_void_p)]
+
+
 class NetWeights(C.Structure):
     """struct l2o_net_weights"""
     _fields_ = [(n, C.c_void_p) for n in ("w_gates1", "b_gates1", "w_gates2", "b_gates2", "w_lin", "b_lin",
@@ -390,6 +412,11 @@ def _prototypes():
             "l2o_klstm_step": (I, [P(KlstmNet), vp, vp, vp, vp, i64, vp]),
             "l2o_klstm_bwd_step": (I, [P(KlstmNet), P(KlstmBwdIO), i64, vp]),
         },
+        "l2o_twin_abi.h": {                  # twin.unroll: the Twin-L2O minimax evaluation unroll
+            "l2o_twin_supported": (I, [P(TwinNet), P(TwinNet), P(TwinProblem)]),
+            "l2o_twin_state_floats": (Z, [P(TwinNet), i64]),
+            "l2o_twin_unroll": (I, [P(TwinNet), P(TwinNet), P(TwinProblem), P(TwinRun)] + [vp] * 7),
+        },
     }
 
 
@@ -397,9 +424,10 @@ def _prototypes():
 # binding's order.  declare() gives a loaded library exactly these prototypes and refuses one that lacks any of them; the
 # per-header tuples below are views of it (tests hold each against its header's text).
 PROTOTYPES = _prototypes()
-SYMBOLS, CONFOCAL_UNROLL_SYMBOLS, CONFOCAL_MULTI_SYMBOLS, MLP_HVP_SYMBOLS, VGG16_SYMBOLS, NAS_SYMBOLS, KLSTM_SYMBOLS = (
-    tuple(PROTOTYPES[h]) for h in ("l2o_abi.h", "l2o_confocal_unroll_abi.h", "l2o_confocal_multi_abi.h", "l2o_mlp_hvp_abi.h",
-                                   "l2o_vgg16_abi.h", "l2o_nas_abi.h", "l2o_klstm_abi.h"))
+SYMBOLS, CONFOCAL_UNROLL_SYMBOLS, CONFOCAL_MULTI_SYMBOLS, MLP_HVP_SYMBOLS, VGG16_SYMBOLS, NAS_SYMBOLS, KLSTM_SYMBOLS, \
+    TWIN_SYMBOLS = (
+        tuple(PROTOTYPES[h]) for h in ("l2o_abi.h", "l2o_confocal_unroll_abi.h", "l2o_confocal_multi_abi.h", "l2o_mlp_hvp_abi.h",
+                                       "l2o_vgg16_abi.h", "l2o_nas_abi.h", "l2o_klstm_abi.h", "l2o_twin_abi.h"))
 
 
 class L2OError(RuntimeError):

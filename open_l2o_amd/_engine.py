@@ -240,6 +240,44 @@ def _upload_lstm_stack(engine, c, params, layers):
     return tensors + [wl, bl]
 
 
+# struct l2o_twin_net field -> torch parameter name of the reference's optimizer module
+_TWIN_NET_FIELDS = (("w_ih1", "recurs.weight_ih"), ("w_hh1", "recurs.weight_hh"), ("b_ih1", "recurs.bias_ih"),
+                    ("b_hh1", "recurs.bias_hh"), ("w_ih2", "recurs2.weight_ih"), ("w_hh2", "recurs2.weight_hh"),
+                    ("b_ih2", "recurs2.bias_ih"), ("b_hh2", "recurs2.bias_hh"), ("w_out", "output.weight"),
+                    ("b_out", "output.bias"))
+
+
+class TwinDevice(object):
+    """Device copies of what a Twin-L2O launch reads beside theta and the states -- the two networks ((hidden, n_in, {torch
+    parameter name: array}) for min and max), the instance data (problem = (kind, n_inst, dim, data)) and the schedule (run:
+    dict of iter0, n_iter, n_sign, rescale, out_mul, sign_lr) -- and the structs nets[0], nets[1], problem, run
+    (include/l2o_twin_abi.h) that point at them.  `engine` supplies tensor(): a HipEngine."""
+
+    def __init__(self, engine, nets, problem, run):
+        self.keep, self.nets = [], []
+        for hidden, n_in, params in nets:
+            c = _abi.TwinNet()
+            c.hidden, c.n_in = int(hidden), int(n_in)
+            for field, name in _TWIN_NET_FIELDS:
+                t = engine.tensor(params[name])
+                self.keep.append(t)
+                setattr(c, field, t.data_ptr())
+            self.nets.append(c)
+        kind, n_inst, dim, data = problem
+        data_d = engine.tensor(data)
+        lr_d = engine.tensor(run["sign_lr"]) if len(run["sign_lr"]) else None
+        self.keep += [data_d, lr_d]
+        self.problem = _abi.TwinProblem(int(kind), int(n_inst), int(dim), 0, data_d.data_ptr())
+        self.run = _abi.TwinRun(int(run["iter0"]), int(run["n_iter"]), int(run["n_sign"]), float(run["rescale"]),
+                                float(run["out_mul"]), None if lr_d is None else lr_d.data_ptr())
+
+    def unroll(self, theta, state_min, state_max, curve=None, fval=None, delta=None, stream=None):
+        """l2o_twin_unroll on contiguous fp32 device tensors (None: NULL); returns its return code."""
+        return _abi.lib().l2o_twin_unroll(C.byref(self.nets[0]), C.byref(self.nets[1]), C.byref(self.problem),
+                                          C.byref(self.run), _ptr(theta), _ptr(state_min), _ptr(state_max), _ptr(curve),
+                                          _ptr(fval), _ptr(delta), stream)
+
+
 class HipEngine(object):
     """MI355X engine: every method is one call through the C ABI."""
 
@@ -802,22 +840,21 @@ class HipEngine(object):
         c = _fill(_abi.KlstmBwdIO(), io, checked=True)
         _abi.check(self.lib.l2o_klstm_bwd_step(C.byref(net.device_net(self).c), C.byref(c), int(N), self._stream()))
 
-    # -- twin.unroll (l2o_twin_unroll of libl2o_twin.so, csrc_twin/l2o_twin_abi.h) ------------------------
+    # -- twin.unroll (l2o_twin_unroll, include/l2o_twin_abi.h) ---------------------------------------------
     def twin_unroll(self, nets, problem, run, theta, states, record=()):
         """The Twin-L2O evaluation unroll of every instance in one launch.  Host arrays in, host arrays out:
         nets ((hidden, n_in, {torch parameter name: array}) for min and max), problem (kind, dim, data), run (dict: iter0,
         n_iter, n_sign, rescale, out_mul, sign_lr), theta [n_inst, 2, dim], states ([4, H, rows] for min and max), record
         (any of "curve", "f", "delta").  Returns a dict: theta, states and the recorded arrays in the library's layouts
         (curve [n_iter, n_inst, 2 dim], f [n_iter, n_inst], delta [n_iter, n_inst, dim])."""
-        from . import _twin_abi as T
         kind, dim, data = problem
         theta_d, st = self.tensor(theta), [self.tensor(s) for s in states]
         n_inst, n_iter = int(theta_d.shape[0]), int(run["n_iter"])
-        dev = T.Device(self, nets, (kind, n_inst, dim, data), run)
+        dev = TwinDevice(self, nets, (kind, n_inst, dim, data), run)
         shapes = {"curve": (n_iter, n_inst, 2 * int(dim)), "f": (n_iter, n_inst), "delta": (n_iter, n_inst, int(dim))}
         out = {k: (self.empty(*shapes[k]) if k in record else None) for k in shapes}
         with torch.cuda.device(self.device):
-            T.check(dev.unroll(theta_d, st[0], st[1], out["curve"], out["f"], out["delta"], self._stream()))
+            _abi.check(dev.unroll(theta_d, st[0], st[1], out["curve"], out["f"], out["delta"], self._stream()))
         res = {k: (None if t is None else self.to_numpy(t)) for k, t in out.items()}
         res["theta"] = self.to_numpy(theta_d)
         res["states"] = tuple(self.to_numpy(s) for s in st)

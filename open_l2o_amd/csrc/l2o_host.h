@@ -1,6 +1,7 @@
 // l2o_host.h -- host code only: what the translation units of libl2o_hip.so (l2o_core.hip, l2o_unroll.hip, l2o_bwd.hip,
-// l2o_mlp.hip, l2o_nets.hip, l2o_confocal.hip) share on the host side of the C ABI of include/l2o_abi.h -- the error text,
-// the launch helpers, the call-scoped option word, the device queries and the descriptor -> kernel-parameter conversions.
+// l2o_mlp.hip, l2o_nets.hip, l2o_confocal.hip, l2o_twin.hip) share on the host side of the C ABI of include/l2o_abi.h --
+// the error text, the launch helpers, the call-scoped option word, the device queries and the descriptor ->
+// kernel-parameter conversions.
 // Everything here is `inline` (C++17: functions AND variables), so the library holds exactly one g_err, t_optw, ... however
 // many units include this; a helper with callers in one unit only lives in that unit as a `static`.
 #pragma once

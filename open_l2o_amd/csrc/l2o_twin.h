@@ -19,7 +19,7 @@
 // (a lane reads and writes only what it owns).  Gates, cell update and the head are fp32 VALU with accurate expf / tanhf /
 // sinf / cosf; the head's sum over the four q lanes is an xor butterfly, the same bits in all four lanes and all eight waves.
 #pragma once
-#include "../csrc/l2o_common.h"
+#include "l2o_common.h"
 
 namespace l2o {
 

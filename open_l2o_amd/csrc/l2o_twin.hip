@@ -1,12 +1,8 @@
-// l2o_twin.hip -- host side of libl2o_twin.so (l2o_twin_abi.h): descriptor checks, the weight re-pack and the one launch of
-// k_twin_unroll (l2o_twin.h).  Written for gfx950 only.
-#include "../csrc/l2o_host.h"
+// l2o_twin.hip -- one translation unit of libl2o_hip.so: the Twin-L2O entry points of include/l2o_twin_abi.h -- descriptor
+// checks, the weight re-pack and the one launch of k_twin_unroll (l2o_twin.h).  Written for gfx950 only.
+#include "l2o_host.h"
 #include "l2o_twin.h"
-#include "l2o_twin_abi.h"
-
-#ifndef L2O_TWIN_BUILD_ID
-#define L2O_TWIN_BUILD_ID "unknown"
-#endif
+#include "../../include/l2o_twin_abi.h"
 
 static bool twin_net_ok(const l2o_twin_net* n) {
   return n && n->hidden >= 1 && n->hidden <= L2O_TWIN_MAX_HIDDEN && (n->n_in == 1 || n->n_in == 2);
@@ -33,9 +29,6 @@ static int twin_pack(const l2o_twin_net* n, float* out, hipStream_t s) {
 }
 
 extern "C" {
-
-const char* l2o_twin_last_error(void) { return g_err; }
-const char* l2o_twin_build_id(void) { return L2O_TWIN_BUILD_ID; }
 
 int l2o_twin_supported(const l2o_twin_net* mn, const l2o_twin_net* mx, const l2o_twin_problem* p) {
   return twin_ok(mn, mx, p) ? 1 : 0;

@@ -4,7 +4,7 @@
 Two per-coordinate two-layer LSTM optimizers -- one steps the min variable ``u``, one the max variable ``v`` -- alternate
 over an analytic saddle objective; every coordinate of every problem instance shares the two networks.  The reference calls
 two ``nn.LSTMCell`` per iteration per instance from Python; here all iterations of all instances are ONE launch of
-``l2o_twin_unroll`` (``libl2o_twin.so``, ``csrc_twin/``).  Meta-training of the twin networks is not built.
+``l2o_twin_unroll`` (``libl2o_hip.so``, ``csrc/l2o_twin.h``).  Meta-training of the twin networks is not built.
 
 Objectives (``params["loss"]``; ``u = theta_min``, ``v = theta_max``): 1 saddle ``a u^2 - b v^2``, 2 rotated saddle
 ``a u^2 - b v^2 + 2 u v``, 3 seesaw ``-b v sin(a pi u)`` (all with dim 1), 4 matrix game ``u^T A v`` (dim >= 1).

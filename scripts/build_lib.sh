@@ -9,7 +9,7 @@ set -e
 OUT=$(realpath -m "$1"); shift
 cd "$(dirname "$0")/../open_l2o_amd/csrc"
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -mllvm -amdgpu-mfma-vgpr-form -fno-slp-vectorize"
-UNITS="l2o_core l2o_unroll l2o_bwd l2o_mlp l2o_nets l2o_confocal l2o_kernels_ilp"
+UNITS="l2o_core l2o_unroll l2o_bwd l2o_mlp l2o_nets l2o_confocal l2o_twin l2o_kernels_ilp"
 OBJ=$(dirname "$OUT")/obj_$(basename "$OUT" .so)
 rm -rf "$OBJ"
 mkdir -p "$OBJ"

@@ -61,7 +61,6 @@ def child(reps):
     import torch
     import __graft_entry__  # noqa: F401
     from open_l2o_amd import _abi, _engine, twin
-    from open_l2o_amd import _twin_abi as T
 
     if not torch.cuda.is_available():
         raise SystemExit("twin_bench: no GPU")
@@ -91,8 +90,8 @@ def child(reps):
         prob = twin.problem(kind, data, dim)
         mn, mx = twin.Optimizer(H, seed=2), twin.Optimizer(H, seed=3)
         theta0, states0 = twin.draw_start(prob, mn, mx, seed=4)
-        dev = T.Device(eng, tuple((o.hidden_size, o.n_in, o.params) for o in (mn, mx)), (kind, n, dim, prob.data),
-                       dict(iter0=1, n_iter=OPTIM_IT, n_sign=n_sign, rescale=RESCALE, out_mul=1.0, sign_lr=lr))
+        dev = _engine.TwinDevice(eng, tuple((o.hidden_size, o.n_in, o.params) for o in (mn, mx)), (kind, n, dim, prob.data),
+                                 dict(iter0=1, n_iter=OPTIM_IT, n_sign=n_sign, rescale=RESCALE, out_mul=1.0, sign_lr=lr))
         keep = [eng.tensor(theta0)] + [eng.tensor(s) for s in states0]
         bufs = [t.clone() for t in keep]
         curve = eng.empty(OPTIM_IT, n, 2 * dim)

@@ -150,6 +150,7 @@ REFUSED_CALLS = (
     ("l2o_mnist_conv_fg", lambda: (None,) * 7),                                                        # l2o_nets.hip
     ("l2o_nas_fg", lambda: (None,) * 7),                                                               # l2o_nets.hip
     ("l2o_confocal_fg", lambda: (None,) * 7),                                                          # l2o_confocal.hip
+    ("l2o_twin_unroll", lambda: (None,) * 11),                                                         # l2o_twin.hip
 )
 
 

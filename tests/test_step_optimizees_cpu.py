@@ -90,14 +90,14 @@ def test_symbols_are_declared():
 
 
 SYMBOL_TUPLES = ("SYMBOLS", "CONFOCAL_UNROLL_SYMBOLS", "CONFOCAL_MULTI_SYMBOLS", "MLP_HVP_SYMBOLS", "VGG16_SYMBOLS",
-                 "NAS_SYMBOLS", "KLSTM_SYMBOLS")
+                 "NAS_SYMBOLS", "KLSTM_SYMBOLS", "TWIN_SYMBOLS")
 
 
 def test_every_listed_symbol_has_a_prototype():
     listed = [name for t in SYMBOL_TUPLES for name in getattr(_abi, t)]
     table = {name: proto for protos in _abi.PROTOTYPES.values() for name, proto in protos.items()}
-    assert len(listed) == len(set(listed)) == 84 and set(listed) == set(table)
-    assert sum(len(protos) for protos in _abi.PROTOTYPES.values()) == 84         # (no symbol under two headers)
+    assert len(listed) == len(set(listed)) == 87 and set(listed) == set(table)
+    assert sum(len(protos) for protos in _abi.PROTOTYPES.values()) == 87         # (no symbol under two headers)
     for name in listed:
         restype, argtypes = table[name]
         assert restype in (C.c_int, C.c_int32, C.c_int64, C.c_size_t, C.c_char_p) and type(argtypes) is list, name

@@ -1,4 +1,4 @@
-"""l2o_twin_unroll (csrc_twin/l2o_twin.h) on the MI355X, through the C ABI and through twin.unroll, against the float64 torch
+"""l2o_twin_unroll (csrc/l2o_twin.h) on the MI355X, through the C ABI and through twin.unroll, against the float64 torch
 restatement of twin_reference.py.
 
 Criterion.  Every output array (curve, f, delta, theta, the two final states) is compared relative to its largest float64
@@ -23,7 +23,6 @@ import torch
 
 import twin_reference as TR
 from open_l2o_amd import _abi, _engine, twin
-from open_l2o_amd import _twin_abi as T
 from test_twin_cpu import GOLDEN, load_driver, make_data
 
 pytestmark = pytest.mark.gpu
@@ -183,8 +182,9 @@ class Launcher(object):
     def device(self, iter0, n_iter):
         kind, n_inst, dim, H, n_in, _, _, rescale, out_mul, _ = self.s
         nets = tuple((o.hidden_size, o.n_in, o.params) for o in (self.mn, self.mx))
-        return T.Device(self.eng, nets, (kind, n_inst, dim, self.prob.data),
-                        dict(iter0=iter0, n_iter=n_iter, n_sign=self.n_sign, rescale=rescale, out_mul=out_mul, sign_lr=self.lr))
+        return _engine.TwinDevice(self.eng, nets, (kind, n_inst, dim, self.prob.data),
+                                  dict(iter0=iter0, n_iter=n_iter, n_sign=self.n_sign, rescale=rescale, out_mul=out_mul,
+                                       sign_lr=self.lr))
 
     def start(self):
         return [self.eng.tensor(self.theta0)] + [self.eng.tensor(st) for st in self.states]
@@ -194,7 +194,7 @@ class Launcher(object):
         outs = [torch.full(shape, float("nan"), dtype=torch.float32, device=self.eng.device)
                 for shape in ((n_iter, n, 2 * dim), (n_iter, n), (n_iter, n, dim))] if record else [None] * 3
         rc = self.device(iter0, n_iter).unroll(*bufs, *outs, self.eng._stream())
-        assert rc == _abi.L2O_OK, T.lib().l2o_twin_last_error()
+        assert rc == _abi.L2O_OK, _abi.lib().l2o_last_error()
         torch.cuda.synchronize()
         return [None if o is None else o.cpu().numpy() for o in outs]
 
@@ -245,7 +245,7 @@ def test_unsupported_descriptors_touch_nothing(eng, what):
         dev.problem.kind = 5
     elif what == "kind 1 with dim 2":
         dev.problem.dim, dev.problem.n_inst, n, dim = 2, 3, 3, 2      # the same 6 rows
-    assert T.lib().l2o_twin_supported(dev.nets[0], dev.nets[1], dev.problem) == 0
+    assert _abi.lib().l2o_twin_supported(dev.nets[0], dev.nets[1], dev.problem) == 0
     bufs = L.start()
     outs = [torch.full(shape, 7.0, dtype=torch.float32, device=eng.device) for shape in ((4, n, 2 * dim), (4, n), (4, n, dim))]
     before = [t.clone() for t in bufs + outs]
@@ -254,7 +254,7 @@ def test_unsupported_descriptors_touch_nothing(eng, what):
     assert rc == _abi.L2O_ERR_UNSUPPORTED
     assert all(torch.equal(a, b) for a, b in zip(before, bufs + outs))
     if what == "hidden 97":
-        assert T.lib().l2o_twin_state_floats(dev.nets[0], 5) == 0 and T.lib().l2o_twin_state_floats(dev.nets[1], 5) == 4 * 50 * 5
+        assert _abi.lib().l2o_twin_state_floats(dev.nets[0], 5) == 0 and _abi.lib().l2o_twin_state_floats(dev.nets[1], 5) == 4 * 50 * 5
 
 
 # 8. the driver
