@@ -393,6 +393,48 @@ __device__ __forceinline__ void issue(const W& w, const BOp<PK>& b, f32x4 (&acc)
   });
 }
 
+// split5<true, true> and the twenty MFMAs of chunk CH in ONE hand-written program order (k_unroll_pair, chunk L2A: the one
+// chunk on the step's dependent chain).  An MFMA holds the lone wave's vector issue for 8 of its 16 cycles of matrix pipe, so
+// two plain VALU instructions behind it are free and a second MFMA behind it waits 8.  Products 0, 1 need the first three
+// conversions, product 2 the first residuals, product 3 the split's last word: the fifteen MFMAs of products 0..2 each take two
+// instructions of the split behind them, the five of product 3 follow in one run.  Every MFMA and every pair is a scheduling
+// region of its own -- in one region the scheduler puts the pair on either side of its MFMA and MFMAs meet at the borders;
+// left alone it issues eleven under the split, five of them back to back, and nine behind it.  The inputs are copied in front
+// of the first fence: read through the reference behind it, three floats of the state came back as a per-thread LDS slot.
+// The same operations on the same operands as split5 + issue, every accumulator's products in order: bit-identical
+// (profiles/pair_l2a_under_gates.txt).
+template <int CH, class W>
+__device__ __forceinline__ void split5_issue(const float (&v)[kNT], unsigned one, BOp<true>& o, const W& w, f32x4 (&acc)[kNT]) {
+  static_assert(!W::kLdsFrags, "split5_issue: fragments in registers");
+#define L2O_FENCE __builtin_amdgcn_sched_barrier(0)
+#define L2O_MF(t, p) acc[t] = mfma_bf(w.a[CH][t][p], o.m[p], acc[t]); L2O_FENCE
+  float a0 = v[0], a1 = v[1], b0 = v[2], b1 = v[3];
+  const float v4 = v[4];
+  const unsigned pa0 = cvt_pk(mk2(a0, a1)), pb0 = cvt_pk(mk2(b0, b1)), ca = cvt_pk(mk2(v4, v4));
+  o.m[0][0] = pa0; o.m[0][1] = pb0; o.m[0][2] = ca; o.m[0][3] = one;
+  o.m[1][0] = pa0; o.m[1][1] = pb0; o.m[1][2] = pa0; o.m[1][3] = pb0;
+  L2O_FENCE;
+  L2O_MF(0, 0); a0 -= __uint_as_float(pa0 << 16); L2O_FENCE;
+  L2O_MF(1, 0); a1 -= __uint_as_float(pa0 & 0xffff0000u); L2O_FENCE;
+  L2O_MF(2, 0); b0 -= __uint_as_float(pb0 << 16); L2O_FENCE;
+  L2O_MF(3, 0); b1 -= __uint_as_float(pb0 & 0xffff0000u); L2O_FENCE;
+  L2O_MF(4, 0); const float r1 = v4 - __uint_as_float(ca << 16); L2O_FENCE;
+  L2O_MF(0, 1); const unsigned pa1 = cvt_pk(mk2(a0, a1)), pb1 = cvt_pk(mk2(b0, b1)); L2O_FENCE;
+  L2O_MF(1, 1); const unsigned cb = cvt_pk(mk2(v4, r1));
+  o.m[2][0] = pa1; o.m[2][1] = pb1; o.m[2][2] = cb; o.m[2][3] = pa1; L2O_FENCE;
+  L2O_MF(2, 1); a0 -= __uint_as_float(pa1 << 16); L2O_FENCE;
+  L2O_MF(3, 1); a1 -= __uint_as_float(pa1 & 0xffff0000u); L2O_FENCE;
+  L2O_MF(4, 1); b0 -= __uint_as_float(pb1 << 16); L2O_FENCE;
+  L2O_MF(0, 2); b1 -= __uint_as_float(pb1 & 0xffff0000u); L2O_FENCE;
+  L2O_MF(1, 2); const float r2 = r1 - __uint_as_float(cb & 0xffff0000u); L2O_FENCE;
+  L2O_MF(2, 2); o.m[3][0] = pb1; o.m[3][1] = cvt_pk(mk2(a0, a1)); L2O_FENCE;
+  L2O_MF(3, 2); o.m[3][2] = cvt_pk(mk2(b0, b1)); L2O_FENCE;
+  L2O_MF(4, 2); o.m[3][3] = cvt_pk(mk2(r1, r2)); L2O_FENCE;
+  static_for<0, kNT>([&](auto tc) { acc[decltype(tc)::value] = mfma_bf(w.a[CH][decltype(tc)::value][3], o.m[3], acc[decltype(tc)::value]); });
+#undef L2O_MF
+#undef L2O_FENCE
+}
+
 // acc = [-log2e*i, 2log2e*j, -log2e*(f+1), -log2e*o] of the unit pair (T0, T0+1)
 // (the part of gates_pair behind the four first-stage exponentials of each unit, which the caller supplies)
 template <int T0>
@@ -525,13 +567,15 @@ struct NoShadow { __device__ __forceinline__ void operator()() const {} };
 // L2B_LATE (k_unroll_pair, kPairL2bLate): the LAST L2B_LATE MFMAs of chunk L2B are issued here, beside the layer-1 gate
 // exponentials, instead of by the caller in front of finish() -- b2 must still hold the split of h2(t-1)
 template <int PRE, bool NEXT, bool PK, class Shadow = NoShadow, bool REARM = true, class W = NetWB<PRE, PK>, bool SR = false,
-          int L2B_LATE = 0>
+          int L2B_LATE = 0, bool L2A_UNDER_SPLIT = false>
 __device__ __forceinline__ float finish(const W& w, TileState& s, BOp<PK>& b1, BOp<PK>& b2,
                                         f32x4 (&acc1)[kNT], f32x4 (&acc2)[kNT], float in0, float in1, unsigned one,
                                         int q, PhaseClock& pc, Shadow&& shadow = Shadow()) {
   constexpr int kN = chunk_mfmas(PK);
   static_assert(!SR || (PK && !NEXT && !W::kLdsFrags), "finish: the scalar-residual split is k_unroll_pair's");
   static_assert(L2B_LATE == 0 || (PK && !NEXT && !W::kLdsFrags && L2B_LATE <= kN), "finish: the late part of chunk L2B is k_unroll_pair's");
+  static_assert(!L2A_UNDER_SPLIT || (PK && SR && !NEXT && !W::kLdsFrags && std::is_same<typename std::decay<Shadow>::type, NoShadow>::value),
+                "finish: chunk L2A hand-ordered under the split of h1 is k_unroll_pair's");
   if constexpr (PRE == L2O_PRE_FC_ELU) {   // (constexpr: chunk L1X does not exist for the DM nets)
     float fc[kNT];
 #pragma unroll
@@ -584,8 +628,16 @@ __device__ __forceinline__ float finish(const W& w, TileState& s, BOp<PK>& b1, B
   constexpr bool kPinBias = !W::kLdsFrags || L2O_FINISH_PINNED_LDSFRAGS;
   if (REARM || NEXT) preload_bias<0, W, kPinBias>(w, acc1);   // acc1 is dead: the next step's layer-1 accumulator init
   pc.mark(6);
-  split5<PK, SR>(s.h1, one, b1);
-  issue<PRE, kChL2A, 0, kN, false>(w, b1, acc2);
+  if constexpr (L2A_UNDER_SPLIT) {
+    // The split of h1 and chunk L2A as one hand-ordered stream (split5_issue): fifteen of the twenty MFMAs stand in the gaps of
+    // the split, five wait for its last word.  Left to the scheduler, eleven went out under the split -- three and two of them
+    // back to back -- and nine in one run behind it, where the wave waits 8 of every 16 cycles (profiles/pair_l2a_under_gates.txt)
+    __builtin_amdgcn_sched_barrier(0);
+    split5_issue<kChL2A>(s.h1, one, b1, w, acc2);
+  } else {
+    split5<PK, SR>(s.h1, one, b1);
+    issue<PRE, kChL2A, 0, kN, false>(w, b1, acc2);
+  }
   if constexpr (!std::is_same<typename std::decay<Shadow>::type, NoShadow>::value) {
     // the caller's work between the MFMAs: in program order the wave would issue the kN MFMAs back to back
     // (16 cycles each, 4 needed) and only then the shadow
@@ -898,10 +950,10 @@ struct LstmCoreRegs {
   // REARM = false: the caller re-arms the accumulators itself -- arm() from the registers, or preload_unpinned() in front
   // of its barrier -- finish<.., true> issues the reads right behind the gate blocks and the pinning asm WAITS for them
   // there, i.e. in front of the split of h1 and in front of the output Linear / the x update (round 4, k_unroll_pair)
-  template <bool NEXT, class Shadow = bx::NoShadow, bool REARM = true, int L2B_LATE = 0>
+  template <bool NEXT, class Shadow = bx::NoShadow, bool REARM = true, int L2B_LATE = 0, bool L2A_UNDER_SPLIT = false>
   __device__ __forceinline__ float finish(TileState& s, f32x4 (&acc1)[kNT], f32x4 (&acc2)[kNT], float in0, float in1,
                                           int q, PhaseClock& pc, Shadow&& shadow = Shadow()) {
-    return bx::finish<PRE, NEXT, PK, Shadow, REARM, WT, SR, L2B_LATE>(w, s, b1, b2, acc1, acc2, in0, in1, one, q, pc, static_cast<Shadow&&>(shadow));
+    return bx::finish<PRE, NEXT, PK, Shadow, REARM, WT, SR, L2B_LATE, L2A_UNDER_SPLIT>(w, s, b1, b2, acc1, acc2, in0, in1, one, q, pc, static_cast<Shadow&&>(shadow));
   }
   // after finish<false>: b1 already holds split h1(t) (finish builds it for chunk L2A); split h2(t) for chunk L2B
   __device__ __forceinline__ void refresh(const TileState& s) { bx::split5<PK, SR>(s.h2, one, b2); }
@@ -951,6 +1003,11 @@ template <int PRE, int KIND, int CH, bool HIST, bool EXACT, bool FAST>
 constexpr int kPairL2bLate =
     (FAST && !HIST && !EXACT && bx::packed_default(PRE) && !(PRE == L2O_PRE_LOGSIGN && CH == 8)) ? 15 : 0;
 constexpr int kPairL2bB2 = 7;
+// Which of them also issue chunk L2A (h1(t) -> layer 2, the one chunk on the step's dependent chain) hand-ordered under the
+// split of h1 (bx::split5_issue): the same twenty kernels -- the form needs the scalar-residual split, and the registers are
+// the parent's (scripts/so_regs.py).  Everything else keeps split5 + issue, text and ISA.
+template <int PRE, int KIND, int CH, bool HIST, bool EXACT, bool FAST>
+constexpr bool kPairL2aUnderSplit = kPairL2bLate<PRE, KIND, CH, HIST, EXACT, FAST> > 0 && L2O_PAIR_SPLIT_SCALAR != 0;
 constexpr int kPairPollAtLate = 10;
 // the 6-product form with chunk LDSCH in LDS (bx::NetWBH); stage_chunk: every thread copies its share, a barrier follows
 template <int PRE, int LDSCH>

@@ -323,6 +323,7 @@ __device__ __forceinline__ void unroll_pair_body_gather(const UnrollPairArgs& pa
 
   constexpr bool kBiasRegs = kPairBiasRegs<PRE, KIND, CH, HIST, EXACT, false>;
   constexpr int kL2bLate = kPairL2bLate<PRE, KIND, CH, HIST, EXACT, false>;
+  constexpr bool kL2aUnderSplit = kPairL2aUnderSplit<PRE, KIND, CH, HIST, EXACT, false>;
 #define L2O_PAIR_FX_PTR 0
 #include "l2o_unroll_pair_loop.h"
 #undef L2O_PAIR_FX_PTR
@@ -578,6 +579,7 @@ __device__ __forceinline__ void unroll_pair_body(const UnrollPairArgs& pa) {
 
   constexpr bool kBiasRegs = kPairBiasRegs<PRE, KIND, CH, HIST, EXACT, true>;
   constexpr int kL2bLate = kPairL2bLate<PRE, KIND, CH, HIST, EXACT, true>;
+  constexpr bool kL2aUnderSplit = kPairL2aUnderSplit<PRE, KIND, CH, HIST, EXACT, true>;
 #define L2O_PAIR_FX_PTR 1
 #include "l2o_unroll_pair_loop.h"
 #undef L2O_PAIR_FX_PTR

@@ -40,7 +40,7 @@
       preprocess_grad<PRE>(gv, a.np.k_inv_ln2, a.np.exp_k, in0, in1);
     }
     float d;                                                // (re-armed below)
-    if constexpr (kL2bLate > 0) d = core.template finish<false, bx::NoShadow, false, kL2bLate - kL2bB2>(s, acc1, acc2, in0, in1, q, pc);
+    if constexpr (kL2bLate > 0) d = core.template finish<false, bx::NoShadow, false, kL2bLate - kL2bB2, kL2aUnderSplit>(s, acc1, acc2, in0, in1, q, pc);
     else d = core.template finish<false, bx::NoShadow, false>(s, acc1, acc2, in0, in1, q, pc);
     // a real (uniform) branch: as a select hipcc computes the exp + rcp of tanh on every step of the nets without it.
     // Marked unlikely (a run-time field: the RNNProp nets do take it): the block moves out of line, and the nets without a

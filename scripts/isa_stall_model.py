@@ -17,7 +17,8 @@ two_wave_issue.hip): issue of a plain VALU instruction from a lone wave 5.26, tr
 16x16x32 MFMA holds the SIMD's vector issue for 8 of the 16 cycles it occupies the matrix pipe (row "vector-instruction ISSUE
 cost"), so whatever follows it -- a transcendental included -- issues 8 after it and runs beside the rest of its pipe slot, and
 only the next MFMA waits for the slot to end; it delivers its accumulator to a VALU reader
-~40 after issue (8 passes x 4 + write-back), to a dependent MFMA on the same accumulator when the pipe is free; v_exp / v_rcp /
+~40 after issue (8 passes x 4 + write-back), to a dependent MFMA that takes it as C when the pipe is free (row "v_mfma_f32_16x16x32_bf16,
+back-to-back issue": 16 cycles per MFMA on 1, 4 and 16 accumulators alike -- a chain on one accumulator is no penalty); v_exp / v_rcp /
 v_log / v_sqrt deliver 16 after issue; DPP / permlane consumers see VALU results 8 after issue; ds_read 64 (b32) .. 128 (b128)
 after issue; SALU 4.  These are nominal -- the point is the ATTRIBUTION, which chains own the stall cycles, not the third digit."""
 import re
@@ -142,8 +143,11 @@ def main():
             dsts = ["vcc"]
         t = earliest
         why = None
+        acc_in = set(regs(ops[3])) if cls == "mfma" and len(ops) > 3 else ()
         for r in srcs:
             rt = ready.get(r, 0.0)
+            if r in acc_in and producer.get(r) == "mfma":
+                rt = rt - LAT["mfma"] + MFMA_PIPE
             if producer.get(r) in ("valu", "pk") and cls == "dpp":
                 rt = rt - LAT["valu"] + LAT["dpp"]
             if rt > t:

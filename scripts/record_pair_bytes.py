@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 SUITES = {"split": "test_pair_split_forms", "step": "test_pair_step_paths", "combine": "test_pair_prologue_staging",
-          "bias": "test_pair_bias_registers", "l2b": "test_pair_l2b_placement"}
+          "bias": "test_pair_bias_registers", "l2b": "test_pair_l2b_placement", "l2a": "test_pair_l2a_placement"}
 
 
 def main():
