@@ -277,6 +277,20 @@ class TwinRun(C.Structure):
                 ("out_mul", C.c_float), ("sign_lr", C.c_void_p)]
 
 
+TWIN_TRAIN_MAX_ITER = 64                                                        # L2O_TWIN_TRAIN_MAX_ITER (csrc/l2o_twin_train_abi.h)
+
+
+class TwinSegment(C.Structure):
+    """struct l2o_twin_segment"""
+    _fields_ = [("run", TwinRun), ("loss_scale", C.c_float), ("inst_weight", C.c_void_p)]
+
+
+class TwinGrad(C.Structure):
+    """struct l2o_twin_grad"""
+    _fields_ = [(n, C.c_void_p) for n in ("w_ih1", "w_hh1", "b_ih1", "b_hh1", "w_ih2", "w_hh2", "b_ih2", "b_hh2",
+                                          "w_out", "b_out")]
+
+
 class NetWeights(C.Structure):
     """struct l2o_net_weights"""
     _fields_ = [(n, C.c_void_p) for n in ("w_gates1", "b_gates1", "w_gates2", "b_gates2", "w_lin", "b_lin",
@@ -430,6 +444,26 @@ SYMBOLS, CONFOCAL_UNROLL_SYMBOLS, CONFOCAL_MULTI_SYMBOLS, MLP_HVP_SYMBOLS, VGG16
                                        "l2o_vgg16_abi.h", "l2o_nas_abi.h", "l2o_klstm_abi.h", "l2o_twin_abi.h"))
 
 
+def _twin_train_prototypes():
+    P, vp, I, Z = C.POINTER, C.c_void_p, C.c_int, C.c_size_t
+    head = [P(TwinNet), P(TwinNet), P(TwinProblem)]
+    return {
+        "l2o_twin_train_abi.h": {            # twin.meta_gradient: one segment of the Twin-L2O meta-training
+            "l2o_twin_train_floats": (Z, head + [C.c_int32]),
+            "l2o_twin_train_forward": (I, head + [P(TwinSegment)] + [vp] * 8),
+            "l2o_twin_train_backward": (I, head + [P(TwinSegment), vp, P(TwinGrad), P(TwinGrad), vp]),
+        },
+    }
+
+
+# A second table, header of csrc/ -> {symbol: (restype, argtypes)}: the meta-training entry points of the Twin-L2O family.
+# lib() applies it after declare() and refuses a library that lacks one of its symbols in the same way.  (It stands outside
+# PROTOTYPES, and its header outside include/, because tests pin that table's size and its keys to include/'s file list; a
+# change that may touch those tests folds both in.)
+TWIN_TRAIN_PROTOTYPES = _twin_train_prototypes()
+TWIN_TRAIN_SYMBOLS = tuple(TWIN_TRAIN_PROTOTYPES["l2o_twin_train_abi.h"])
+
+
 class L2OError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libl2o_hip error %d: %s" % (code, msg))
@@ -488,18 +522,22 @@ def last_unroll_variant():
             "NV": (w >> 12) & 3}
 
 
-def declare(library):
-    """Give every symbol of PROTOTYPES its restype / argtypes on the loaded `library` and return it.  The library is built
-    from this tree, so one that lacks a listed symbol is a stale file: it is refused whole, at load."""
-    missing = [name for protos in PROTOTYPES.values() for name in protos if not hasattr(library, name)]
+def _declare(library, table):
+    missing = [name for protos in table.values() for name in protos if not hasattr(library, name)]
     if missing:
         raise RuntimeError("open_l2o_amd: %s has no %s: the library is stale (built from older sources) -- rebuild it with "
                            "`make -C open_l2o_amd/csrc`" % (LIB_PATH, ", ".join(missing)))
-    for protos in PROTOTYPES.values():
+    for protos in table.values():
         for name, (restype, argtypes) in protos.items():
             fn = getattr(library, name)
             fn.restype, fn.argtypes = restype, argtypes
     return library
+
+
+def declare(library):
+    """Give every symbol of PROTOTYPES its restype / argtypes on the loaded `library` and return it.  The library is built
+    from this tree, so one that lacks a listed symbol is a stale file: it is refused whole, at load."""
+    return _declare(library, PROTOTYPES)
 
 
 def lib():
@@ -511,7 +549,7 @@ def lib():
         raise RuntimeError(
             "open_l2o_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C open_l2o_amd/csrc`.  There is no CPU fallback." % LIB_PATH)
-    L = declare(C.CDLL(LIB_PATH))
+    L = _declare(declare(C.CDLL(LIB_PATH)), TWIN_TRAIN_PROTOTYPES)
     if L.l2o_abi_version() != L2O_ABI_VERSION:
         raise RuntimeError("libl2o_hip.so ABI version %d != binding version %d"
                            % (L.l2o_abi_version(), L2O_ABI_VERSION))

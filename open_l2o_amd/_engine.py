@@ -277,6 +277,32 @@ class TwinDevice(object):
                                           C.byref(self.run), _ptr(theta), _ptr(state_min), _ptr(state_max), _ptr(curve),
                                           _ptr(fval), _ptr(delta), stream)
 
+    # -- one segment of the meta-training (csrc/l2o_twin_train_abi.h) ------------------------------------------
+    def segment(self, loss_scale, inst_weight=None):
+        """struct l2o_twin_segment of this run; inst_weight: None or a device tensor [n_inst]."""
+        self.keep.append(inst_weight)
+        return _abi.TwinSegment(self.run, float(loss_scale), _ptr(inst_weight))
+
+    def work_floats(self):
+        return int(_abi.lib().l2o_twin_train_floats(C.byref(self.nets[0]), C.byref(self.nets[1]), C.byref(self.problem),
+                                                    self.run.n_iter))
+
+    def train_forward(self, seg, theta, state_min, state_max, curve, fval, delta, work, stream=None):
+        return _abi.lib().l2o_twin_train_forward(C.byref(self.nets[0]), C.byref(self.nets[1]), C.byref(self.problem),
+                                                 C.byref(seg), _ptr(theta), _ptr(state_min), _ptr(state_max), _ptr(curve),
+                                                 _ptr(fval), _ptr(delta), _ptr(work), stream)
+
+    def train_backward(self, seg, work, grads, stream=None):
+        """grads: for min and max a dict {torch parameter name: device tensor}; every entry is written."""
+        cg = []
+        for g in grads:
+            c = _abi.TwinGrad()
+            for field, name in _TWIN_NET_FIELDS:
+                setattr(c, field, g[name].data_ptr())
+            cg.append(c)
+        return _abi.lib().l2o_twin_train_backward(C.byref(self.nets[0]), C.byref(self.nets[1]), C.byref(self.problem),
+                                                  C.byref(seg), _ptr(work), C.byref(cg[0]), C.byref(cg[1]), stream)
+
 
 class HipEngine(object):
     """MI355X engine: every method is one call through the C ABI."""
@@ -859,6 +885,41 @@ class HipEngine(object):
         res["theta"] = self.to_numpy(theta_d)
         res["states"] = tuple(self.to_numpy(s) for s in st)
         return res
+
+    def twin_segment_forward(self, nets, problem, run, theta, states, loss_scale):
+        """The recording forward of one meta-training segment (l2o_twin_train_forward).  Arguments as twin_unroll; returns
+        (its dict with curve, f and delta, a handle for twin_segment_backward).  Between the two the host may compute the
+        instance weights from the curve."""
+        kind, dim, data = problem
+        theta_d, st = self.tensor(theta), [self.tensor(s) for s in states]
+        n_inst, n_iter = int(theta_d.shape[0]), int(run["n_iter"])
+        dev = TwinDevice(self, nets, (kind, n_inst, dim, data), run)
+        out = {"curve": self.empty(n_iter, n_inst, 2 * int(dim)), "f": self.empty(n_iter, n_inst),
+               "delta": self.empty(n_iter, n_inst, int(dim))}
+        seg = dev.segment(loss_scale)
+        with torch.cuda.device(self.device):
+            work = self.empty(dev.work_floats())
+            _abi.check(dev.train_forward(seg, theta_d, st[0], st[1], out["curve"], out["f"], out["delta"], work, self._stream()))
+        res = {k: self.to_numpy(t) for k, t in out.items()}
+        res["theta"] = self.to_numpy(theta_d)
+        res["states"] = tuple(self.to_numpy(s) for s in st)
+        return res, (dev, work, nets, float(loss_scale))
+
+    def twin_segment_backward(self, handle, inst_weight=None):
+        """(grads_min, grads_max), dicts {torch parameter name: array}, of the segment behind `handle`
+        (l2o_twin_train_backward); inst_weight: None or [n_inst]."""
+        dev, work, nets, loss_scale = handle
+        w_d = None if inst_weight is None else self.tensor(np.ascontiguousarray(inst_weight, dtype=np.float32))
+        seg = dev.segment(loss_scale, w_d)
+        grads = [{name: self.empty(*np.shape(params[name])) for _, name in _TWIN_NET_FIELDS} for _, _, params in nets]
+        with torch.cuda.device(self.device):
+            _abi.check(dev.train_backward(seg, work, grads, self._stream()))
+        return tuple({k: self.to_numpy(t) for k, t in g.items()} for g in grads)
+
+    def twin_segment_grad(self, nets, problem, run, theta, states, loss_scale, inst_weight=None):
+        """Forward and backward of one segment: (the forward's dict, (grads_min, grads_max))."""
+        res, handle = self.twin_segment_forward(nets, problem, run, theta, states, loss_scale)
+        return res, self.twin_segment_backward(handle, inst_weight)
 
     def lstm_step(self, spec: NetSpec, wpack, g, m, v, pow1, pow2, st, x, B, D):
         if isinstance(wpack, HipEngine.GenNet):

@@ -165,6 +165,9 @@ __device__ __forceinline__ void tw_layer(const float* __restrict__ sp, float bsp
   }
 }
 
+// (l2o_twin_train.h holds a sibling copy of this kernel and of tw_layer, k_twin_record / tw_layer_rec, with the stores of the
+// meta-training history added: a template flag here changed this kernel's schedule.  Any change to the arithmetic below must
+// be repeated there; tests/test_twin_train.py holds the two to the same bits.)
 __global__ __launch_bounds__(kTwThreads) void k_twin_unroll(TwParams p) {
   extern __shared__ float tw_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;

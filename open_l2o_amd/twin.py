@@ -1,10 +1,18 @@
-"""Twin-L2O: the reference's model-free minimax optimizer (``Model_Free_L2O/L2O-Minimax/Twin-L2O.py``), its evaluation
-(``mode: "test"``) unroll.
+"""Twin-L2O: the reference's model-free minimax optimizer (``Model_Free_L2O/L2O-Minimax/Twin-L2O.py``): its evaluation
+(``mode: "test"``) unroll and its meta-training (``mode: "train"``).
 
 Two per-coordinate two-layer LSTM optimizers -- one steps the min variable ``u``, one the max variable ``v`` -- alternate
 over an analytic saddle objective; every coordinate of every problem instance shares the two networks.  The reference calls
 two ``nn.LSTMCell`` per iteration per instance from Python; here all iterations of all instances are ONE launch of
-``l2o_twin_unroll`` (``libl2o_hip.so``, ``csrc/l2o_twin.h``).  Meta-training of the twin networks is not built.
+``l2o_twin_unroll`` (``libl2o_hip.so``, ``csrc/l2o_twin.h``).
+
+Meta-training (``meta_gradient``, ``train_batch``, ``fit``: the reference's ``do_fit(should_train=True)`` and
+``fit_optimizer``).  A training batch is cut into segments of ``2 unroll_unit`` iterations; a segment's forward, its BPTT and
+the weight-gradient contraction are HIP (``csrc/l2o_twin_train.h``); ``torch.optim.Adam`` -- the reference's own optimizer --
+steps both networks at every segment's end.  Inside a segment the LSTM inputs are detached, the stepped variable is detached
+right after its loss is taken and the sign rule has derivative zero, so each network's gradient is a BPTT through its own
+state chain alone; iteration k contributes ``(loss_k + loss_{k-1}) / batch_size`` with ``loss_k = +f`` after a min step and
+``-f`` after a max step (``loss_{k-1} = 0`` at a segment's first iteration).
 
 Objectives (``params["loss"]``; ``u = theta_min``, ``v = theta_max``): 1 saddle ``a u^2 - b v^2``, 2 rotated saddle
 ``a u^2 - b v^2 + 2 u v``, 3 seesaw ``-b v sin(a pi u)`` (all with dim 1), 4 matrix game ``u^T A v`` (dim >= 1).
@@ -269,3 +277,262 @@ def distances(problem, result):
                 best = np.minimum(best, np.abs(du - k / a))
         du = best
     return du, dv
+
+
+# ---------------------------------------------------------------------------------------------------------
+# meta-training
+# ---------------------------------------------------------------------------------------------------------
+def _segment_forward(problem, opt_min, opt_max, optim_it, iter0, n_iter, theta0, states, rescale, out_mul, batch_size):
+    """The recording forward of one segment: (Result of the forward, the engine's handle for _segment_backward)."""
+    optim_it, iter0, n_iter = int(optim_it), int(iter0), int(n_iter)
+    n_sign, sign_lr = schedule(optim_it)
+    if iter0 < 1 or iter0 % 2 == 0 or n_iter < 2 or n_iter % 2:
+        raise ValueError("twin.meta_gradient: a segment starts at an odd iteration and has an even number of them "
+                         "(iter0 = %d, n_iter = %d)" % (iter0, n_iter))
+    n_inst, dim = problem.n_inst, problem.dim
+    theta0 = np.ascontiguousarray(theta0, dtype=np.float32)
+    if theta0.shape != (n_inst, 2, dim):
+        raise ValueError("twin.meta_gradient: theta0 is %r, expected %r" % (theta0.shape, (n_inst, 2, dim)))
+    states = tuple(np.ascontiguousarray(s, dtype=np.float32) for s in states)
+    for s, o in zip(states, (opt_min, opt_max)):
+        if s.shape != (4, o.hidden_size, n_inst * dim):
+            raise ValueError("twin.meta_gradient: a state is %r, expected %r" % (s.shape, (4, o.hidden_size, n_inst * dim)))
+    batch_size = n_inst if batch_size is None else int(batch_size)
+    out, handle = _engine.default_engine().twin_segment_forward(
+        tuple((o.hidden_size, o.n_in, o.params) for o in (opt_min, opt_max)), (problem.kind, dim, problem.data),
+        dict(iter0=iter0, n_iter=n_iter, n_sign=n_sign, rescale=float(rescale), out_mul=float(out_mul), sign_lr=sign_lr),
+        theta0, states, 1.0 / batch_size)
+    curve = np.concatenate([theta0.reshape(n_inst, 1, 2 * dim),
+                            np.asarray(out["curve"]).reshape(n_iter, n_inst, 2 * dim).transpose(1, 0, 2)], axis=1)
+    res = Result(theta=np.asarray(out["theta"]).reshape(n_inst, 2, dim), states=tuple(np.asarray(s) for s in out["states"]),
+                 curve=curve, f=np.ascontiguousarray(np.asarray(out["f"]).reshape(n_iter, n_inst).T),
+                 delta=np.ascontiguousarray(np.asarray(out["delta"]).reshape(n_iter, n_inst, dim).transpose(1, 0, 2)),
+                 iter0=iter0, n_iter=n_iter, optim_it=optim_it, dim=dim, batch_size=batch_size)
+    return res, handle
+
+
+def _segment_backward(res, handle, inst_weight):
+    """Fills res.grads and res.loss: the segment's total_loss, sum over k and instances of w_k s_k f m / batch_size in
+    float64 from the recorded f (w_k = 2, 1 at the last iteration; s_k = +1 for a min step, -1 for a max step)."""
+    if inst_weight is not None:
+        inst_weight = np.ascontiguousarray(inst_weight, dtype=np.float32)
+        if inst_weight.shape != (res.f.shape[0],):
+            raise ValueError("twin.meta_gradient: inst_weight is %r, expected %r" % (inst_weight.shape, (res.f.shape[0],)))
+    res.grads = _engine.default_engine().twin_segment_backward(handle, inst_weight)
+    k = res.iter0 + np.arange(res.n_iter)
+    ws = np.where(k % 2 == 1, 1.0, -1.0) * np.where(np.arange(res.n_iter) == res.n_iter - 1, 1.0, 2.0)
+    m = np.ones(res.f.shape[0]) if inst_weight is None else inst_weight.astype(np.float64)
+    res.loss = float((res.f.astype(np.float64) * ws[None, :] * m[:, None]).sum() / res.batch_size)
+    return res
+
+
+def meta_gradient(problem, opt_min, opt_max, optim_it, iter0, n_iter, theta0, states, rescale=1e-4, out_mul=1.0,
+                  batch_size=None, inst_weight=None):
+    """One segment of the meta-training: iterations iter0 (odd) ... iter0 + n_iter - 1 (n_iter even) of a run of optim_it
+    iterations, and the gradient of the segment's loss with respect to both networks.  Returns the Result of ``unroll``
+    (curve, f and delta recorded, bit for bit those of ``unroll``) with ``grads = (dict, dict)`` under PARAM_NAMES for the
+    min and the max network and ``loss``, the segment's total_loss.  batch_size (default n_inst) is the reference's divisor;
+    inst_weight [n_inst] (default all 1) the curriculum's weights."""
+    res, handle = _segment_forward(problem, opt_min, opt_max, optim_it, iter0, n_iter, theta0, states, rescale, out_mul,
+                                   batch_size)
+    return _segment_backward(res, handle, inst_weight)
+
+
+def sche_ratio(epoch_index):
+    """The reference's curriculum schedule (Twin-L2O.py lines 84-88)."""
+    if 0 <= epoch_index <= 80:
+        return 0.2 + epoch_index / 100
+    return 1
+
+
+def get_index(curve_info, iteration_index, unroll_unit, batch_data, ratio):
+    """The reference's ``metrics.get_index`` (utils/metrics.py lines 18-38): the instances that enter a segment's loss, the
+    ``int(ratio * batch)`` with the smallest sum over the curve so far of ``(-b sin(a pi u))^2``.  As there: the curve so far
+    is columns ``0 : flag * 2 * unroll_unit - 1`` with ``flag = iteration_index // 10`` (a literal 10; with flag 0 the slice
+    ends at -1), the sums are Python floats, the sort is stable and descending, and ``[-k:]`` is the whole list when k = 0.
+    (a and b enter as Python floats of their float32 values.)"""
+    import math
+    result = []
+    k = int(ratio * len(curve_info))
+    flag = iteration_index // 10
+    curve_u = curve_info[:, 0:flag * 2 * unroll_unit - 1, 0]
+    for i in range(len(curve_u)):
+        a, b = float(batch_data[i, 0]), float(batch_data[i, 1])
+        grad_v = [(-1) * b * math.sin(a * math.pi * float(u)) for u in curve_u[i]]
+        result.append(sum([d ** 2 for d in grad_v]))
+    return sorted(range(len(result)), key=lambda i: result[i], reverse=True)[-k:]
+
+
+class Trainer(object):
+    """The two networks' parameters as torch tensors and their two ``torch.optim.Adam`` (default betas and eps,
+    ``lr = meta_lr``): the reference's meta-optimizers.  ``step`` assigns ``.grad`` from a segment's gradients, steps both
+    and writes the new values back into the two ``Optimizer``s' float32 arrays."""
+
+    def __init__(self, opt_min, opt_max, lr):
+        self.opts = (opt_min, opt_max)
+        self.tensors = tuple(collections.OrderedDict((k, torch.nn.Parameter(torch.from_numpy(o.params[k].copy())))
+                                                     for k in PARAM_NAMES) for o in self.opts)
+        self.adams = tuple(torch.optim.Adam(list(t.values()), lr=lr) for t in self.tensors)
+
+    def step(self, grads):
+        for o, t, adam, g in zip(self.opts, self.tensors, self.adams, grads):
+            for k in PARAM_NAMES:
+                t[k].grad = torch.from_numpy(np.ascontiguousarray(g[k], dtype=np.float32).reshape(tuple(t[k].shape)).copy())
+            adam.step()
+            for k in PARAM_NAMES:
+                o.params[k] = t[k].detach().numpy().copy()
+
+    def step_counts(self):
+        """Adam's step count of the min and of the max network (0 before the first step)."""
+        return tuple(int(next(iter(a.state.values()))["step"]) if a.state else 0 for a in self.adams)
+
+
+def train_batch(problem, trainer, optim_it, unroll_unit, rescale=1e-4, out_mul=1.0, theta0=None, states=None, seed=None,
+                curriculum=False, epoch_index=0, log=None):
+    """The reference's ``do_fit(should_train=True)`` on one batch -- every instance of `problem` -- with the networks and
+    Adams of `trainer`: optim_it iterations cut into segments of 2 unroll_unit; at each segment's end both Adams step on the
+    segment's gradient (iterations past the last whole segment run without a step).  curriculum (the config's ``CL``;
+    seesaw only): between a segment's forward and its backward ``get_index`` picks the instances that enter the loss from
+    the train-mode curve so far (which, as in the reference, does not yet hold the segment's last iteration); with none
+    picked there is no backward and no step.  A segment wholly inside the sign phase has zero gradients and still steps.
+    Returns (all_distance_ever_v, all_distance_ever_u, curve_info): the distances [batch, optim_it] and the train-mode
+    curve_info [batch, optim_it, 2 dim] (row k - 1: the point after iteration k).  log: a list that gets one dict per
+    segment (iter0, inst_weight, loss, stepped)."""
+    optim_it, unroll_unit = int(optim_it), int(unroll_unit)
+    if curriculum and problem.kind != SEESAW:
+        raise ValueError("twin.train_batch: the curriculum (CL) ranks instances by the seesaw's gradient, (-b sin(a pi u))^2: "
+                         "it is defined for loss 3 only (got loss %d)" % problem.kind)
+    if unroll_unit < 1:
+        raise ValueError("twin.train_batch: unroll_unit %d" % unroll_unit)
+    schedule(optim_it)
+    opt_min, opt_max = trainer.opts
+    if theta0 is None or states is None:
+        t0, s0 = draw_start(problem, opt_min, opt_max, seed)
+        theta0 = t0 if theta0 is None else theta0
+        states = s0 if states is None else states
+    n_inst, dim, L = problem.n_inst, problem.dim, 2 * unroll_unit
+    info = np.zeros((n_inst, optim_it, 2 * dim))
+    theta, iter0 = np.ascontiguousarray(theta0, dtype=np.float32), 1
+    while iter0 + L - 1 <= optim_it:
+        res, handle = _segment_forward(problem, opt_min, opt_max, optim_it, iter0, L, theta, states, rescale, out_mul, n_inst)
+        info[:, iter0 - 1:iter0 + L - 2] = res.curve[:, 1:L]
+        weight, stepped = None, True
+        if curriculum:
+            index = get_index(info, iter0 + L - 1, unroll_unit, problem.data, sche_ratio(epoch_index))
+            weight = np.zeros(n_inst, np.float32)
+            for b in index:
+                weight[b] += 1.0
+            stepped = len(index) > 0
+        info[:, iter0 + L - 2] = res.curve[:, L]
+        if stepped:
+            _segment_backward(res, handle, weight)
+            trainer.step(res.grads)
+        if log is not None:
+            log.append(dict(iter0=iter0, inst_weight=weight, loss=res.loss if stepped else None, stepped=stepped))
+        theta, states, iter0 = res.theta, res.states, iter0 + L
+    if iter0 <= optim_it:
+        res = unroll(problem, opt_min, opt_max, optim_it, rescale=rescale, out_mul=out_mul, theta0=theta, states=states,
+                     iter0=iter0, record=("curve",))
+        info[:, iter0 - 1:] = res.curve[:, 1:]
+    whole = Result(curve=np.concatenate([np.zeros((n_inst, 1, 2 * dim), np.float32), info.astype(np.float32)], axis=1))
+    du, dv = distances(problem, whole)
+    return dv, du, info
+
+
+def batch_seed(seed, epoch, batch):
+    """The seed of ``draw_start`` for batch `batch` of epoch `epoch` of a ``fit`` with config seed `seed`:
+    ``(seed * 1000003 + epoch) * 1000003 + batch + 1``, reduced mod 2^63.  (The reference draws every batch's start from the
+    global torch generator as it goes; here each batch's draw stands alone.)"""
+    return ((int(seed) * 1000003 + int(epoch)) * 1000003 + int(batch) + 1) % (1 << 63)
+
+
+EVAL_SEED = 70
+
+
+def evaluate(params, eval_prob, opt_min, opt_max):
+    """fit_optimizer's evaluation loss: every eval instance in ONE ``unroll`` launch of eval_optim_iter iterations, the mean
+    over instances of sum(dist_v^2 + dist_u^2) after the burn-in half."""
+    theta0, states = draw_start(eval_prob, opt_min, opt_max, seed=EVAL_SEED)
+    res = unroll(eval_prob, opt_min, opt_max, params["eval_optim_iter"], rescale=params["rescale"], out_mul=1.0, theta0=theta0,
+                 states=states, record=("curve",))
+    du, dv = distances(eval_prob, res)
+    burn = int(0.5 * params["eval_optim_iter"])
+    du, dv = np.asarray(du, np.float64)[:, burn:], np.asarray(dv, np.float64)[:, burn:]
+    return float(np.mean(np.sum(np.square(dv) + np.square(du), axis=1)))
+
+
+def fit(params, root, out, epochs=None, eval_interval=5, verbose=False):
+    """The reference's ``fit_optimizer`` for a ``*_train.json`` config (dict `params`; paths relative to `root`; results under
+    `out`).  Per epoch: the training rows are shuffled by ``RandomState(10)`` -- the stream of the reference's
+    ``np.random.seed(10)`` / ``np.random.shuffle`` -- (the matrix game's on their reshaped [n, dim, dim] form);
+    ``n_train // batch_size`` batches of ``train_batch``, each from a start drawn by ``draw_start(seed=batch_seed(seed, epoch,
+    batch))``; ``epoch{e}min.pth`` / ``epoch{e}max.pth`` (``torch.save`` of the reference-named state dict); with
+    ``save_curve`` every instance's train-mode curve under ``curve_info/epoch{e}/`` by the reference's names; every
+    eval_interval epochs ``evaluate`` and, on improvement, ``bestmin.pth`` / ``bestmax.pth``.  The networks are seeded `seed`
+    and `seed + 1`.  ``save_train`` (the reference's seaborn plots) is read and ignored.  Data files shorter than n_train / n_eval are used as
+    far as they go, with a warning.  Returns (best_loss, opt_min,
+    opt_max, history: one dict per epoch)."""
+    dim, loss = int(params.get("dim", 1)), int(params["loss"])
+    curriculum = bool(params.get("CL", 0))
+    if curriculum and loss != SEESAW:
+        raise ValueError("twin.fit: \"CL\": 1 ranks instances by the seesaw's gradient: loss 3 only (got loss %d)" % loss)
+    n_train, n_eval, batch = int(params["n_train"]), int(params["n_eval"]), int(params["batch_size"])
+    epochs = int(params["train_epochs"] if epochs is None else epochs)
+
+    def find(rel):
+        for q in (os.path.join(root, rel), os.path.join(root, os.path.basename(rel))):
+            if os.path.exists(q):
+                return q
+        raise FileNotFoundError("twin.fit: %s not found under %s" % (rel, root))
+
+    train = np.loadtxt(find(params["train_data_path"]), ndmin=2).astype(np.float32)[:n_train]
+    evald = np.loadtxt(find(params["eval_data_path"]), ndmin=2).astype(np.float32)[:n_eval]
+    if train.shape[0] < n_train or evald.shape[0] < n_eval or n_train < batch:
+        # (the reference slices [0:n_train] without a check and then fails on the first batch; a short file -- the truncated
+        # fixtures of tests/golden/twin -- trains on what it holds, in one batch at the most, and says so)
+        import warnings
+        warnings.warn("twin.fit: n_train = %d, n_eval = %d, batch_size = %d but the data holds %d and %d instances: using "
+                      "what is there" % (n_train, n_eval, batch, train.shape[0], evald.shape[0]))
+        n_train, n_eval = min(n_train, train.shape[0]), min(n_eval, evald.shape[0])
+        batch = min(batch, n_train)
+    if batch < 1 or n_eval < 1:
+        raise ValueError("twin.fit: batch_size = %d, n_eval = %d" % (batch, n_eval))
+    if loss == MATRIX_GAME:
+        train, evald = train.reshape(n_train, dim, dim), evald.reshape(n_eval, dim, dim)
+    eval_prob = Problem(loss, evald, dim)
+    seed = int(params.get("seed", 0))
+    opts = tuple(Optimizer(hidden_size=params["hidden_size"], use_second=bool(params["use_second"]), seed=seed + i)
+                 for i in range(2))
+    trainer = Trainer(opts[0], opts[1], lr=params["meta_lr"])
+    rng = np.random.RandomState(10)
+    os.makedirs(out, exist_ok=True)
+    best, history = 100000000000000000, []
+    for epoch in range(epochs):
+        rng.shuffle(train)
+        for it in range(n_train // batch):
+            rows = train[it * batch:(it + 1) * batch]
+            prob = Problem(loss, rows, dim)
+            theta0, states = draw_start(prob, opts[0], opts[1], seed=batch_seed(seed, epoch, it))
+            dv, du, info = train_batch(prob, trainer, params["train_optim_iter"], params["unroll_unit"],
+                                       rescale=params["rescale"], out_mul=1.0, theta0=theta0, states=states,
+                                       curriculum=curriculum, epoch_index=epoch)
+            if params.get("save_curve"):
+                cdir = os.path.join(out, "curve_info", "epoch%d" % epoch)
+                os.makedirs(cdir, exist_ok=True)
+                for i in range(batch):
+                    first, last = float(rows[i].reshape(-1)[0]), float(rows[i].reshape(-1)[-1])
+                    np.savetxt(os.path.join(cdir, "iteration%d_batch_index_%d_u_%s_v_%s.txt"
+                                            % (it, i, round(first, 3), round(last, 3))), info[i])
+        for o, which in zip(opts, ("min", "max")):
+            torch.save(o.state_dict(), os.path.join(out, "epoch%d%s.pth" % (epoch, which)))
+        entry = dict(epoch=epoch, steps=trainer.step_counts(), eval_loss=None)
+        if epoch % int(eval_interval) == 0:
+            entry["eval_loss"] = evaluate(params, eval_prob, opts[0], opts[1])
+            if entry["eval_loss"] < best:
+                best = entry["eval_loss"]
+                for o, which in zip(opts, ("min", "max")):
+                    torch.save(o.state_dict(), os.path.join(out, "best%s.pth" % which))
+        history.append(entry)
+        if verbose:
+            print(entry)
+    return best, opts[0], opts[1], history

@@ -11,7 +11,8 @@ ships no trained weights: with --random-weights, when those files are absent, th
 the config's seed.  All ``n_test x test_epochs`` runs (instance j, restart i -> row j * test_epochs + i) go out in ONE launch.
 Writes, under --out (default ``<root>/result/<save_name>``): every run's curve_info as the reference names it, and
 ``twin_eval.json`` with the mean distances after the burn-in half and the evaluation loss of fit_optimizer
-(mean over runs of sum(dist_v^2 + dist_u^2) after the burn-in).  ``mode: "train"`` is refused: meta-training is not built.
+(mean over runs of sum(dist_v^2 + dist_u^2) after the burn-in).  ``mode: "train"`` is refused here: meta-training is
+``scripts/train_twin.py``, whose ``best{min,max}.pth`` / ``epoch{e}{min,max}.pth`` this script loads through load_name / load_model.
 """
 import argparse
 import json
@@ -33,8 +34,8 @@ def load_config(path):
         params = json.load(f)
     params["dim"] = params.get("dim", 1)
     if params.get("mode") == "train":
-        raise NotImplementedError("evaluate_twin: mode \"train\": meta-training of the twin networks (BPTT over 2 * unroll_unit "
-                                  "iterations, the curriculum) is not built; only the evaluation unroll (mode \"test\") is")
+        raise NotImplementedError("evaluate_twin: mode \"train\": meta-training of the twin networks is "
+                                  "scripts/train_twin.py; this script runs the evaluation unroll (mode \"test\") alone")
     if params.get("mode") != "test":
         raise ValueError("evaluate_twin: mode %r" % (params.get("mode"),))
     return params
