@@ -1,8 +1,6 @@
 /* l2o_twin_train_abi.h -- Twin-L2O meta-training: one segment of the reference's do_fit(should_train=True) -- its forward
  * with a history, and the meta-gradient of both networks from that history.  Part of the C ABI of libl2o_hip.so beside
- * include/l2o_twin_abi.h (objectives, network and state layouts, iteration rule: there).  It lives here, and its prototypes
- * in a table of their own in open_l2o_amd/_abi.py, until a change that may touch the tests that pin the file list of
- * include/ folds both in.
+ * l2o_twin_abi.h (objectives, network and state layouts, iteration rule: there).
  *
  * The segment.  Iterations iter0 .. iter0 + n_iter - 1 with iter0 odd and n_iter even (the reference: 2 unroll_unit), so a
  * segment starts with a min step and ends with a max step.  Its loss is
@@ -20,7 +18,7 @@
 #ifndef L2O_TWIN_TRAIN_ABI_H
 #define L2O_TWIN_TRAIN_ABI_H
 
-#include "../../include/l2o_twin_abi.h"
+#include "l2o_twin_abi.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in ``include/l2o_abi.h``.
+"""ctypes binding of the C ABI declared in the headers of ``include/``.
 
 This is the ONLY way the Python host reaches the compute path: there is no
 PyTorch / NumPy fallback.  If ``libl2o_hip.so`` is missing (not built) every
@@ -154,7 +154,8 @@ class Mlp(C.Structure):
     ]
 
 
-class MlpHist(C.Structure):            # l2o_mlp_hist: per variable (w1, b1, w2, b2) history of l2o_mlp_unroll_record
+class MlpHist(C.Structure):            # per variable (w1, b1, w2, b2) history of l2o_mlp_unroll_record
+    """struct l2o_mlp_hist"""
     _fields_ = [("st", C.c_void_p * 4), ("g", C.c_void_p * 4), ("m", C.c_void_p * 4), ("v", C.c_void_p * 4)]
 
 
@@ -184,7 +185,7 @@ class Lenet(ImageNet):
 
 
 class Nas(ImageNet):
-    """struct l2o_nas (include/l2o_nas_abi.h)"""
+    """struct l2o_nas"""
 
 
 class Confocal(C.Structure):
@@ -196,7 +197,8 @@ class Confocal(C.Structure):
 CONFOCAL_MAX_VARS = 49     # L2O_CONFOCAL_MAX_VARS: 6 * 8 points + 1
 
 
-class ConfocalHist(C.Structure):       # l2o_confocal_hist: per variable history of l2o_confocal_unroll_record
+class ConfocalHist(C.Structure):       # per variable history of l2o_confocal_unroll_record
+    """struct l2o_confocal_hist"""
     _fields_ = [("st", C.c_void_p * CONFOCAL_MAX_VARS), ("g", C.c_void_p * CONFOCAL_MAX_VARS),
                 ("m", C.c_void_p * CONFOCAL_MAX_VARS), ("v", C.c_void_p * CONFOCAL_MAX_VARS)]
 
@@ -204,18 +206,20 @@ class ConfocalHist(C.Structure):       # l2o_confocal_hist: per variable history
 CONFOCAL_MAX_INSTANCES = 32     # L2O_CONFOCAL_MAX_INSTANCES
 
 
-class ConfocalInstance(C.Structure):   # l2o_confocal_instance: one replica of l2o_confocal_unroll_multi
+class ConfocalInstance(C.Structure):   # one replica of l2o_confocal_unroll_multi
+    """struct l2o_confocal_instance"""
     _fields_ = [(n, C.c_void_p * CONFOCAL_MAX_VARS) for n in ("x", "st", "m", "v", "x_scale", "sim")] + \
                [("img", C.c_void_p), ("fx", C.c_void_p)]
 
 
-class MlpInstance(C.Structure):        # l2o_mlp_instance: one replica of l2o_mlp_unroll_multi
+class MlpInstance(C.Structure):        # one replica of l2o_mlp_unroll_multi
+    """struct l2o_mlp_instance"""
     _fields_ = [("indices", C.c_void_p), ("x", C.c_void_p * 4), ("st", C.c_void_p * 4), ("m", C.c_void_p * 4),
                 ("v", C.c_void_p * 4), ("x_scale", C.c_void_p * 4), ("fx", C.c_void_p)]
 
 
 class Vgg16(C.Structure):
-    """struct l2o_vgg16 (include/l2o_vgg16_abi.h)"""
+    """struct l2o_vgg16"""
     _fields_ = [("batch", C.c_int32), ("n_data", C.c_int32), ("flags", C.c_int32), ("channels", C.c_int32 * 5),
                 ("images", C.c_void_p), ("labels", C.c_void_p)]
 
@@ -242,7 +246,7 @@ class GenBwdIO(C.Structure):
 
 
 class KlstmNet(C.Structure):
-    """struct l2o_klstm_net (include/l2o_klstm_abi.h)"""
+    """struct l2o_klstm_net"""
     _fields_ = [("kw", C.c_int32), ("kh", C.c_int32), ("n_layers", C.c_int32), ("hidden", C.c_int32 * 2),
                 ("preprocess", C.c_int32), ("tanh_output", C.c_int32), ("flags", C.c_int32), ("logsign_k", C.c_double),
                 ("scale", C.c_double), ("w_gates", C.c_void_p * 2), ("b_gates", C.c_void_p * 2), ("w_lin", C.c_void_p),
@@ -277,7 +281,7 @@ class TwinRun(C.Structure):
                 ("out_mul", C.c_float), ("sign_lr", C.c_void_p)]
 
 
-TWIN_TRAIN_MAX_ITER = 64                                                        # L2O_TWIN_TRAIN_MAX_ITER (csrc/l2o_twin_train_abi.h)
+TWIN_TRAIN_MAX_ITER = 64                                                        # L2O_TWIN_TRAIN_MAX_ITER (include/l2o_twin_train_abi.h)
 
 
 class TwinSegment(C.Structure):
@@ -342,6 +346,7 @@ def _prototypes():
     P, vp, i32, i64, dbl, flt, I, Z = C.POINTER, C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float, C.c_int, C.c_size_t
     cfg, prob, mlp, conf = P(NetCfg), P(Problem), P(Mlp), P(Confocal)
     bwd_unroll = [cfg, P(NetWeights), P(BwdUnrollSeg), i32, vp, i32, i64, vp, vp, vp, vp, vp]
+    twin = [P(TwinNet), P(TwinNet), P(TwinProblem)]
     return {
         "l2o_abi.h": {
             "l2o_abi_version": (I, []),
@@ -427,41 +432,22 @@ def _prototypes():
             "l2o_klstm_bwd_step": (I, [P(KlstmNet), P(KlstmBwdIO), i64, vp]),
         },
         "l2o_twin_abi.h": {                  # twin.unroll: the Twin-L2O minimax evaluation unroll
-            "l2o_twin_supported": (I, [P(TwinNet), P(TwinNet), P(TwinProblem)]),
+            "l2o_twin_supported": (I, twin),
             "l2o_twin_state_floats": (Z, [P(TwinNet), i64]),
-            "l2o_twin_unroll": (I, [P(TwinNet), P(TwinNet), P(TwinProblem), P(TwinRun)] + [vp] * 7),
+            "l2o_twin_unroll": (I, twin + [P(TwinRun)] + [vp] * 7),
+        },
+        "l2o_twin_train_abi.h": {            # twin.meta_gradient: one segment of the Twin-L2O meta-training
+            "l2o_twin_train_floats": (Z, twin + [i32]),
+            "l2o_twin_train_forward": (I, twin + [P(TwinSegment)] + [vp] * 8),
+            "l2o_twin_train_backward": (I, twin + [P(TwinSegment), vp, P(TwinGrad), P(TwinGrad), vp]),
         },
     }
 
 
 # THE prototype table: header of include/ -> {symbol: (restype, argtypes)}, every symbol the header declares, in this
-# binding's order.  declare() gives a loaded library exactly these prototypes and refuses one that lacks any of them; the
-# per-header tuples below are views of it (tests hold each against its header's text).
+# binding's order.  declare() gives a loaded library exactly these prototypes and refuses one that lacks any of them
+# (tests/test_abi_headers_cpu.py holds the table, the structs and the constants above to the headers' text).
 PROTOTYPES = _prototypes()
-SYMBOLS, CONFOCAL_UNROLL_SYMBOLS, CONFOCAL_MULTI_SYMBOLS, MLP_HVP_SYMBOLS, VGG16_SYMBOLS, NAS_SYMBOLS, KLSTM_SYMBOLS, \
-    TWIN_SYMBOLS = (
-        tuple(PROTOTYPES[h]) for h in ("l2o_abi.h", "l2o_confocal_unroll_abi.h", "l2o_confocal_multi_abi.h", "l2o_mlp_hvp_abi.h",
-                                       "l2o_vgg16_abi.h", "l2o_nas_abi.h", "l2o_klstm_abi.h", "l2o_twin_abi.h"))
-
-
-def _twin_train_prototypes():
-    P, vp, I, Z = C.POINTER, C.c_void_p, C.c_int, C.c_size_t
-    head = [P(TwinNet), P(TwinNet), P(TwinProblem)]
-    return {
-        "l2o_twin_train_abi.h": {            # twin.meta_gradient: one segment of the Twin-L2O meta-training
-            "l2o_twin_train_floats": (Z, head + [C.c_int32]),
-            "l2o_twin_train_forward": (I, head + [P(TwinSegment)] + [vp] * 8),
-            "l2o_twin_train_backward": (I, head + [P(TwinSegment), vp, P(TwinGrad), P(TwinGrad), vp]),
-        },
-    }
-
-
-# A second table, header of csrc/ -> {symbol: (restype, argtypes)}: the meta-training entry points of the Twin-L2O family.
-# lib() applies it after declare() and refuses a library that lacks one of its symbols in the same way.  (It stands outside
-# PROTOTYPES, and its header outside include/, because tests pin that table's size and its keys to include/'s file list; a
-# change that may touch those tests folds both in.)
-TWIN_TRAIN_PROTOTYPES = _twin_train_prototypes()
-TWIN_TRAIN_SYMBOLS = tuple(TWIN_TRAIN_PROTOTYPES["l2o_twin_train_abi.h"])
 
 
 class L2OError(RuntimeError):
@@ -522,22 +508,18 @@ def last_unroll_variant():
             "NV": (w >> 12) & 3}
 
 
-def _declare(library, table):
-    missing = [name for protos in table.values() for name in protos if not hasattr(library, name)]
+def declare(library):
+    """Give every symbol of PROTOTYPES its restype / argtypes on the loaded `library` and return it.  The library is built
+    from this tree, so one that lacks a listed symbol is a stale file: it is refused whole, at load."""
+    missing = [name for protos in PROTOTYPES.values() for name in protos if not hasattr(library, name)]
     if missing:
         raise RuntimeError("open_l2o_amd: %s has no %s: the library is stale (built from older sources) -- rebuild it with "
                            "`make -C open_l2o_amd/csrc`" % (LIB_PATH, ", ".join(missing)))
-    for protos in table.values():
+    for protos in PROTOTYPES.values():
         for name, (restype, argtypes) in protos.items():
             fn = getattr(library, name)
             fn.restype, fn.argtypes = restype, argtypes
     return library
-
-
-def declare(library):
-    """Give every symbol of PROTOTYPES its restype / argtypes on the loaded `library` and return it.  The library is built
-    from this tree, so one that lacks a listed symbol is a stale file: it is refused whole, at load."""
-    return _declare(library, PROTOTYPES)
 
 
 def lib():
@@ -549,7 +531,7 @@ def lib():
         raise RuntimeError(
             "open_l2o_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C open_l2o_amd/csrc`.  There is no CPU fallback." % LIB_PATH)
-    L = _declare(declare(C.CDLL(LIB_PATH)), TWIN_TRAIN_PROTOTYPES)
+    L = declare(C.CDLL(LIB_PATH))
     if L.l2o_abi_version() != L2O_ABI_VERSION:
         raise RuntimeError("libl2o_hip.so ABI version %d != binding version %d"
                            % (L.l2o_abi_version(), L2O_ABI_VERSION))

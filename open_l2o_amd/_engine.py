@@ -277,7 +277,7 @@ class TwinDevice(object):
                                           C.byref(self.run), _ptr(theta), _ptr(state_min), _ptr(state_max), _ptr(curve),
                                           _ptr(fval), _ptr(delta), stream)
 
-    # -- one segment of the meta-training (csrc/l2o_twin_train_abi.h) ------------------------------------------
+    # -- one segment of the meta-training (include/l2o_twin_train_abi.h) ---------------------------------------
     def segment(self, loss_scale, inst_weight=None):
         """struct l2o_twin_segment of this run; inst_weight: None or a device tensor [n_inst]."""
         self.keep.append(inst_weight)

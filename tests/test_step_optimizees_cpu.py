@@ -1,12 +1,10 @@
 """The Python host layer of the step-path optimizees (problems.mnist with several hidden layers, mnist_conv, cifar10, LeNet,
 confocal_microscopy_3d, vgg16_cifar10, NAS) is one table, _engine.STEP_OPTIMIZEES, and what reads it.  Pinned here, as
-literals: every kind's entry and the predicates that read the table, the symbols and structs of the binding (one prototype
-table, _abi.PROTOTYPES, which a library must export whole), the public names and signatures that tests,
+literals: every kind's entry and the predicates that read the table, the kinds' symbols and structs in the binding (the
+whole of it against the headers: test_abi_headers_cpu.py), the public names and signatures that tests,
 scripts and oracle engines use, and the texts of the refusals -- in the factories (no GPU) and in the engine (GPU)."""
 import ctypes as C
-import hashlib
 import inspect
-import os
 
 import numpy as np
 import pytest
@@ -73,70 +71,13 @@ def test_derived_kind_tuples():
 def test_symbols_are_declared():
     import __graft_entry__  # noqa: F401
     lib = _abi.lib()
-    home = {5: _abi.SYMBOLS, 6: _abi.SYMBOLS, 7: _abi.SYMBOLS, 8: _abi.SYMBOLS, 9: _abi.SYMBOLS, 10: _abi.VGG16_SYMBOLS,
-            11: _abi.NAS_SYMBOLS}                              # (the header that declares the kind's two symbols)
+    home = {k: _abi.PROTOTYPES["l2o_abi.h"] for k in (5, 6, 7, 8, 9)}         # (the header that declares the kind's two symbols)
+    home.update({10: _abi.PROTOTYPES["l2o_vgg16_abi.h"], 11: _abi.PROTOTYPES["l2o_nas_abi.h"]})
     for k, e in STEP_OPTIMIZEES.items():
         floats, fg = e.stem + "_scratch_floats", e.stem + "_fg"
         assert k not in home or (floats in home[k] and fg in home[k])
         assert getattr(lib, floats).restype is C.c_size_t and getattr(lib, floats).argtypes == [C.POINTER(e.struct)]
         assert getattr(lib, fg).restype is C.c_int and getattr(lib, fg).argtypes == [C.POINTER(e.struct)] + [C.c_void_p] * 6
-    # the list and its order, as before the table existed (sha256 of the names joined by blanks)
-    assert len(_abi.SYMBOLS) == len(set(_abi.SYMBOLS)) == 66 and _abi.L2O_ABI_VERSION == 15
-    assert hashlib.sha256(" ".join(_abi.SYMBOLS).encode()).hexdigest()[:16] == "9551088b6b88e711"
-    assert _abi.SYMBOLS[23:33] == (
-        "l2o_mlp_deep_fg", "l2o_mlp_deep_scratch_floats", "l2o_mnist_conv_fg", "l2o_mnist_conv_scratch_floats",
-        "l2o_cifar_conv_fg", "l2o_cifar_conv_scratch_floats", "l2o_lenet_fg", "l2o_lenet_scratch_floats",
-        "l2o_confocal_fg", "l2o_confocal_scratch_floats")
-
-
-SYMBOL_TUPLES = ("SYMBOLS", "CONFOCAL_UNROLL_SYMBOLS", "CONFOCAL_MULTI_SYMBOLS", "MLP_HVP_SYMBOLS", "VGG16_SYMBOLS",
-                 "NAS_SYMBOLS", "KLSTM_SYMBOLS", "TWIN_SYMBOLS")
-
-
-def test_every_listed_symbol_has_a_prototype():
-    listed = [name for t in SYMBOL_TUPLES for name in getattr(_abi, t)]
-    table = {name: proto for protos in _abi.PROTOTYPES.values() for name, proto in protos.items()}
-    assert len(listed) == len(set(listed)) == 87 and set(listed) == set(table)
-    assert sum(len(protos) for protos in _abi.PROTOTYPES.values()) == 87         # (no symbol under two headers)
-    for name in listed:
-        restype, argtypes = table[name]
-        assert restype in (C.c_int, C.c_int32, C.c_int64, C.c_size_t, C.c_char_p) and type(argtypes) is list, name
-        if name.endswith(("_scratch_floats", "_workspace_bytes", "_state_floats", "l2o_wpack_floats")):
-            assert restype is C.c_size_t, name                                    # (ctypes' default int would truncate it)
-    for struct, stem in _abi.STEP_FG:
-        assert table[stem + "_fg"] == (C.c_int, [C.POINTER(struct)] + [C.c_void_p] * 6)
-        assert table[stem + "_scratch_floats"] == (C.c_size_t, [C.POINTER(struct)])
-    assert [stem for _, stem in _abi.STEP_FG] == ["l2o_mlp_deep", "l2o_mnist_conv", "l2o_cifar_conv", "l2o_lenet",
-                                                  "l2o_confocal", "l2o_vgg16", "l2o_nas"]
-    # the headers of include/ are the table's keys, and the loaded library carries exactly the table's prototypes
-    import __graft_entry__
-    assert sorted(_abi.PROTOTYPES) == sorted(os.listdir(os.path.join(__graft_entry__.ROOT, "include")))
-    lib = _abi.lib()
-    for name, (restype, argtypes) in table.items():
-        assert getattr(lib, name).restype is restype and getattr(lib, name).argtypes == argtypes, name
-
-
-class _Without(object):
-    """Stands in for a loaded library that exports every listed symbol but `missing`."""
-
-    def __init__(self, *missing):
-        for protos in _abi.PROTOTYPES.values():
-            for name in protos:
-                if name not in missing:
-                    setattr(self, name, type("fn", (), {})())
-
-
-def test_a_library_that_lacks_a_listed_symbol_is_refused_at_load():
-    whole = _Without()
-    assert _abi.declare(whole) is whole
-    assert whole.l2o_nas_scratch_floats.restype is C.c_size_t and whole.l2o_klstm_step.argtypes[0] is C.POINTER(_abi.KlstmNet)
-    for missing in (("l2o_klstm_bwd_step",), ("l2o_abi_version",), ("l2o_confocal_unroll_multi", "l2o_vgg16_fg")):
-        stale = _Without(*missing)
-        with pytest.raises(RuntimeError) as ei:
-            _abi.declare(stale)
-        assert str(ei.value) == ("open_l2o_amd: %s has no %s: the library is stale (built from older sources) -- rebuild it "
-                                 "with `make -C open_l2o_amd/csrc`" % (_abi.LIB_PATH, ", ".join(missing)))
-        assert not hasattr(stale.l2o_build_id, "restype")                         # (refused whole: nothing was declared)
 
 
 def test_image_net_structs():

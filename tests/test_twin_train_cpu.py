@@ -1,6 +1,6 @@
 """open_l2o_amd.twin's meta-training on the CPU: the closed-form seed the kernels implement against autograd of the reference's
 graph (twin_train_reference.py), the host logic of train_batch / fit on TorchTwinTrainEngine against the oracle's do_fit loop,
-get_index's edge cases, the driver end to end, and the binding held to the text of csrc/l2o_twin_train_abi.h."""
+get_index's edge cases, the driver end to end, and the library's refusals before any launch."""
 import ctypes as C
 import importlib.util
 import json
@@ -176,55 +176,9 @@ def test_train_twin_end_to_end(tmp_path, name):
     assert 0 < moved <= cfg["meta_lr"] * 10 * (1 + 1e-3)
 
 
-# the binding held to the text of csrc/l2o_twin_train_abi.h
-def train_header():
-    import __graft_entry__
-    with open(os.path.join(__graft_entry__.ROOT, "open_l2o_amd", "csrc", "l2o_twin_train_abi.h")) as f:
-        return _abi.lib(), re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-
-
-def test_train_header_symbols_are_the_second_table():
-    lib, text = train_header()
-    declared = set(re.findall(r"\b(l2o_\w+)\s*\(", text))
-    assert declared == set(_abi.TWIN_TRAIN_SYMBOLS) and len(_abi.TWIN_TRAIN_SYMBOLS) == 3
-    assert _abi.TWIN_TRAIN_SYMBOLS == tuple(_abi.TWIN_TRAIN_PROTOTYPES["l2o_twin_train_abi.h"])
-    assert not any(declared & set(protos) for protos in _abi.PROTOTYPES.values())
-    assert all(hasattr(lib, name) and getattr(lib, name).argtypes is not None for name in declared)
-    assert lib.l2o_abi_version() == 15 and _abi.source_build_id() == _abi.build_id()
-
-
-def test_declare_asks_for_the_first_table_alone_and_lib_for_both(monkeypatch):
-    class Fn(object):
-        pass
-    first = type("Lib", (), {})()
-    for protos in _abi.PROTOTYPES.values():
-        for name in protos:
-            setattr(first, name, Fn())
-    assert sum(len(p) for p in _abi.PROTOTYPES.values()) == 87
-    assert _abi.declare(first) is first                                       # a library with the 87 alone is whole for declare()
-    monkeypatch.setattr(_abi, "_lib", None)
-    monkeypatch.setattr(_abi.C, "CDLL", lambda path: first)
-    with pytest.raises(RuntimeError, match=r"has no l2o_twin_train_floats, l2o_twin_train_forward, l2o_twin_train_backward: "
-                                           r"the library is stale"):
-        _abi.lib()
-
-
-def test_train_header_structs_are_the_bindings():
-    _, text = train_header()
-    ctype = {"int32_t": C.c_int32, "float": C.c_float, "l2o_twin_run": _abi.TwinRun}
-    for S, name, size in ((_abi.TwinSegment, "l2o_twin_segment", 48), (_abi.TwinGrad, "l2o_twin_grad", 80)):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, flags=re.S).group(1)
-        fields = []
-        for decl in filter(None, (d.strip() for d in body.split(";"))):
-            base, rest = re.match(r"(?:const\s+)?(\w+)\s*(.*)", decl, flags=re.S).groups()
-            fields += [(n, C.c_void_p if star else ctype[base]) for star, n in re.findall(r"(\*?)\s*(\w+)\s*(?:,|$)", rest)]
-        assert S._fields_ == fields and S.__doc__ == "struct " + name, name
-        assert C.sizeof(S) == size, name
-    assert int(re.search(r"#define L2O_TWIN_TRAIN_MAX_ITER (\d+)", text).group(1)) == _abi.TWIN_TRAIN_MAX_ITER == 64
-
-
 def test_train_refusals_before_any_launch():
-    lib, _ = train_header()
+    import __graft_entry__  # noqa: F401
+    lib = _abi.lib()
     net = _abi.TwinNet(50, 2)
     prob = _abi.TwinProblem(_abi.TWIN_SEESAW, 3, 1, 0, None)
     head = (C.byref(net), C.byref(net), C.byref(prob))
